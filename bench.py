@@ -108,6 +108,45 @@ def cpu_baseline(g_arrays, reads_concat, read_off, k, w, budget_s=6.0):
     return out
 
 
+DUMP_HITS_MAX = 1 << 22          # flags written whole up to this many (16 MB as float32), else a sample of half as many + indices
+DUMP_SPECTRUM_MAX = 1 << 20      # hashes written whole up to this many (2 x 8 MB as float64), else a sample of as many + indices
+DUMP_BYTES_MAX = 64 << 20
+
+
+def _sample(a, whole_max, n, seed):
+    """(a, None) when a has at most `whole_max` elements, else a fixed seeded sample of n of them and their (ascending) indices."""
+    if len(a) <= whole_max:
+        return a, None
+    idx = np.sort(np.random.default_rng(seed).choice(len(a), size=n, replace=False))
+    return a[idx], idx
+
+
+def step_outputs(ctx, dev):
+    """What the context holds after a step, as a caller of the step receives it: the hit vector (phi_hits_buffer, one flag
+    per distinct walk minimiser by dense id), the read counters (phi_reads_stats) and the distinct read hashes that are not
+    walk minimisers (phi_spectrum_export, sorted; split into 32-bit halves so that float64 holds them exactly).  Arrays
+    beyond DUMP_*_MAX are a seeded sample, with `<name>_index` beside them.  {name: float32 / float64 array}"""
+    import torch
+    from phi_amd import dist as pdist
+    p, n = ctx.hits_buffer()
+    hits = torch.as_tensor(pdist.DevArray(p, n), device=dev).cpu().numpy() if n else np.zeros(0, np.uint8)
+    c = ctx.reads_stats()
+    out = {"read_counts": np.array([c["n_reads"], c["n_bases"], c["n_emitted"], c["n_distinct"]], np.float64)}
+    v, idx = _sample(hits, DUMP_HITS_MAX, DUMP_HITS_MAX // 2, 1)
+    out["hits"] = v.astype(np.float32)
+    if idx is not None:
+        out["hits_index"] = idx.astype(np.float64)
+    p, n = ctx.spectrum_export()
+    sp = torch.as_tensor(pdist.DevArray(p, n, "<i8"), device=dev).cpu().numpy().view(np.uint64) if n else np.zeros(0, np.uint64)
+    v, idx = _sample(np.sort(sp), DUMP_SPECTRUM_MAX, DUMP_SPECTRUM_MAX, 2)
+    out["spectrum_hi32"] = (v >> np.uint64(32)).astype(np.float64)
+    out["spectrum_lo32"] = (v & np.uint64(0xFFFFFFFF)).astype(np.float64)
+    if idx is not None:
+        out["spectrum_index"] = idx.astype(np.float64)
+    assert sum(a.nbytes for a in out.values()) <= DUMP_BYTES_MAX
+    return out
+
+
 def _phi_stage_table(stderr):
     """The stage table PHI prints under PHI_TIMING=1: {stage: [begin_s, end_s]} on the process's own clock, plus the
     epochs of main() and of the closed FASTA."""
@@ -221,7 +260,12 @@ def main():
                     help="N > 1: the per-read-set exchange of the hit vectors.  ipc: every rank maps the others' vectors and ORs them with one kernel on a "
                          "stream of its own, beside the next read set's scoring (phi_ipc_*); rccl: ncclAllReduce inside the library (phi_comm_*); "
                          "auto: ipc for hit vectors of up to 4 M flags (every MHC-sized graph), rccl beyond, and rccl when the ipc group cannot be set up or fails its check")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (rank 0) as DIR/<name>.npy, float32 / float64, "
+                         f"at most {DUMP_BYTES_MAX >> 20} MB (see step_outputs); the inputs are the same in every run with the same arguments")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import __graft_entry__
@@ -455,6 +499,13 @@ def main():
     for _ in range(args.warmup):
         primary_step()
     elapsed = timed(primary_step, args.steps, 0)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        dumped = {}
+        for name, a in step_outputs(ctx, dev).items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+            dumped[name] = len(a)
     # the kernel's own duration: a leg of its own, the same step with EVERY sketch launch bracketed by HIP events on the
     # stream the kernel runs on (the timed steps above carry no events: a bracketed launch costs the stream ~5 us more)
     ctx.prof_read()                                            # drop earlier timings
@@ -652,6 +703,8 @@ def main():
         "end_to_end_s": None, "end_to_end_one_process_s": None, "back_to_back_s": None, "end_to_end_detached_s": None, "several_jobs_per_read_set_s": None,
         "synthetic_gen_s": t_gen,
     }
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "lengths": dumped}
     if step_split is not None:
         out["step_split"] = step_split
     if other is not None:

@@ -3,6 +3,8 @@
 
   murmur_vectors.json   inputs + outputs of the REFERENCE's MurmurHash3_x64_128 (folded h1^h2 as in
                         ILP_index.cpp:10-18), produced by the reference's own MurmurHash3.cpp
+  murmur_random_vectors.json  the same for random bytes of every length 0 .. 69 (numpy seed 3: the inputs of
+                        tests/test_cpu_oracle.py::test_murmur_matches_reference_build_when_present)
   gfa_flatten.json      segments / arcs / walks of test/test.gfa as the REFERENCE's gfa_read() parses
                         them, flattened as ILP_index::read_gfa does; plus digests for test/MHC_4.gfa.gz
   hap_names.json        outputs of the reference's get_hap_name() (misc.cpp:58-87)
@@ -24,6 +26,16 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 from oracle import oracle as O  # noqa: E402
 
 
+def murmur_random_vectors(R):
+    import numpy as np
+    rng = np.random.default_rng(3)
+    vec = []
+    for n in range(0, 70):
+        b = bytes(rng.integers(0, 256, size=n, dtype=np.uint8).tolist())
+        vec.append({"hex": b.hex(), "hash": str(R.ref_hash128_to_64(b, n))})
+    json.dump(vec, open(os.path.join(HERE, "murmur_random_vectors.json"), "w"), indent=0)
+
+
 def main():
     R = O.ref()
     rnd = random.Random(20251003)
@@ -33,6 +45,7 @@ def main():
             b = bytes(rnd.choice(b"ACGT") for _ in range(n)) if rnd.random() < 0.7 else bytes(rnd.randrange(256) for _ in range(n))
             vec.append({"hex": b.hex(), "hash": str(R.ref_hash128_to_64(b, n))})
     json.dump(vec, open(os.path.join(HERE, "murmur_vectors.json"), "w"), indent=0)
+    murmur_random_vectors(R)
 
     data = os.path.join(HERE, "data")
     g = O.ref_parse_gfa(os.path.join(data, "test.gfa"))
