@@ -1299,7 +1299,7 @@ int phi_add_reads_device_impl(phi_ctx *c, const void *d_bases, const void *d_rea
     // this batch's part of the log of novel hashes: 1 << nov_shift entries per chunk, behind the chunks logged so far.
     // A log that has no room grows -- keeping what it holds -- up to 1 GB; beyond that what it holds is entered into
     // the set (sp_flush) and the log starts over.  (A batch larger than the log has it made as large as the batch.)
-    const int64_t n_log_chunks = phi_sketch_num_blocks(n_bases);
+    const int64_t n_log_chunks = phi_sketch_read_chunks(c->k, c->w, uniform_len, n_reads, n_bases);
     if (replay) c->log_chunks -= c->last_log_chunks;          // the same entries again
     {
         const size_t ent = (size_t)8 << c->nov_shift;

@@ -88,6 +88,7 @@ struct PhiSketchArgs {
     // ... and, in the first launch after a reset, every wave also empties its share of the buffers the PREVIOUS
     // generation of reads filled (the other half of the context's double buffers), for the generation after this one
     int32_t q_clean;
+    int32_t win_reads;                     // reads of one length in window space: whole reads per wave (set by the launcher; fills the padding after q_clean)
     unsigned long long *ov_zero;           // the overflow counter of the generation after this one (three rotate)
     // a context in a group of processes (phi_ipc.hip): this rank's flag block.  The launch's first wave publishes "the
     // exchanges issued before this launch have their read sets scored" (ipc_scored: the stream is in order, so every
@@ -106,6 +107,10 @@ void phi_launch_mark_starts(hipStream_t st, const int64_t *seq_off, int64_t n_se
 void phi_launch_sketch_bytes(hipStream_t st, int mode, const PhiSketchArgs &A, const unsigned long long *batch_bad);
 void phi_launch_reset_reads(hipStream_t st, uint64_t *hit_words, int64_t n_hit_words, uint64_t *stripes, int64_t n_stripe_words);
 int64_t phi_sketch_num_blocks(int64_t n_bases);
+// read batches (PHI_MODE_PROBE): whole reads per wave of the window-space kernel (0: the batch is sketched in base space),
+// and the chunks -- waves, entries of the log of novel hashes -- its launch fills
+int phi_sketch_win_reads(int k, int w, int64_t uniform_len, int64_t n_reads, int64_t n_bases);
+int64_t phi_sketch_read_chunks(int k, int w, int64_t uniform_len, int64_t n_reads, int64_t n_bases);
 void phi_launch_sketch(hipStream_t st, int mode, const PhiSketchArgs &A, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
 void phi_launch_scan_counts(hipStream_t st, const int32_t *cnt, int64_t n, int64_t *off);
 

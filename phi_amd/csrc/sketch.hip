@@ -617,7 +617,10 @@ __device__ __forceinline__ void start_bits_uniform(const PhiSketchArgs &A, int64
     if (p < hi_b && p < A.n_bases) set_start_bit(s_bits, p, org);  // (64 lanes cover the range: L >= 32 > 1024 / 63)
 }
 
-// phase 0 of a read chunk: lane -> the 16 bases c0 - 32 + 16 lane .. + 15 as four words ('A' beyond the batch)
+// phase 0 of a read chunk: lane -> the 16 bases c0 - 32 + 16 lane .. + 15 as four words ('A' beyond the batch).
+// (ONE: phi_sketch_win_kernel's own instance -- the compiler otherwise derives the function's properties from the calls of
+// both kernels, and the base-space kernels' code changes with it)
+template <int ONE = 0>
 __device__ __forceinline__ uint4 load_bases16(const uint8_t *__restrict__ ascii, int64_t N, int64_t c0, int lane)
 {
     const int64_t b = c0 - 32 + 16 * (int64_t)lane;
@@ -692,47 +695,7 @@ __global__ void __launch_bounds__(TPB, MODE == PHI_MODE_PROBE ? 6 : 1) phi_sketc
 #if PHI_ABL == 2
     ncand = 0;
 #endif
-    if (ncand > 0) {
-        uint64_t carry = PHI_EMPTY_KEY;
-        for (int r0 = 0; r0 <= ncand; r0 += 64) {
-            const int t = r0 + lane;
-            const bool valid = t <= ncand;
-            uint32_t meta = 0;
-            uint64_t h = 0;
-            if (valid) {
-                meta = s_meta[t];
-                h = phi_kmer_hash(SM((int)(meta & 0x3FFu)), k);
-            }
-            const uint64_t hp = wave_prev_u64(h, carry, lane);
-            carry = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(h >> 32), 63) << 32) |
-                    (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)h, 63);
-            const bool emit = valid && !(meta & ITEM_NOEMIT) && ((meta & ITEM_FIRST) || h != hp);
-            const unsigned long long bal = __ballot(emit);
-            bool novel = false;
-            if (emit) {
-                const int rank = n_emit + __popcll(bal & ((1ull << lane) - 1));
-                if (MODE == PHI_MODE_WRITE) {
-                    A.out_hash[out_base + rank] = h;
-                    A.out_pos[out_base + rank] = c0 - 1 + (int64_t)((meta >> 10) & 0x3FFu);
-                } else if (MODE == PHI_MODE_PROBE) {
-                    novel = probe_table(A, h);
-                }
-            }
-            if (MODE == PHI_MODE_PROBE) {
-                // the round's novel hashes, appended to the chunk's log in lane order: one coalesced store
-                const unsigned long long ib = __ballot(novel);
-                const int pos = n_log + __popcll(ib & ((1ull << lane) - 1));
-                const int cap = 1 << A.nov_shift;
-                if (novel && pos < cap) A.nov_log[((A.log_base + chunk) << A.nov_shift) + pos] = h;
-                n_log += __popcll(ib);
-                if (n_log > cap) {                            // (wave-uniform, rare) past the chunk's log: the overflow list
-                    const OverflowArgs O{A.ov_list, A.ov_count, A.ov_cap, A.err};
-                    overflow_novel(O, novel && pos >= cap, h, lane);
-                }
-            }
-            n_emit += __popcll(bal);
-        }
-    }
+#include "sketch_rounds.inc"
 
     if (FUSED && chunk_bad) {
         // (rare) windows over a base outside ACGTacgt, or right after one: the exact byte-wise routine, by the wave
@@ -755,6 +718,231 @@ __global__ void __launch_bounds__(TPB, MODE == PHI_MODE_PROBE ? 6 : 1) phi_sketc
             if (n_nov_wave && A.n_logged) atomicAdd(A.n_logged + stripe, (unsigned long long)n_nov_wave);
             if (n_emit && A.n_emitted) atomicAdd(A.n_emitted + stripe, (unsigned long long)n_emit);
         }
+    }
+}
+
+// ---- read batches of ONE length in WINDOW space (phi_launch_sketch: uniform_len > 0, k <= 32, phi_sketch_win_reads > 0)
+// A read of length L has V = L - (k + w - 1) + 1 windows; the base-space kernel above spends its lanes on all L positions
+// of it (150-bp reads at (31, 25): 96 windows, 150 positions -- a third of phases 2 - 3b on positions that cannot be
+// windows).  Here a wave takes R = A.win_reads WHOLE reads: read rl of the wave gets G = ceil(V / Q) lanes, lane j of it the
+// read's windows 8j .. 8j + 7 (those past V are masked), and the lanes past R * G idle.  No read starts inside a window,
+// so the read-start search and the `blocked` mask go; phase 1 rolls only the read's own L - k + 1 k-mers.
+//
+// LDS of a wave (phi_win_mp_u64): read rl's k-mers lie in s = G + ceil(w / Q) rows of 9 u64 (8 slots + the pad word SM
+// keeps), k-mer t in slot 8 s rl + 1 + t, so that lane j reads its Q + w k-mers at constant offsets from one address, as in
+// base space; once they are read, the lanes' minima go to slots 8 lane + i (rows 0 .. 64, the layout phases 4 - 5 and the
+// items expect) and the 16-bit items behind them.  With the staged words and bitmap of bases outside ACGTacgt that is at
+// most what the base-space kernel takes for the same (k, w): phi_sketch_win_reads picks R so.  At L = 150, (31, 25):
+// G = 12, s = 16, R = 5 (480 windows a wave instead of ~330), 6 144 B a wave (base space: 6 560 B).
+__host__ __device__ static inline int phi_win_items_u64(int w, int k) { return ((phi_wave_items(w, k) + 4) * 2 + 7) / 8; }
+__host__ __device__ static inline int phi_win_mp_u64(int R, int s, int w, int k)
+{
+    const int kmers = 9 * R * s;                                  // R reads of s rows
+    const int minima = 9 * (64 + 1) + phi_win_items_u64(w, k);    // minima of 64 lanes (rows 0 .. 64), then the items
+    return kmers > minima ? kmers : minima;
+}
+__host__ __device__ static inline int phi_win_region_u64(int R, int s, int w, int k) { return phi_win_mp_u64(R, s, w, k) + SWW + SBW; }
+
+// The byte-wise routine for the windows of this wave's reads that touch a base outside ACGTacgt (window, or its predecessor:
+// the same partition as in base space).  Window q of the wave = window v of read rl: base (r0 + rl) L + v.
+__device__ __forceinline__ void slow_windows_reads(const PhiSketchArgs &A, int64_t r0, int nr, int L, int V, int64_t c0, int lane,
+                                                   int k, int w, const unsigned long long *s_bad, int &n_emit, int &n_nov)
+{
+    const int span = w + k - 1, n_win = nr * V;
+    for (int q0 = 0; q0 < n_win; q0 += 64) {
+        const int q = q0 + lane;
+        const int rl = q / V, v = q - rl * V;
+        const int64_t a = (r0 + rl) * (int64_t)L + v;
+        const int lp = (int)(a - (c0 - 64));                       // local bit of base a
+        const bool todo = q < n_win && range_has_bit(s_bad, lp - 1, lp + span - 1);
+        bool emit = false;
+        uint64_t h = 0;
+        if (todo) {
+            const KRef best = window_best_bytes(A.ascii, a, k, w);
+            h = khash_bytes<false>(A.ascii, best, k);
+            if (v == 0) emit = h != PHI_EMPTY_KEY;                   // prev_hash = UINT64_MAX (:383, :455)
+            else {
+                const KRef prev = window_best_bytes(A.ascii, a - 1, k, w);
+                emit = !(prev.pos == best.pos && prev.rc == best.rc) && khash_bytes<false>(A.ascii, prev, k) != h;
+            }
+        }
+        const unsigned long long bal = __ballot(emit);
+        const bool novel = emit && probe_table(A, h);
+        const OverflowArgs O{A.ov_list, A.ov_count, A.ov_cap, A.err};
+        n_nov += overflow_novel(O, novel, h, lane);                   // (straight to the overflow list, as in base space)
+        n_emit += __popcll(bal);
+    }
+}
+
+template <bool WIDE, int KT, int WT>
+__global__ void __launch_bounds__(TPB, 6) phi_sketch_win_kernel(PhiSketchArgs A)   // (six waves per SIMD, at most 80 VGPRs)
+{
+    constexpr int MODE = PHI_MODE_PROBE;
+    constexpr bool NEED_POS = false;                     // (names of the shared phases)
+    constexpr bool FMIN = KT > 0 && KT <= 31;            // values < 2^62: minima by v_min_f64
+    static_assert(KT >= 0, "k <= 32");
+    extern __shared__ uint64_t s_dyn[];
+
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int k = KT > 0 ? KT : A.k, w = WT ? WT : A.w;
+    const int64_t N = A.n_bases;
+    const int L = A.uniform_len, span = w + k - 1, V = L - span + 1;
+    const int G = (V + Q - 1) / Q, s = G + (w + Q - 1) / Q, R = A.win_reads;
+    const int64_t chunk = (int64_t)blockIdx.x * (TPB / 64) + wid;     // this wave's reads: chunk * R .. + R - 1
+    const int64_t rd0 = chunk * R;
+    if (A.ipc_mb && chunk == 0 && lane == 0)               // (a group of processes: see PhiSketchArgs)
+        __hip_atomic_store(A.ipc_mb + PHI_MB_SCORED, A.ipc_scored, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+    if (rd0 >= A.n_reads) {                                // wave-uniform
+        if (A.q_clean) clean_finish(A, chunk, (int64_t)gridDim.x * (TPB / 64), lane);
+        return;
+    }
+    const int nr = A.n_reads - rd0 < R ? (int)(A.n_reads - rd0) : R;   // reads of this wave
+    const uint64_t kmask = phi_kmask(k);
+    // staging origin: the 32-base word holding the wave's first base.  Local base lb <-> base c0-32+lb, local bit lp <->
+    // base c0-64+lp, as in base space; R L <= 928 (phi_sketch_win_reads) keeps every word and bit a lane reads staged
+    const int64_t c0 = (rd0 * (int64_t)L) & ~(int64_t)31;
+    // this lane's read and lane group: rl = lane / G (exact in single precision for lane < 64), j = lane % G
+    const int rl = (int)(((float)lane + 0.5f) * (1.0f / (float)G)), j = lane - rl * G;
+    const bool live = rl < nr;
+
+    using MetaT = uint16_t;
+    constexpr uint32_t ITEM_FIRST = 1u << 15;            // the first window of its read
+    constexpr uint32_t ITEM_NOEMIT = 1u << 14;           // only its hash is needed (the window before a candidate)
+    uint64_t *s_mp = s_dyn + (size_t)wid * phi_win_region_u64(R, s, w, k);   // k-mers; later the window minima and the items
+    uint64_t *s_words = s_mp + phi_win_mp_u64(R, s, w, k);
+    unsigned long long *s_bad = (unsigned long long *)(s_words + SWW);
+    MetaT *s_meta = (MetaT *)(s_mp + 9 * (64 + 1));      // items: behind the minima
+    uint64_t *s_q = s_mp + (live ? 9 * (rl * s + j) : 0);   // k-mer 8j - 1 + x of the lane's read: s_q[x + (x >> 3)]
+
+    // ---- phase 0: lane -> the 16 bases c0 - 32 + 16 lane .. + 15: one 32-bit half of a packed word + 16 flags of bases
+    //      outside ACGTacgt (the text of sketch_phases.inc, phase 0)
+    bool chunk_bad;
+    {
+        const uint4 v = load_bases16<1>(A.ascii, N, c0, lane);
+        const uint32_t x[4] = {v.x, v.y, v.z, v.w};
+        uint32_t code = 0, bad = 0;
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const uint32_t t = ((x[q] >> 1) ^ (x[q] >> 2)) & 0x03030303u;
+            const uint32_t c8 = (t * 0x40100401u) >> 24;
+            code = (code << 8) | c8;
+            if (__builtin_amdgcn_perm(0x54474341u, 0x54474341u, t) != (x[q] & 0xDFDFDFDFu)) {
+#pragma unroll
+                for (int b = 0; b < 4; b++) bad |= (uint32_t)(!phi_is_acgt((x[q] >> (8 * b)) & 0xFFu)) << (4 * q + b);
+            }
+        }
+        reinterpret_cast<uint32_t *>(s_words)[lane ^ 1] = code;
+        uint16_t *s_bad16 = reinterpret_cast<uint16_t *>(s_bad);
+        if (lane < 62) s_bad16[lane + 2] = (uint16_t)bad;
+        else { s_bad16[lane - 62] = 0; bad = 0; }
+        chunk_bad = __ballot(bad != 0) != 0ull;          // wave-uniform
+    }
+    wave_sync();
+
+    // ---- phase 1: the read's L - k + 1 canonical k-mers, P consecutive per lane of its group
+    if (live) {
+        const int n_km = L - k + 1, P = (n_km + G - 1) / G;
+        const int t0 = j * P;
+        const int n = n_km - t0 < P ? n_km - t0 : P;
+        if (n > 0) {
+            const int lb = (int)((rd0 + rl) * (int64_t)L + t0 - c0) + 32;
+            uint64_t F = lds_extract64(s_words, lb) >> (64 - 2 * k);
+            uint64_t Rc = phi_revcomp(F, k);
+            uint64_t nxt = lds_extract64(s_words, lb + k);         // the bases after the first k-mer
+            int u = 8 * s * rl + 1 + t0;                              // slot of k-mer t0
+            for (int i = 0; i < n; i++, u++) {
+                if (i) {
+                    const uint64_t b = nxt >> 62;
+                    nxt <<= 2;
+                    F = ((F << 2) | b) & kmask;
+                    Rc = (Rc >> 2) | ((3 - b) << (2 * k - 2));
+                }
+                s_mp[u + (u >> 3)] = FMIN ? min_u62(F, Rc) : (F < Rc ? F : Rc);
+            }
+        }
+    }
+    wave_sync();
+
+    // ---- phase 2: minima of the lane's windows 8j - 1 .. 8j + 7 of its read (k-mers 8j - 1 .. 8j + 6 + w)
+#include "sketch_minima.inc"
+
+    // ---- phase 3: candidate windows i = 1..Q of this lane (window 8j + i - 1 of its read)
+    uint32_t cflag = 0, fflag = 0, pflag = 0;             // candidates; first windows; candidates that carry their predecessor
+    if (live) {
+        const int imax = V - Q * j < Q ? V - Q * j : Q;   // windows i <= imax exist
+        const uint32_t in_read = (2u << imax) - 2u;        // bits 1 .. imax
+        const uint32_t first = j == 0 ? 2u : 0u;           // window 0 of the read
+        uint32_t changed = 0;
+#pragma unroll
+        for (int i = 1; i <= Q; i++) changed |= (uint32_t)(wv[i] != wv[i - 1]) << i;
+        // bit i of `dall`: a base outside ACGT under window i or its predecessor (bases a-1 .. a+span-1; for a read's first
+        // window a-1 is the last base of the read before, as in base space): such windows take the byte-wise routine, and
+        // the first window after a stretch of them carries its own predecessor
+        uint32_t dall = 0, reseed = 0;
+        if (chunk_bad) {
+            const int lp0 = (int)((rd0 + rl) * (int64_t)L + Q * j - 1 - (c0 - 64));   // local bit of window 0's base
+            for (int i = 0; i <= Q; i++) dall |= (uint32_t)range_has_bit(s_bad, lp0 + i - 1, lp0 + i + span - 1) << i;
+            reseed = ~dall & (dall << 1);
+        }
+        cflag = in_read & ~dall & (first | changed | reseed);
+        fflag = cflag & first;
+        pflag = cflag & reseed & ~first;
+    }
+    // wave prefix sum of the per-lane candidate counts
+    int ncand, coff;
+    {
+        const int cnt = __popc(cflag) + __popc(pflag);
+        const int v = wave_scan_inclusive(cnt);
+        ncand = __builtin_amdgcn_readlane(v, 63);
+        coff = v - cnt;
+    }
+    wave_sync();                                          // every lane has read its k-mers
+    {
+        // the minimum of window i of lane goes to SM(lane * Q + i) -- the layout of base space
+        uint64_t *s_w = s_mp + 9 * lane;
+#define SW(x) s_w[(x) + ((x) >> 3)]
+        if (lane == 0) SW(0) = wv[0];
+#pragma unroll
+        for (int i = 1; i <= Q; i++) SW(i) = wv[i];
+#undef SW
+        int c = coff + 1;
+        if (!chunk_bad) {
+            for (uint32_t f = cflag; f; f &= f - 1) {
+                const uint32_t i = (uint32_t)__ffs((int)f) - 1;
+                s_meta[c++] = (MetaT)((uint32_t)(lane * Q) + i + (((fflag >> i) & 1u) ? ITEM_FIRST : 0u));
+            }
+        } else {
+#pragma unroll
+            for (int i = 1; i <= Q; i++) {
+                if ((cflag >> i) & 1u) {
+                    if ((pflag >> i) & 1u) s_meta[c++] = (MetaT)((uint32_t)(lane * Q + i - 1) | ITEM_NOEMIT);
+                    s_meta[c++] = (MetaT)((uint32_t)(lane * Q + i) | (((fflag >> i) & 1u) ? ITEM_FIRST : 0u));
+                }
+            }
+        }
+        if (coff == 0 && cflag) s_meta[0] = (MetaT)((uint32_t)(lane * Q + __ffs((int)cflag) - 2) | ITEM_NOEMIT);
+    }
+    wave_sync();
+#undef SQ
+
+    // ---- phases 4 + 5, as in base space
+    int n_emit = 0, n_log = 0, n_nov_slow = 0;
+    const int64_t out_base = 0;
+#include "sketch_rounds.inc"
+
+    if (chunk_bad) {
+        int n_emit_slow = 0;
+        slow_windows_reads(A, rd0, nr, L, V, c0, lane, k, w, s_bad, n_emit_slow, n_nov_slow);
+        n_emit += n_emit_slow;
+    }
+    if (A.q_clean) clean_finish(A, chunk, (int64_t)gridDim.x * (TPB / 64), lane);
+    if (lane == 0) {
+        const int cap = 1 << A.nov_shift;
+        A.nov_cnt[A.log_base + chunk] = (uint16_t)(n_log < cap ? n_log : cap);
+        const int n_nov_wave = n_log + n_nov_slow;
+        const int stripe = (int)(chunk & (PHI_STRIPES - 1)) * 8;
+        if (n_nov_wave && A.n_logged) atomicAdd(A.n_logged + stripe, (unsigned long long)n_nov_wave);
+        if (n_emit && A.n_emitted) atomicAdd(A.n_emitted + stripe, (unsigned long long)n_emit);
     }
 }
 
@@ -1075,11 +1263,68 @@ static void launch_sketch_mode(hipStream_t st, unsigned nb, size_t lds, const Ph
     else hipExtLaunchKernelGGL((phi_sketch_kernel<MODE, false, 0, 0>), dim3(nb), dim3(TPB), lds, st, t0, t1, 0, A);
 }
 
+// chunks from which a read batch takes the pooled kernel
+static int64_t pool_min_chunks()
+{
+    int64_t min_chunks = 4 * 6144;
+    if (const char *e = getenv("PHI_SKETCH_POOL_MIN")) min_chunks = atoll(e);
+    return min_chunks;
+}
+
+// Reads of one length: whole reads per wave of phi_sketch_win_kernel, or 0 for base space.  A wave holds R reads of
+// G = ceil(V / Q) lanes each (R G <= 64), its staged bases (R L <= 928: the 1 024 bases of phase 0, less the alignment of the
+// first read and the word read past a k-mer's last base), no more LDS than the base-space kernel for the same (k, w) (so
+// never fewer waves per SIMD), and a lane rolls at most 32 k-mers (one staged word of bases ahead).  It pays when the
+// wave's R L bases outnumber the 512 positions of a base-space chunk clearly -- R L >= 576: at most 8 waves where base
+// space has 9 (long reads have few positions that are not windows: L = 300 at (31, 25) gives R = 2, 600 bases, 4 %
+// fewer waves).  It also takes the batches of 12 Mbases and more that the pooled kernel took (C3: 495 -> 633 Gbases/s,
+// DESIGN.md 4.1), unless PHI_SKETCH_POOL_MIN is set: then batches from that size on stay pooled (tests of that kernel).
+// PHI_SKETCH_WINDOWS: "0" never, "1" whenever the geometry allows (tests run a batch both ways).
+int phi_sketch_win_reads(int k, int w, int64_t uniform_len, int64_t n_reads, int64_t n_bases)
+{
+    if (uniform_len <= 0 || n_reads <= 0 || k > PHI_MAX_K_PACKED) return 0;
+    int force = -1;
+    if (const char *e = getenv("PHI_SKETCH_WINDOWS")) force = atoi(e) ? 1 : 0;
+    if (force == 0) return 0;
+    const int64_t L = uniform_len, V = L - (k + w - 1) + 1;
+    if (V < 1 || L > 928) return 0;
+    const int G = (int)((V + Q - 1) / Q), s = G + (w + Q - 1) / Q;
+    if (G > 64 || (L - k + 1 + G - 1) / G > 32) return 0;
+    int R = 64 / G;
+    if (R > 928 / L) R = (int)(928 / L);
+    while (R > 0 && phi_win_region_u64(R, s, w, k) > phi_wave_region_u64(w, k, false)) R--;
+    if (R < 1) return 0;
+    if (force != 1 && (R * L < WCH + WCH / 8 || (getenv("PHI_SKETCH_POOL_MIN") && phi_sketch_num_blocks(n_bases) >= pool_min_chunks()))) return 0;
+    return R;
+}
+
+int64_t phi_sketch_read_chunks(int k, int w, int64_t uniform_len, int64_t n_reads, int64_t n_bases)
+{
+    const int R = phi_sketch_win_reads(k, w, uniform_len, n_reads, n_bases);
+    return R > 0 ? (n_reads + R - 1) / R : phi_sketch_num_blocks(n_bases);
+}
+
 void phi_launch_sketch(hipStream_t st, int mode, const PhiSketchArgs &A0, hipEvent_t t0, hipEvent_t t1)
 {
     const int64_t nchunks = phi_sketch_num_blocks(A0.n_bases);
     if (nchunks <= 0) return;
     PhiSketchArgs A = A0;
+    if (mode == PHI_MODE_PROBE) {
+        const int R = phi_sketch_win_reads(A.k, A.w, A.uniform_len, A.n_reads, A.n_bases);
+        if (R > 0) {
+            // reads of one length in window space: R whole reads per wave (phi_sketch_win_kernel)
+            A.win_reads = R;
+            const int64_t waves = (A.n_reads + R - 1) / R;
+            const unsigned nb = (unsigned)((waves + TPB / 64 - 1) / (TPB / 64));
+            const int V = (int)(A.uniform_len - (A.k + A.w - 1) + 1);
+            const int s = (V + Q - 1) / Q + (A.w + Q - 1) / Q;
+            const size_t lds = (size_t)phi_win_region_u64(R, s, A.w, A.k) * 8 * (TPB / 64);
+            if (A.k == 31 && A.w == 25) hipExtLaunchKernelGGL((phi_sketch_win_kernel<true, 31, 25>), dim3(nb), dim3(TPB), lds, st, t0, t1, 0, A);
+            else if (A.w > Q) hipExtLaunchKernelGGL((phi_sketch_win_kernel<true, 0, 0>), dim3(nb), dim3(TPB), lds, st, t0, t1, 0, A);
+            else hipExtLaunchKernelGGL((phi_sketch_win_kernel<false, 0, 0>), dim3(nb), dim3(TPB), lds, st, t0, t1, 0, A);
+            return;
+        }
+    }
     // Reads (k <= 32), batches of 12 Mbases and more: wave g of `njobs` takes the chunks g, g + njobs, ... and hashes their
     // items in full rounds (POOL in the kernel).  Four times as many waves as the machine holds at once (256 CUs x 4 SIMDs
     // x 6 waves of this kernel): the SIMDs serve their oldest wave first, so waves of equal shares end far apart (the first
@@ -1090,9 +1335,8 @@ void phi_launch_sketch(hipStream_t st, int mode, const PhiSketchArgs &A0, hipEve
     bool pooled = false;
     if (mode == PHI_MODE_PROBE && A.k <= PHI_MAX_K_PACKED) {
         int64_t slots = 4 * 256 * 4 * 6;
-        int64_t min_chunks = 4 * 6144;
+        const int64_t min_chunks = pool_min_chunks();
         if (const char *e = getenv("PHI_SKETCH_WAVES")) slots = atoll(e) > 0 ? atoll(e) : slots;
-        if (const char *e = getenv("PHI_SKETCH_POOL_MIN")) min_chunks = atoll(e);
         if (nchunks >= min_chunks) {
             int64_t m = (nchunks + slots - 1) / slots;          // chunks per wave
             if (m < 3) m = 3;
