@@ -379,6 +379,14 @@ int phi_walk_entries(phi_ctx *ctx, int32_t *out, int64_t cap, int64_t *n);
  * state: a fault raised by an earlier asynchronous launch surfaces here (diagnostics; no reference counterpart). */
 int phi_device_synchronize(phi_ctx *ctx);
 
+/* data/edlib_edits.py:24-27, data/postprocessing_2_MIQP.py:21-42, data/get_edit_stats.sh: edlib NW edit distance of
+ * pair i = (a[a_off[i]..a_off[i+1]), b[b_off[i]..b_off[i+1])), one workgroup per pair.  out[i] = distance, or -1 when
+ * max_distance >= 0 and the distance exceeds it.  Needs no phi_set_params / phi_set_graph and leaves graph, reads and
+ * result state untouched.  Bytes compare exactly (case-sensitive, no wildcards); each sequence < 2^31 bytes
+ * (PHI_ERR_UNSUPPORTED beyond).  Runs on the context's stream and returns when out is filled. */
+int phi_edit_distances(phi_ctx *ctx, const char *a, const int64_t *a_off, const char *b, const int64_t *b_off,
+                       int64_t n_pairs, int64_t max_distance, int64_t *out);
+
 #ifdef __cplusplus
 }
 #endif

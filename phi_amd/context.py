@@ -268,6 +268,21 @@ class Context:
         self._chk(self._L.phi_path_sequence(self._h, buf, hap_len))
         return buf.raw[:hap_len]
 
+    # ------------------------------------------------------------------ evaluation
+    def edit_distances(self, a_list, b_list, max_distance=-1):
+        """edlib NW edit distance of every pair (a_list[i], b_list[i]) of byte strings on the GPU (phi_edit_distances):
+        np.int64 array; -1 where max_distance >= 0 and the distance exceeds it."""
+        if len(a_list) != len(b_list):
+            raise ValueError("a_list and b_list differ in length")
+        n = len(a_list)
+        a_off, b_off = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64)
+        np.cumsum([len(s) for s in a_list], out=a_off[1:])
+        np.cumsum([len(s) for s in b_list], out=b_off[1:])
+        a, b = b"".join(a_list), b"".join(b_list)
+        out = np.zeros(n, np.int64)
+        self._chk(self._L.phi_edit_distances(self._h, a, _ptr(a_off), b, _ptr(b_off), n, int(max_distance), _ptr(out)))
+        return out
+
     # ------------------------------------------------------------------ introspection
     def sketch(self, seqs, k, w):
         """Stand-alone minimiser sketch: (hash[], pos[], seq[]) sorted by (seq, pos)."""

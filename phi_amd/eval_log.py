@@ -9,6 +9,9 @@ command line, so that the harness' tables can be made from runs of this build:
 
     python -m phi_amd.eval_log run1.log [run2.log ...]            # CSV on stdout
     python -m phi_amd.eval_log --truth truth.fa --query out.fa run.log   # + edit distance (banded, exact within the band)
+
+The edit distance runs on the GPU (phi_edit_distances: whole MHCs in about a second) when a HIP device is present and
+libphi_amd.so loads; otherwise on the numpy function below, which is exact but only practical up to some 10^4 bases.
 """
 import argparse
 import csv
@@ -85,6 +88,15 @@ def edit_distance(a, b, band=None):
         band *= 2
 
 
+def _device_context():
+    """A context on device 0, or None when there is no HIP device or the library does not load."""
+    try:
+        from .context import Context
+        return Context(0)
+    except (OSError, RuntimeError):
+        return None
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="Scrape PHI logs as data/postprocessing_2_MIQP.py does")
     ap.add_argument("logs", nargs="+")
@@ -94,11 +106,20 @@ def main(argv=None):
     w = csv.writer(sys.stdout)
     extra = ["edit_distance"] if args.truth and args.query else []
     w.writerow(["log"] + FIELDS + extra)
+    dist = None
+    if extra:
+        truth, query = read_fasta(args.truth), read_fasta(args.query)
+        ctx = _device_context()
+        if ctx is not None:
+            dist = int(ctx.edit_distances([truth], [query])[0])
+            ctx.close()
+        else:
+            dist = edit_distance(truth, query)
     for p in args.logs:
         row = parse_log(open(p, errors="replace").read())
         vals = [row[k] for k in FIELDS]
         if extra:
-            vals.append(edit_distance(read_fasta(args.truth), read_fasta(args.query)))
+            vals.append(dist)
         w.writerow([p] + vals)
 
 
