@@ -387,6 +387,19 @@ int phi_device_synchronize(phi_ctx *ctx);
 int phi_edit_distances(phi_ctx *ctx, const char *a, const int64_t *a_off, const char *b, const int64_t *b_off,
                        int64_t n_pairs, int64_t max_distance, int64_t *out);
 
+/* data/edlib_edits.py:8-43, data/postprocessing_2_MIQP.py:21-39: one optimal global alignment (unit costs, bytes compared
+ * exactly) of each pair of phi_edit_distances' layout, query a and target b as in edlib.align(a, b), given its distance
+ * dist[i] (as phi_edit_distances returned it; -1: the pair is skipped and its counts are -1).  counts[5i .. 5i+4] = M
+ * ('='), X (mismatch), I (a byte of a only), D (a byte of b only) and the CIGAR's length in bytes; identity =
+ * M * 100 / (M + X + I + D).  The path is the traceback from (|a|, |b|) that takes at each cell the first step keeping the
+ * optimal value: diagonal, then I, then D.  cigar may be NULL (counts only); otherwise pair i's extended CIGAR ('=', 'X',
+ * 'I', 'D' runs, no terminator) goes to cigar[cigar_off[i] .. cigar_off[i+1]), which must hold 11 (2 dist[i] + 1) bytes
+ * (PHI_ERR_INVALID before any work otherwise).  PHI_ERR_INVALID, naming the pair, when no alignment costs dist[i];
+ * PHI_ERR_NOMEM when a pair's checkpoints do not fit in free device memory.  Needs no phi_set_params / phi_set_graph and
+ * leaves graph, reads and result state untouched.  Runs on the context's stream and returns when counts are filled. */
+int phi_edit_alignments(phi_ctx *ctx, const char *a, const int64_t *a_off, const char *b, const int64_t *b_off,
+                        int64_t n_pairs, const int64_t *dist, int64_t *counts, char *cigar, const int64_t *cigar_off);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,7 +28,7 @@ SYMBOLS = [
     "phi_add_reads_text_parked",
     "phi_peers_create", "phi_peers_join", "phi_peers_allreduce_hits", "phi_peers_exchange", "phi_peers_destroy",
     "phi_ipc_unique_id", "phi_ipc_init", "phi_ipc_info", "phi_ipc_allreduce_hits", "phi_ipc_flush", "phi_ipc_exchange", "phi_ipc_check", "phi_ipc_destroy",
-    "phi_edit_distances",
+    "phi_edit_distances", "phi_edit_alignments",
 ]
 
 
@@ -138,6 +138,7 @@ def load():
     L.phi_walk_text_resolve.argtypes = [vp, C.c_char_p, i32, vp, i64, i32, vp, C.POINTER(C.c_uint32)]
     L.phi_walk_entries.argtypes = [vp, vp, i64, C.POINTER(i64)]
     L.phi_edit_distances.argtypes = [vp, vp, vp, vp, vp, i64, i64, vp]
+    L.phi_edit_alignments.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp, vp, vp]
     for name in SYMBOLS:
         f = getattr(L, name)          # AttributeError here = the library does not export the ABI
         if f.restype is C.c_int and name not in ("phi_strerror", "phi_last_error", "phi_ctx_destroy"):

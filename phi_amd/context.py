@@ -1,5 +1,6 @@
 """Thin object wrapper over the C ABI: one Context == one phi_ctx (one GPU)."""
 import ctypes as C
+from typing import NamedTuple
 
 import numpy as np
 
@@ -15,6 +16,15 @@ class PhiError(RuntimeError):
 
 def _ptr(a):
     return a.ctypes.data if a is not None and a.size else None
+
+
+class Alignments(NamedTuple):
+    """Context.edit_alignments: per pair the distance, the counts (M, X, I, D) as an (n, 4) int64 array, the extended
+    CIGAR (str, or None) and the alignment identity M * 100 / (M + X + I + D) in percent (float64)."""
+    distance: np.ndarray
+    counts: np.ndarray
+    cigar: list
+    identity: np.ndarray
 
 
 class Context:
@@ -282,6 +292,40 @@ class Context:
         out = np.zeros(n, np.int64)
         self._chk(self._L.phi_edit_distances(self._h, a, _ptr(a_off), b, _ptr(b_off), n, int(max_distance), _ptr(out)))
         return out
+
+    def edit_alignments(self, a_list, b_list, dist=None, cigar=True):
+        """One optimal alignment of every pair (query a_list[i], target b_list[i]) on the GPU (phi_edit_alignments):
+        Alignments(distance, counts, cigar, identity).  dist: the pairs' distances (phi_edit_distances runs first when
+        None); a pair with dist -1 is skipped (counts -1, cigar None, identity nan).  cigar=False: counts only.  The
+        identity of two empty sequences is 0, as data/edlib_edits.py gives it."""
+        if len(a_list) != len(b_list):
+            raise ValueError("a_list and b_list differ in length")
+        n = len(a_list)
+        if dist is None:
+            dist = self.edit_distances(a_list, b_list)
+        dist = np.ascontiguousarray(dist, np.int64)
+        if dist.shape != (n,):
+            raise ValueError("dist must hold one distance per pair")
+        a_off, b_off = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64)
+        np.cumsum([len(s) for s in a_list], out=a_off[1:])
+        np.cumsum([len(s) for s in b_list], out=b_off[1:])
+        a, b = b"".join(a_list), b"".join(b_list)
+        counts = np.zeros((n, 5), np.int64)
+        buf, c_off = None, None
+        if cigar:
+            c_off = np.zeros(n + 1, np.int64)
+            np.cumsum(np.where(dist >= 0, 11 * (2 * dist + 1), 0), out=c_off[1:])
+            buf = C.create_string_buffer(max(int(c_off[-1]), 1))
+        self._chk(self._L.phi_edit_alignments(self._h, a, _ptr(a_off), b, _ptr(b_off), n, _ptr(dist), _ptr(counts),
+                                               buf, _ptr(c_off)))
+        cig = None
+        if cigar:
+            raw = buf.raw
+            cig = [raw[c_off[i]:c_off[i] + counts[i, 4]].decode() if dist[i] >= 0 else None for i in range(n)]
+        total = counts[:, :4].sum(axis=1)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            ident = np.where(dist < 0, np.nan, np.where(total > 0, counts[:, 0] * 100.0 / np.maximum(total, 1), 0.0))
+        return Alignments(dist, counts[:, :4].copy(), cig, ident)
 
     # ------------------------------------------------------------------ introspection
     def sketch(self, seqs, k, w):
