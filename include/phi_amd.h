@@ -400,6 +400,48 @@ int phi_edit_distances(phi_ctx *ctx, const char *a, const int64_t *a_off, const 
 int phi_edit_alignments(phi_ctx *ctx, const char *a, const int64_t *a_off, const char *b, const int64_t *b_off,
                         int64_t n_pairs, const int64_t *dist, int64_t *counts, char *cigar, const int64_t *cigar_off);
 
+
+/* gzip (RFC 1952, any number of members) inflated on a device, DESIGN.md 4.8.  in[0, n): the whole file; the output goes
+ * to out[0, cap) when it fits.  *out_size = the inflated size in every successful call: when it exceeds cap nothing is
+ * copied (call again with a larger buffer).  chunk_bytes: the compressed bytes per chunk (<= 0: PHI_INFLATE_CHUNK from the
+ * environment, else PHI_INFLATE_CHUNK_DEFAULT).  flags: PHI_INFLATE_NO_FINDER searches no chunk for a block start (every
+ * chunk is then decoded by its predecessor: serial speed, for tests).  Every member's CRC32 and ISIZE are checked; an
+ * invalid code, a distance before the start of its member, truncation or a CRC / ISIZE mismatch is PHI_ERR_INVALID and
+ * claims no output.  info (may be NULL) is filled, its detail text on any error.  Needs no phi_ctx. */
+#define PHI_INFLATE_CHUNK_DEFAULT (64 << 10)
+#define PHI_INFLATE_NO_FINDER 1
+typedef struct {
+    int64_t in_bytes;          /* compressed bytes */
+    int64_t out_bytes;         /* inflated bytes */
+    int64_t members;           /* gzip members */
+    int64_t chunks;            /* chunks the stream was cut into */
+    int64_t confirmed;         /* chunks whose decoder's output was used (confirmed at their found start), chunk 0 aside */
+    int64_t redecoded;         /* chunks decoded by a predecessor instead (start missing or false) */
+    int64_t marker_bytes;      /* output bytes that referred to an earlier chunk's window and were resolved afterwards */
+    double device_ms;          /* span from the uploaded input to the checked output (upload and download excluded; the host's
+                                  work between kernels included: an upper bound of the device time) */
+    char detail[192];
+} phi_inflate_info;
+int phi_inflate(int32_t device, const void *in, int64_t n, void *out, int64_t cap, int64_t chunk_bytes, int32_t flags,
+                int64_t *out_size, phi_inflate_info *info);
+/* phi_inflate with the output in a host buffer it allocates (*out, *out_size bytes; free it with phi_inflate_free): one
+ * inflate whatever the output's size (phi_inflate needs a second call when cap is too small) */
+int phi_inflate_alloc(int32_t device, const void *in, int64_t n, int64_t chunk_bytes, int32_t flags, void **out, int64_t *out_size,
+                      phi_inflate_info *info);
+void phi_inflate_free(void *p);
+/* A gzip stream into a park: _begin, the compressed bytes in slices of any size through _add (gathered on the
+ * host), then _end inflates them on the park's device and parks the text as *count pieces of at most piece_bytes, indices
+ * *first .. *first + *count - 1 in stream order, which phi_add_reads_text_parked and phi_text_park_fetch take as they are.
+ * _end's status is phi_inflate's (PHI_ERR_INVALID for a corrupt stream: no piece is added), info its detail. */
+int phi_text_park_gzip_begin(phi_text_park *park, int64_t piece_bytes);
+int phi_text_park_gzip_add(phi_text_park *park, const void *data, int64_t n);
+int phi_text_park_gzip_end(phi_text_park *park, int32_t *first, int32_t *count, phi_inflate_info *info);
+/* the gzip member header at byte pos of data[0, n): *deflate_start = the offset of its deflate data (FEXTRA, FNAME,
+ * FCOMMENT skipped, FHCRC checked); PHI_ERR_INVALID when it is no header or is cut short */
+int phi_gzip_header(const void *data, int64_t n, int64_t pos, int64_t *deflate_start);
+/* CRC32 (the gzip one) of A followed by B, from crc(A), crc(B) and |B| */
+uint32_t phi_crc32_combine(uint32_t crc_a, uint32_t crc_b, int64_t len_b);
+
 #ifdef __cplusplus
 }
 #endif

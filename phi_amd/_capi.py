@@ -29,7 +29,11 @@ SYMBOLS = [
     "phi_peers_create", "phi_peers_join", "phi_peers_allreduce_hits", "phi_peers_exchange", "phi_peers_destroy",
     "phi_ipc_unique_id", "phi_ipc_init", "phi_ipc_info", "phi_ipc_allreduce_hits", "phi_ipc_flush", "phi_ipc_exchange", "phi_ipc_check", "phi_ipc_destroy",
     "phi_edit_distances", "phi_edit_alignments",
+    "phi_inflate", "phi_inflate_alloc", "phi_inflate_free", "phi_gzip_header", "phi_crc32_combine",
+    "phi_text_park_gzip_begin", "phi_text_park_gzip_add", "phi_text_park_gzip_end",
 ]
+PHI_INFLATE_NO_FINDER = 1
+PHI_INFLATE_CHUNK_DEFAULT = 64 << 10          # include/phi_amd.h
 
 
 class PhiIndexInfo(C.Structure):
@@ -51,6 +55,11 @@ class PhiResult(C.Structure):
         ("n_walks", C.c_int32), ("n_minimizers", C.POINTER(C.c_int64)), ("n_anchors", C.POINTER(C.c_int64)),
         ("spectrum_size", C.c_int64), ("filtered", C.c_int64), ("retained", C.c_int64), ("n_in_model", C.c_int64),
     ]
+
+
+class PhiInflateInfo(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("in_bytes", "out_bytes", "members", "chunks", "confirmed", "redecoded", "marker_bytes")] + [
+        ("device_ms", C.c_double), ("detail", C.c_char * 192)]
 
 
 _lib = None
@@ -139,9 +148,19 @@ def load():
     L.phi_walk_entries.argtypes = [vp, vp, i64, C.POINTER(i64)]
     L.phi_edit_distances.argtypes = [vp, vp, vp, vp, vp, i64, i64, vp]
     L.phi_edit_alignments.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp, vp, vp]
+    L.phi_inflate.argtypes = [i32, vp, i64, vp, i64, i64, i32, C.POINTER(i64), C.POINTER(PhiInflateInfo)]
+    L.phi_inflate_alloc.argtypes = [i32, vp, i64, i64, i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(PhiInflateInfo)]
+    L.phi_inflate_free.argtypes = [vp]
+    L.phi_inflate_free.restype = None
+    L.phi_text_park_gzip_begin.argtypes = [vp, i64]
+    L.phi_text_park_gzip_add.argtypes = [vp, vp, i64]
+    L.phi_text_park_gzip_end.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(PhiInflateInfo)]
+    L.phi_gzip_header.argtypes = [vp, i64, i64, C.POINTER(i64)]
+    L.phi_crc32_combine.argtypes = [C.c_uint32, C.c_uint32, i64]
+    L.phi_crc32_combine.restype = C.c_uint32
     for name in SYMBOLS:
         f = getattr(L, name)          # AttributeError here = the library does not export the ABI
-        if f.restype is C.c_int and name not in ("phi_strerror", "phi_last_error", "phi_ctx_destroy"):
+        if f.restype is C.c_int and name not in ("phi_strerror", "phi_last_error", "phi_ctx_destroy", "phi_crc32_combine", "phi_inflate_free"):
             f.restype = C.c_int
     _lib = L
     return L

@@ -391,6 +391,47 @@ class Context:
         return n.value, ms.value, b.value
 
 
+def _info(info):
+    return {n: getattr(info, n) for n, _ in _capi.PhiInflateInfo._fields_ if n != "detail"}
+
+
+def inflate(data, device=0, chunk_bytes=0, finder=True, as_array=False):
+    """A gzip file (bytes; any number of members) inflated on `device` (include/phi_amd.h phi_inflate_alloc: one inflate,
+    whatever the output's size).  Returns (text, info): text as bytes (a uint8 numpy array with as_array), info a dict of
+    phi_inflate_info.  chunk_bytes (0: the default) and finder=False are test knobs.  PhiError(PHI_ERR_INVALID) for a
+    corrupt stream."""
+    L = _capi.load()
+    buf = np.frombuffer(data, np.uint8) if not isinstance(data, np.ndarray) else data
+    flags = 0 if finder else _capi.PHI_INFLATE_NO_FINDER
+    p, size, info = C.c_void_p(), C.c_int64(), _capi.PhiInflateInfo()
+    rc = L.phi_inflate_alloc(device, _ptr(buf), len(buf), chunk_bytes, flags, C.byref(p), C.byref(size), C.byref(info))
+    if rc:
+        raise PhiError(rc, info.detail.decode())
+    try:
+        out = np.empty(size.value, np.uint8)
+        if size.value:
+            C.memmove(out.ctypes.data, p, size.value)
+    finally:
+        L.phi_inflate_free(p)
+    return (out if as_array else out.tobytes()), _info(info)
+
+
+def gzip_header(data, pos=0):
+    """The offset of the deflate data of the gzip member header at data[pos:] (PhiError when there is none)."""
+    L = _capi.load()
+    buf = np.frombuffer(data, np.uint8) if not isinstance(data, np.ndarray) else data
+    q = C.c_int64()
+    rc = L.phi_gzip_header(_ptr(buf), len(buf), pos, C.byref(q))
+    if rc:
+        raise PhiError(rc, "no gzip member header")
+    return q.value
+
+
+def crc32_combine(crc_a, crc_b, len_b):
+    """zlib.crc32(a + b) from zlib.crc32(a), zlib.crc32(b) and len(b)."""
+    return _capi.load().phi_crc32_combine(crc_a, crc_b, len_b)
+
+
 class TextPark:
     """Pieces of a reads text in device memory before any context wants them (include/phi_amd.h phi_text_park_*)."""
 
@@ -408,6 +449,23 @@ class TextPark:
         if rc:
             raise PhiError(rc, "phi_text_park_add failed")
         return idx.value
+
+    def add_gzip(self, slices, piece_bytes):
+        """A gzip stream given as compressed slices (bytes each), inflated on the park's device and parked as pieces of at
+        most piece_bytes in stream order (phi_text_park_gzip_*).  Returns (indices, info)."""
+        rc = self._L.phi_text_park_gzip_begin(self._h, piece_bytes)
+        if rc:
+            raise PhiError(rc, "phi_text_park_gzip_begin failed")
+        for sl in slices:
+            buf = np.frombuffer(sl, np.uint8) if not isinstance(sl, np.ndarray) else sl
+            rc = self._L.phi_text_park_gzip_add(self._h, _ptr(buf), len(buf))
+            if rc:
+                raise PhiError(rc, "phi_text_park_gzip_add failed")
+        first, count, info = C.c_int32(), C.c_int32(), _capi.PhiInflateInfo()
+        rc = self._L.phi_text_park_gzip_end(self._h, C.byref(first), C.byref(count), C.byref(info))
+        if rc:
+            raise PhiError(rc, info.detail.decode())
+        return list(range(first.value, first.value + count.value)), _info(info)
 
     def fetch(self, index):
         n = self._L.phi_text_park_bytes(self._h, index)

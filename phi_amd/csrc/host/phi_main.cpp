@@ -271,11 +271,60 @@ static int run(const Options &o)
         const int64_t least = getenv("PHI_TEXT_PARK_MIN") ? atoll(getenv("PHI_TEXT_PARK_MIN")) : ((int64_t)256 << 20);
         park_on = stat(reads_file.c_str(), &st) == 0 && S_ISREG(st.st_mode) && (int64_t)st.st_size >= least;
     }
+    // Single-stream gzip reads (not BGZF) of a one-GPU run, from PHI_INFLATE_MIN compressed bytes on: inflated on the device
+    // (phi_text_park_gzip_*) instead of one host thread, the text parked in pieces of chunk_bytes that the
+    // reads stage takes as it takes any parked chunk.  PHI_INFLATE=0 or PHI_TEXT_PARK=0 keeps the host inflater; a stream the
+    // device finds corrupt goes to the host inflater too, which reports it as it always has.
+    const int64_t inflate_min = getenv("PHI_INFLATE_MIN") ? atoll(getenv("PHI_INFLATE_MIN")) : ((int64_t)16 << 20);
+    const bool inflate_on = devices.size() == 1 && !(getenv("PHI_INFLATE") && atoi(getenv("PHI_INFLATE")) == 0) &&
+                            !(getenv("PHI_TEXT_PARK") && atoi(getenv("PHI_TEXT_PARK")) == 0);
+    int64_t inflated_bytes = 0, inflated_in = 0, inflated_chunks = 0, inflated_confirmed = 0, inflated_again = 0;
+    auto device_inflate = [&](const std::string &rf) -> bool {
+        if (!inflate_on) return false;
+        struct stat st;
+        if (stat(rf.c_str(), &st) != 0 || !S_ISREG(st.st_mode) || (int64_t)st.st_size < std::max<int64_t>(inflate_min, 18)) return false;
+        FILE *fp = fopen(rf.c_str(), "rb");
+        if (!fp) return false;
+        unsigned char u[14];
+        if (fread(u, 1, sizeof u, fp) != sizeof u || u[0] != 0x1f || u[1] != 0x8b || ((u[3] & 4) && u[12] == 'B' && u[13] == 'C')) {
+            fclose(fp);                                       // not gzip, or BGZF (the host pool): today's path, nothing read
+            return false;
+        }
+        std::vector<char> gz((size_t)st.st_size);
+        memcpy(gz.data(), u, sizeof u);
+        const size_t got = sizeof u + fread(gz.data() + sizeof u, 1, gz.size() - sizeof u, fp);
+        fclose(fp);
+        if (got != gz.size()) return false;
+        {
+            // the device is free once the GFA is parsed (as for parking)
+            std::unique_lock<std::mutex> lk(Q.mu);
+            Q.cv.wait(lk, [&] { return park_go.load() || graph_ready.load() || Q.stop; });
+            if (Q.stop) return false;
+        }
+        if (!park && phi_text_park_create(devices[0], &park) != PHI_OK) return false;
+        int32_t first = -1, count = 0;
+        phi_inflate_info info;
+        if (phi_text_park_gzip_begin(park, chunk_bytes) != PHI_OK || phi_text_park_gzip_add(park, gz.data(), (int64_t)gz.size()) != PHI_OK ||
+            phi_text_park_gzip_end(park, &first, &count, &info) != PHI_OK)
+            return false;
+        {
+            std::lock_guard<std::mutex> lk(Q.mu);
+            for (int32_t i = 0; i < count; i++) {
+                Q.buf.push_back(Chunk{nullptr, phi_text_park_bytes(park, first + i), first + i});
+                Q.q_full.push_back((int)Q.buf.size() - 1);
+            }
+        }
+        Q.cv.notify_all();
+        inflated_bytes += info.out_bytes; inflated_in += info.in_bytes; inflated_chunks += info.chunks;
+        inflated_confirmed += info.confirmed; inflated_again += info.redecoded;
+        return true;
+    };
     auto start_reads = [&]() {
       f_reads = std::async(std::launch::async, [&, rf = reads_file]() {
         Stage st("reads file -> text chunks [thread]");
         phi_text_stream *ts = nullptr;
-        int r = phi_text_stream_open(rf.c_str(), &ts, rerr, sizeof rerr);
+        const bool on_device = device_inflate(rf);             // (then only the end of the stream is left to queue)
+        int r = on_device ? PHI_HOST_OK : phi_text_stream_open(rf.c_str(), &ts, rerr, sizeof rerr);
         int slot = -1, fly_slot = -1;
         int32_t fly_idx = -1;
         for (;;) {
@@ -286,7 +335,9 @@ static int run(const Options &o)
                 slot = Q.q_free.front(); Q.q_free.pop_front();
             }
             int64_t n = 0;
-            if (r == PHI_HOST_OK) {
+            if (r == PHI_HOST_OK && on_device) {
+                n = 0;
+            } else if (r == PHI_HOST_OK) {
                 n = phi_text_stream_read(ts, Q.buf[(size_t)slot].text, chunk_bytes, rerr, sizeof rerr);
                 if (n < 0) { r = (int)n; }
             } else n = r;
@@ -707,6 +758,9 @@ static int run(const Options &o)
             peakrss() / 1024.0 / 1024.0 / 1024.0);
     if (timing) {
         if (parked_bytes) fprintf(stderr, "[phi timing] main: %lld bytes of the reads text waited in device memory for the index\n", (long long)parked_bytes);
+        if (inflated_bytes)
+            fprintf(stderr, "[phi timing] main: %lld bytes inflated on the device from %lld gzip bytes (%lld chunks: %lld confirmed at their start, %lld decoded again)\n",
+                    (long long)inflated_bytes, (long long)inflated_in, (long long)inflated_chunks, (long long)inflated_confirmed, (long long)inflated_again);
         fprintf(stderr, "[phi timing] main: %d text chunk(s) of up to %lld bytes%s on %d GPU(s); %lld bases through the host reader; FASTA closed at epoch %.6f%s\n",
                 n_chunks.load(), (long long)chunk_bytes, n_chunks >= 2 && pinned ? ", pinned" : "", n_dev, (long long)host_parsed_bases, realtime(),
                 o.detached ? "; teardown detached" : "");

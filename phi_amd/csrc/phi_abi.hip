@@ -1637,6 +1637,9 @@ struct phi_text_park {
     std::deque<Piece> pieces;                                  // (a deque: references stay valid while pieces are added)
     std::vector<DevBuf> spare;                                 // buffers of released pieces
     std::vector<void *> pinned;
+    std::vector<char> gz;                                      // a gzip stream being gathered (phi_text_park_gzip_*)
+    int64_t gz_piece = 0;
+    bool gz_on = false;
 };
 
 int phi_text_park_create(int32_t device, phi_text_park **out)
@@ -1747,6 +1750,77 @@ void phi_text_park_destroy(phi_text_park *p)
     for (void *h : p->pinned) (void)hipHostUnregister(h);
     if (p->stream) (void)hipStreamDestroy(p->stream);
     delete p;
+}
+
+extern "C" int phi_inflate_to_device(int32_t device, const void *in, int64_t n, int64_t chunk_bytes, int32_t flags, void **d_out,
+                                     int64_t *out_size, phi_inflate_info *info);      // inflate.hip
+
+int phi_text_park_gzip_begin(phi_text_park *p, int64_t piece_bytes)
+{
+    if (!p || piece_bytes <= 0) return PHI_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(p->mu);
+    p->gz.clear();
+    p->gz_piece = piece_bytes;
+    p->gz_on = true;
+    return PHI_OK;
+}
+
+int phi_text_park_gzip_add(phi_text_park *p, const void *data, int64_t n)
+{
+    if (!p || !p->gz_on || n < 0 || (n > 0 && !data)) return PHI_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(p->mu);
+    p->gz.insert(p->gz.end(), (const char *)data, (const char *)data + n);
+    return PHI_OK;
+}
+
+// the gathered stream inflated on the park's device (phi_inflate), its text cut into pieces of at most gz_piece bytes
+int phi_text_park_gzip_end(phi_text_park *p, int32_t *first, int32_t *count, phi_inflate_info *info)
+{
+    if (info) memset(info, 0, sizeof(*info));
+    if (!p || !p->gz_on || !first || !count) return PHI_ERR_INVALID;
+    *first = -1;
+    *count = 0;
+    p->gz_on = false;
+    std::vector<char> gz;
+    gz.swap(p->gz);
+    void *d = nullptr;
+    int64_t total = 0;
+    int rc = phi_inflate_to_device(p->device, gz.data(), (int64_t)gz.size(), 0, 0, &d, &total, info);
+    if (rc) return rc;
+    std::vector<char>().swap(gz);
+    if (hipSetDevice(p->device) != hipSuccess) { (void)hipFree(d); return PHI_ERR_DEVICE; }
+    for (int64_t at = 0; at < total && !rc; at += p->gz_piece) {
+        const int64_t n = std::min<int64_t>(p->gz_piece, total - at);
+        phi_text_park::Piece pc;
+        const size_t want = (size_t)n + 64;
+        {
+            std::lock_guard<std::mutex> lk(p->mu);
+            for (size_t i = 0; i < p->spare.size(); i++)
+                if (p->spare[i].cap >= want) { pc.d = p->spare[i]; p->spare.erase(p->spare.begin() + (ptrdiff_t)i); break; }
+        }
+        if (!pc.d.p) {
+            if (hipMalloc(&pc.d.p, want) != hipSuccess) { (void)hipGetLastError(); rc = PHI_ERR_NOMEM; break; }
+            pc.d.cap = want;
+        }
+        pc.n = n;
+        if (hipMemcpy(&pc.first, (char *)d + at, 1, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipEventCreateWithFlags(&pc.ev, hipEventDisableTiming) != hipSuccess ||
+            hipMemcpyAsync(pc.d.p, (char *)d + at, (size_t)n, hipMemcpyDeviceToDevice, p->stream) != hipSuccess ||
+            hipEventRecord(pc.ev, p->stream) != hipSuccess) {
+            (void)hipGetLastError();
+            if (pc.ev) (void)hipEventDestroy(pc.ev);
+            (void)hipFree(pc.d.p);
+            rc = PHI_ERR_DEVICE;
+            break;
+        }
+        std::lock_guard<std::mutex> lk(p->mu);
+        p->pieces.push_back(pc);
+        if (*first < 0) *first = (int32_t)p->pieces.size() - 1;
+        (*count)++;
+    }
+    (void)hipStreamSynchronize(p->stream);                    // (the pieces' copies read d)
+    (void)hipFree(d);
+    return rc;
 }
 
 int phi_add_reads_text_parked(phi_ctx *c, phi_text_park *p, int32_t index, int32_t *irregular)
