@@ -442,6 +442,27 @@ int phi_gzip_header(const void *data, int64_t n, int64_t pos, int64_t *deflate_s
 /* CRC32 (the gzip one) of A followed by B, from crc(A), crc(B) and |B| */
 uint32_t phi_crc32_combine(uint32_t crc_a, uint32_t crc_b, int64_t len_b);
 
+/* A gzip GFA split on the device: the file (RFC 1952, any number of members) is inflated on the context's
+ * device, the walk field of every W-line -- everything after its 6th tab, tags included, by the host reader's line rules
+ * (include/phi_host.h) -- stays there, laid out as phi_walk_text_upload lays it out (phi_walk_text_resolve follows as after
+ * an upload), and *host_text receives the rest: the file with every walk field cut out (a W-line then ends right after its
+ * 6th tab), *host_n bytes, NUL-terminated, in pinned memory the caller lets go with phi_gfa_gzip_free once the host reader
+ * is done with it (phi_gfa_read_deferred_text borrows it).  The inflated text is freed before the call returns.
+ * chunk_bytes as for phi_inflate.  PHI_ERR_INVALID for a corrupt stream (info->inflate.detail says why); PHI_ERR_UNSUPPORTED
+ * when the split refuses (more W-lines than it lists: PHI_GFA_SPLIT_CAP, default 2^20); nothing is kept on either error.
+ * info (may be NULL): the inflate's detail, the text's bytes, the bytes returned to the host, the walk bytes kept and the
+ * number of walks. */
+typedef struct {
+    int64_t text_bytes;        /* inflated bytes */
+    int64_t host_bytes;        /* bytes of *host_text */
+    int64_t walk_bytes;        /* bytes of walk fields left on the device */
+    int32_t n_walks;
+    phi_inflate_info inflate;
+} phi_gfa_gzip_info;
+int phi_gfa_gzip_split(phi_ctx *ctx, const void *gz, int64_t n, int64_t chunk_bytes, char **host_text, int64_t *host_n,
+                       phi_gfa_gzip_info *info);
+void phi_gfa_gzip_free(char *host_text);
+
 #ifdef __cplusplus
 }
 #endif

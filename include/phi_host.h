@@ -54,6 +54,12 @@ int phi_gfa_read(const char *path, phi_graph **out, char *err, int err_cap);
 typedef struct { const char *text; int64_t n; } phi_host_walk_text;
 typedef void (*phi_walk_text_fn)(void *user, const phi_host_walk_text *walks, int32_t n_walks);
 int phi_gfa_read_deferred(const char *path, phi_graph **out, phi_walk_text_fn on_text, void *user, char *err, int err_cap);
+/* phi_gfa_read_deferred on text already in memory, e.g. phi_gfa_gzip_split's host text (phi_amd.h): the graph, hap names, name
+ * index and walks are those phi_gfa_read_deferred returns for a file holding text[0, n) (a W-line cut right after its 6th tab
+ * has an empty walk field).  The text is BORROWED, not copied: it must stay valid and unchanged until the walks are resolved
+ * (phi_graph_set_walk_off, phi_graph_resolve_walks) or the graph is freed, whichever comes first; the caller frees it.
+ * name_for_messages (may be NULL) stands for the file in messages. */
+int phi_gfa_read_deferred_text(const char *text, int64_t n, const char *name_for_messages, phi_graph **out, char *err, int err_cap);
 int phi_graph_walks_deferred(const phi_graph *g);
 int phi_graph_walk_texts(const phi_graph *g, phi_host_walk_text *out, int32_t cap);
 int phi_graph_name_index(const phi_graph *g, const char **prefix, int32_t *prefix_n, const int32_t **num2id, int64_t *n_num);

@@ -31,6 +31,7 @@ SYMBOLS = [
     "phi_edit_distances", "phi_edit_alignments",
     "phi_inflate", "phi_inflate_alloc", "phi_inflate_free", "phi_gzip_header", "phi_crc32_combine",
     "phi_text_park_gzip_begin", "phi_text_park_gzip_add", "phi_text_park_gzip_end",
+    "phi_gfa_gzip_split", "phi_gfa_gzip_free",
 ]
 PHI_INFLATE_NO_FINDER = 1
 PHI_INFLATE_CHUNK_DEFAULT = 64 << 10          # include/phi_amd.h
@@ -60,6 +61,11 @@ class PhiResult(C.Structure):
 class PhiInflateInfo(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("in_bytes", "out_bytes", "members", "chunks", "confirmed", "redecoded", "marker_bytes")] + [
         ("device_ms", C.c_double), ("detail", C.c_char * 192)]
+
+
+class PhiGfaGzipInfo(C.Structure):
+    _fields_ = [("text_bytes", C.c_int64), ("host_bytes", C.c_int64), ("walk_bytes", C.c_int64), ("n_walks", C.c_int32),
+                ("inflate", PhiInflateInfo)]
 
 
 _lib = None
@@ -158,9 +164,12 @@ def load():
     L.phi_gzip_header.argtypes = [vp, i64, i64, C.POINTER(i64)]
     L.phi_crc32_combine.argtypes = [C.c_uint32, C.c_uint32, i64]
     L.phi_crc32_combine.restype = C.c_uint32
+    L.phi_gfa_gzip_split.argtypes = [vp, vp, i64, i64, C.POINTER(vp), C.POINTER(i64), C.POINTER(PhiGfaGzipInfo)]
+    L.phi_gfa_gzip_free.argtypes = [vp]
+    L.phi_gfa_gzip_free.restype = None
     for name in SYMBOLS:
         f = getattr(L, name)          # AttributeError here = the library does not export the ABI
-        if f.restype is C.c_int and name not in ("phi_strerror", "phi_last_error", "phi_ctx_destroy", "phi_crc32_combine", "phi_inflate_free"):
+        if f.restype is C.c_int and name not in ("phi_strerror", "phi_last_error", "phi_ctx_destroy", "phi_crc32_combine", "phi_inflate_free", "phi_gfa_gzip_free"):
             f.restype = C.c_int
     _lib = L
     return L

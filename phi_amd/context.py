@@ -379,6 +379,26 @@ class Context:
             self._chk(self._L.phi_walk_entries(self._h, _ptr(out), n.value, C.byref(n)))
         return out
 
+    def gfa_gzip_split(self, data, chunk_bytes=0):
+        """A gzip GFA (bytes) inflated and split on this context's device (include/phi_amd.h phi_gfa_gzip_split): the walk
+        fields stay there for phi_walk_text_resolve.  Returns (host_text, info): the text with every walk field cut out, as
+        bytes, and phi_gfa_gzip_info as a dict (its inflate part a dict of phi_inflate_info).  PhiError(PHI_ERR_INVALID) for
+        a corrupt stream, PhiError(PHI_ERR_UNSUPPORTED) when the split refuses."""
+        p, n, info = self._gfa_gzip_split_raw(data, chunk_bytes)
+        try:
+            return C.string_at(p, n) if n else b"", info
+        finally:
+            self._L.phi_gfa_gzip_free(p)
+
+    def _gfa_gzip_split_raw(self, data, chunk_bytes=0):
+        """(pinned host text pointer, its bytes, info): the caller lets it go with phi_gfa_gzip_free."""
+        buf = np.frombuffer(data, np.uint8) if not isinstance(data, np.ndarray) else data
+        p, n, info = C.c_void_p(), C.c_int64(), _capi.PhiGfaGzipInfo()
+        self._chk(self._L.phi_gfa_gzip_split(self._h, _ptr(buf), len(buf), chunk_bytes, C.byref(p), C.byref(n), C.byref(info)))
+        d = {k: getattr(info, k) for k in ("text_bytes", "host_bytes", "walk_bytes", "n_walks")}
+        d["inflate"] = _info(info.inflate)
+        return p, n.value, d
+
     def device_synchronize(self):
         self._chk(self._L.phi_device_synchronize(self._h))
 

@@ -385,17 +385,24 @@ phi_graph::~phi_graph() { if (reaper.joinable()) reaper.join(); free(seq_concat)
 
 static int resolve_walks(GfaState &st, phi_graph *g, StageTimer &tm, char *err, int err_cap);
 
-static int gfa_read_impl(const char *path, phi_graph **out, bool defer, phi_walk_text_fn on_text, void *user, char *err, int err_cap)
+// mem != NULL: the text is mem[0, mem_n), borrowed (path only names it in messages); else the file at path
+static int gfa_read_impl(const char *path, const char *mem, int64_t mem_n, phi_graph **out, bool defer, phi_walk_text_fn on_text, void *user,
+                         char *err, int err_cap)
 {
-    if (!path || !out) return fail(err, err_cap, PHI_HOST_ERR_INVALID, "null argument");
+    if ((!path && !mem) || !out || mem_n < 0) return fail(err, err_cap, PHI_HOST_ERR_INVALID, "null argument");
     *out = nullptr;
     StageTimer tm;
     GfaState *stp = new GfaState();
     struct StateGuard { GfaState *&p; ~StateGuard() { delete p; } } state_guard{stp};      // (handed to the graph when the walks stay text)
     Text &text = stp->text;
-    if (const int lr = text.load(path))
-        return fail(err, err_cap, PHI_HOST_ERR_IO, lr == -2 ? "gzip stream corrupt in the GFA file %s" : "failed to load the GFA file %s", path);
-    tm.lap(text.map ? "map" : "read / inflate");
+    if (mem) {
+        text.p = mem;
+        text.n = (size_t)mem_n;
+    } else {
+        if (const int lr = text.load(path))
+            return fail(err, err_cap, PHI_HOST_ERR_IO, lr == -2 ? "gzip stream corrupt in the GFA file %s" : "failed to load the GFA file %s", path);
+        tm.lap(text.map ? "map" : "read / inflate");
+    }
 
     // ---- lines and fields, on all threads over slices of the text cut at line ends
     const char *const t0 = text.p, *const tend = text.p + text.n;
@@ -893,7 +900,7 @@ static int resolve_walks(GfaState &st, phi_graph *g, StageTimer &tm, char *err, 
 
 extern "C" {
 
-int phi_gfa_read(const char *path, phi_graph **out, char *err, int err_cap) { return gfa_read_impl(path, out, false, nullptr, nullptr, err, err_cap); }
+int phi_gfa_read(const char *path, phi_graph **out, char *err, int err_cap) { return gfa_read_impl(path, nullptr, 0, out, false, nullptr, nullptr, err, err_cap); }
 
 /* The same, but the walks stay TEXT: on_text (optional) is called on a thread of its own as soon as the walk fields are known
  * -- long before the names are --, and the graph comes back without walk_off / walk_vtx.  The caller resolves the walks on the
@@ -901,7 +908,13 @@ int phi_gfa_read(const char *path, phi_graph **out, char *err, int err_cap) { re
  * or has them resolved here after all: phi_graph_resolve_walks. */
 int phi_gfa_read_deferred(const char *path, phi_graph **out, phi_walk_text_fn on_text, void *user, char *err, int err_cap)
 {
-    return gfa_read_impl(path, out, true, on_text, user, err, err_cap);
+    return gfa_read_impl(path, nullptr, 0, out, true, on_text, user, err, err_cap);
+}
+/* The same from text in memory (the host part of phi_gfa_gzip_split, include/phi_amd.h): only how the text is loaded differs */
+int phi_gfa_read_deferred_text(const char *text, int64_t n, const char *name_for_messages, phi_graph **out, char *err, int err_cap)
+{
+    if (!text) return fail(err, err_cap, PHI_HOST_ERR_INVALID, "null argument");
+    return gfa_read_impl(name_for_messages ? name_for_messages : "(memory)", text, n, out, true, nullptr, nullptr, err, err_cap);
 }
 int phi_graph_walks_deferred(const phi_graph *g) { return g && g->state != nullptr; }
 int phi_graph_walk_texts(const phi_graph *g, phi_host_walk_text *out, int32_t cap)

@@ -418,7 +418,68 @@ static int run(const Options &o)
         f_ctx.wait(); stop_reads();
         return 1;
     };
+    // A single-stream gzip GFA (not BGZF) of a one-GPU run, from PHI_GFA_INFLATE_MIN compressed bytes on (default 256 MB):
+    // inflated and split on the device (phi_gfa_gzip_split).  The walk fields stay in HBM whatever
+    // PHI_WALK_TEXT_MIN says, and only the rest of the text -- S-lines, L-lines, W-line heads -- comes to the host reader.
+    // Whatever that route does not finish (a corrupt stream, a refused split, walks counted differently, names not
+    // <prefix><number>, a W-line among the S-lines, irregular walk text) is read again from the file, from scratch, as below:
+    // messages, exit status and output are those of PHI_GFA_INFLATE=0.
+    bool gfa_on_device = false;
     {
+        const int64_t gfa_min = getenv("PHI_GFA_INFLATE_MIN") ? atoll(getenv("PHI_GFA_INFLATE_MIN")) : ((int64_t)256 << 20);
+        const bool gfa_inflate_on = n_dev == 1 && defer_walks && !(getenv("PHI_GFA_INFLATE") && atoi(getenv("PHI_GFA_INFLATE")) == 0);
+        std::vector<char> gz;
+        struct stat st;
+        if (gfa_inflate_on && stat(gfa_file.c_str(), &st) == 0 && S_ISREG(st.st_mode) && (int64_t)st.st_size >= std::max<int64_t>(gfa_min, 18)) {
+            if (FILE *fp = fopen(gfa_file.c_str(), "rb")) {
+                unsigned char u[14];
+                if (fread(u, 1, sizeof u, fp) == sizeof u && u[0] == 0x1f && u[1] == 0x8b && !((u[3] & 4) && u[12] == 'B' && u[13] == 'C')) {
+                    Stage st2("GFA gzip read (device context starting)");
+                    gz.resize((size_t)st.st_size);
+                    memcpy(gz.data(), u, sizeof u);
+                    if (sizeof u + fread(gz.data() + sizeof u, 1, gz.size() - sizeof u, fp) != gz.size()) std::vector<char>().swap(gz);
+                }
+                fclose(fp);
+            }
+        }
+        if (!gz.empty()) {
+            Stage st2("GFA on the device: inflate, split, parse, walks");
+            const char *why = nullptr;
+            char *host_text = nullptr;
+            int64_t host_n = 0;
+            phi_gfa_gzip_info gi;
+            memset(&gi, 0, sizeof gi);
+            if (f_ctx.get()) why = "no device context";
+            int r = why ? 0 : phi_gfa_gzip_split(ctxs[0], gz.data(), (int64_t)gz.size(), 0, &host_text, &host_n, &gi);
+            std::vector<char>().swap(gz);
+            if (!why && r) why = r == PHI_ERR_INVALID ? "gzip stream corrupt" : r == PHI_ERR_UNSUPPORTED ? "split refused" : "device error";
+            if (!why && phi_gfa_read_deferred_text(host_text, host_n, gfa_file.c_str(), &g, err, sizeof err) != PHI_HOST_OK) why = "host reader failed on the split text";
+            if (!why && phi_graph_n_walks(g) != gi.n_walks) why = "walk count differs from the host reader's";
+            const char *prefix = nullptr; int32_t prefix_n = 0; const int32_t *num2id = nullptr; int64_t n_num = 0;
+            if (!why && phi_graph_name_index(g, &prefix, &prefix_n, &num2id, &n_num) != PHI_HOST_OK) why = "names not <prefix><number>, or a W-line among the S-lines";
+            if (!why) {
+                std::vector<int64_t> woff((size_t)phi_graph_n_walks(g) + 1, 0);
+                uint32_t irregular = 0;
+                if (phi_walk_text_resolve(ctxs[0], prefix, prefix_n, num2id, n_num, phi_graph_n_vtx(g), woff.data(), &irregular) != PHI_OK) why = "walks on the device failed";
+                else if (irregular) why = "irregular walk text";
+                else { phi_graph_set_walk_off(g, woff.data()); gfa_on_device = true; }
+            }
+            if (!gfa_on_device) {
+                if (g) { phi_graph_free(g); g = nullptr; }
+                if (!f_ctx.get()) (void)phi_walk_text_upload(ctxs[0], nullptr, 0);          // (lets the text on the device go)
+                err[0] = 0;
+            }
+            phi_gfa_gzip_free(host_text);                            // (the reader borrowed it until the walks were resolved)
+            if (timing) {
+                if (gfa_on_device)
+                    fprintf(stderr, "[phi timing] main: GFA: %lld bytes inflated on the device from %lld gzip bytes (%lld chunks); %lld bytes to the host, %lld bytes of %d walks kept on the device\n",
+                            (long long)gi.text_bytes, (long long)gi.inflate.in_bytes, (long long)gi.inflate.chunks, (long long)gi.host_bytes, (long long)gi.walk_bytes, gi.n_walks);
+                else
+                    fprintf(stderr, "[phi timing] main: GFA: not on the device (%s): the host reader from the file\n", why);
+            }
+        }
+    }
+    if (!gfa_on_device) {
         Stage st("GFA read + parse");
         int r;
         if (defer_walks)
@@ -437,7 +498,7 @@ static int run(const Options &o)
     }
     park_go = true;                                           // (the reads text may go to device memory from here on: see start_reads)
     Q.cv.notify_all();
-    if (defer_walks) {
+    if (defer_walks && !gfa_on_device) {
         Stage st("walks");
         bool on_device = false;
         if (wt.rc) { fprintf(stderr, "[E::%s] walk text to the device: %s: %s\n", "main", phi_strerror(wt.rc), phi_last_error(ctxs[0])); stop_reads(); return 1; }

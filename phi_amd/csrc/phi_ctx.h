@@ -92,6 +92,7 @@ struct phi_ctx {
 
     // ---- the walks resolved on the device from the text of the W-lines (walk_text.hip): the text while it is being uploaded and
     //      resolved; afterwards d_walk_vtx holds the entries and phi_set_graph(walk_vtx = NULL) takes them from there
+#define WT_TILE 4096                                  // bytes per tile; every walk's text starts on a tile boundary of d_text
     struct PhiWalkText {
         bool ready = false;
         int32_t n_walks = 0;

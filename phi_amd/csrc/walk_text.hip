@@ -25,8 +25,6 @@
 #define HIPCHK(call) do { int rc_ = phi_hip_check(c, (call), #call); if (rc_) return rc_; } while (0)
 #define PHICHK(call) do { int rc_ = (call); if (rc_) return rc_; } while (0)
 
-#define WT_TILE 4096            // bytes per tile; every walk's text starts on a tile boundary of the device buffer
-
 namespace {
 
 __device__ __forceinline__ bool is_step(unsigned c) { return c == '>' || c == '<'; }

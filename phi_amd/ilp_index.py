@@ -29,7 +29,7 @@ HOST_SYMBOLS = [
     "phi_reads_stream_bases", "phi_reads_stream_close", "phi_reads_stream_open_blocks",
     "phi_text_stream_open", "phi_text_stream_read", "phi_text_stream_close",
     "phi_gfa_read_deferred", "phi_graph_walks_deferred", "phi_graph_walk_texts", "phi_graph_name_index", "phi_graph_resolve_walks",
-    "phi_graph_set_walk_off",
+    "phi_graph_set_walk_off", "phi_gfa_read_deferred_text",
 ]
 
 WALK_TEXT_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_int32)
@@ -95,6 +95,7 @@ def host_lib():
     L.phi_graph_name_index.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int32), C.POINTER(vp), C.POINTER(C.c_int64)]
     L.phi_graph_resolve_walks.argtypes = [vp, C.c_char_p, C.c_int]
     L.phi_graph_set_walk_off.argtypes = [vp, vp]
+    L.phi_gfa_read_deferred_text.argtypes = [vp, C.c_int64, C.c_char_p, C.POINTER(vp), C.c_char_p, C.c_int]
     L.phi_hap_name.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int]
     L.phi_write_fasta.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int64]
     for n in HOST_SYMBOLS:
@@ -242,13 +243,16 @@ class DeferredGraph:
     to the context's GPU and resolves them there (include/phi_amd.h phi_walk_text_*); when the text is not of the kind
     the device takes -- or on request -- resolve_on_host() does what Graph does.  set_graph(ctx) hands the graph over."""
 
-    def __init__(self, path, on_text=None):
+    def __init__(self, path, on_text=None, _text=None):
         L = host_lib()
         self._L = L
         self._h = C.c_void_p()
         err = C.create_string_buffer(512)
         self._cb = WALK_TEXT_FN(on_text) if on_text else None
-        rc = L.phi_gfa_read_deferred(os.fsencode(path), C.byref(self._h), C.cast(self._cb, C.c_void_p) if self._cb else None, None, err, 512)
+        if _text is not None:                         # (address, bytes) of text in memory, borrowed: phi_gfa_read_deferred_text
+            rc = L.phi_gfa_read_deferred_text(_text[0], _text[1], os.fsencode(path), C.byref(self._h), err, 512)
+        else:
+            rc = L.phi_gfa_read_deferred(os.fsencode(path), C.byref(self._h), C.cast(self._cb, C.c_void_p) if self._cb else None, None, err, 512)
         if rc:
             raise HostError(rc, err.value.decode())
         h = self._h
@@ -264,6 +268,34 @@ class DeferredGraph:
         self.walk_off = None
         self.walk_vtx = None                          # stays None when the device resolved the walks
         self.on_device = False
+
+    @classmethod
+    def from_gzip_on_device(cls, path, ctx, chunk_bytes=0):
+        """A gzip GFA through the device route of the command line: inflated and split on ctx's GPU
+        (Context.gfa_gzip_split), the S-lines, L-lines and W-line heads read by the host reader from the split text, the
+        walks resolved on the device from the fields that never left it.  Whatever that route does not finish -- a walk
+        count that differs from the reader's, names not <prefix><number>, a W-line among the S-lines, irregular walk text --
+        is read again from the file and resolved on the host; .route says which ("device" or the reason).  PhiError for a
+        corrupt stream or a refused split (the file is then the caller's to read)."""
+        p, n, info = ctx._gfa_gzip_split_raw(open(path, "rb").read(), chunk_bytes)
+        try:
+            g = cls(path, _text=(p.value, n))
+            g.split_info = info
+            if g.num_walks != info["n_walks"]:
+                g.route = "walk count differs from the host reader's"
+            elif g.resolve_on_device(ctx, upload=False):
+                g.route = "device"
+                return g
+            else:
+                g.route = "irregular walk text" if getattr(g, "irregular", 0) else "names not <prefix><number>, or a W-line among the S-lines"
+            g.close()
+        finally:
+            ctx._L.phi_gfa_gzip_free(p)
+        ctx._chk(ctx._L.phi_walk_text_upload(ctx._h, None, 0))
+        h = cls(path)
+        h.split_info, h.route = info, g.route
+        h.resolve_on_host()
+        return h
 
     def close(self):
         if self._h:

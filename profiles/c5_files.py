@@ -4,6 +4,10 @@ and the 30x read set (34 M reads: ~10.5 GB of FASTQ) to a RAM disk, then the dro
 process start to closed FASTA, with its stage table (PHI_TIMING=1).  Not part of the default bench (20 GB of files).
 
     python3 profiles/c5_files.py [--config C5|C5s] [--dir /dev/shm/phi_c5] [--fasta] [--out gpurun_out/r03/c5_files.json]
+
+--gz: the GFA and the reads are each compressed as one gzip member (16 host threads, pigz-style, level --gz-level), and the
+runs alternate the two inflaters: on the device (the defaults: DESIGN.md 4.8 and 4.9) and on the host (PHI_GFA_INFLATE=0
+PHI_INFLATE=0), --runs of each, in one process.
 """
 import argparse
 import json
@@ -17,6 +21,37 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def gzip_file(src, dst, level, piece=32 << 20, threads=16):
+    """src as ONE gzip member written to dst, deflated by `threads` host threads in 32-MB pieces, each with the 32 KB before
+    it as its dictionary and ending on a sync flush (profiles/inflate_rate.py gzip_one_member, over a mapping of the file)"""
+    import mmap
+    import zlib
+    from concurrent.futures import ThreadPoolExecutor
+    with open(src, "rb") as f, open(dst, "wb") as o:
+        m = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
+        n = len(m)
+
+        def one(i):
+            c = zlib.compressobj(level, zlib.DEFLATED, -15, 9, zlib.Z_DEFAULT_STRATEGY, *([m[max(0, i - 32768):i]] if i else []))
+            last = i + piece >= n
+            return c.compress(m[i:i + piece]) + c.flush(zlib.Z_FINISH if last else zlib.Z_SYNC_FLUSH), zlib.crc32(m[i:i + piece]), min(piece, n - i)
+        o.write(b"\x1f\x8b\x08\x00\x00\x00\x00\x00\x00\x03")
+        crc = 0
+        with ThreadPoolExecutor(threads) as ex:
+            for i0 in range(0, n, piece * threads):                  # (a window of pieces at a time: bounded memory)
+                for body, c, ln in ex.map(one, range(i0, min(n, i0 + piece * threads), piece)):
+                    o.write(body)
+                    crc = phi_crc32_combine(crc, c, ln)
+        o.write(crc.to_bytes(4, "little") + (n & 0xffffffff).to_bytes(4, "little"))
+        m.close()
+    return os.path.getsize(dst)
+
+
+def phi_crc32_combine(a, b, len_b):
+    import phi_amd
+    return phi_amd.crc32_combine(a, b, len_b)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="C5")
@@ -25,6 +60,8 @@ def main():
     ap.add_argument("--runs", type=int, default=2)
     ap.add_argument("--out", default=None)
     ap.add_argument("--keep", action="store_true")
+    ap.add_argument("--gz", action="store_true", help="the GFA and the reads as one gzip member each; runs alternate device and host inflaters")
+    ap.add_argument("--gz-level", type=int, default=6)
     ap.add_argument("--gap", type=float, default=4.0, help="seconds between runs: the driver clears the 65 GB of HBM the last process gave back before it hands "
                     "them out again, and a process that starts within a second of the last one's end waits ~1 s in one of its large allocations "
                     "(r04i: PHI_TIMING_ALLOC=1 shows one hipMalloc of 11.4 GB taking 0.26 ms or 1 s, in alternate runs 1 s apart)")
@@ -56,16 +93,28 @@ def main():
         del g
         print(json.dumps(out), flush=True)
         phi = os.path.join(ROOT, "phi_amd", "PHI")
+        legs = [("plain", {})]
+        if args.gz:
+            for name in ("gfa", "rd"):
+                src = gfa if name == "gfa" else rd
+                t0 = time.perf_counter()
+                out[name + "_gz_bytes"] = gzip_file(src, src + ".gz", args.gz_level)
+                out[name + "_gz_s"] = time.perf_counter() - t0
+                os.remove(src)
+            gfa, rd = gfa + ".gz", rd + ".gz"
+            legs = [("device", {}), ("host", {"PHI_GFA_INFLATE": "0", "PHI_INFLATE": "0"})]
+            print(json.dumps({k: v for k, v in out.items() if k.endswith(("_gz_bytes", "_gz_s"))}), flush=True)
         runs = []
-        for i in range(args.runs):
+        for i in range(args.runs * len(legs)):
+            leg, leg_env = legs[i % len(legs)]
             time.sleep(args.gap)
             t_spawn = time.time()
             t0 = time.perf_counter()
-            r = subprocess.run([phi, "-g", gfa, "-r", rd, "-o", fa], capture_output=True, text=True, env=dict(os.environ, PHI_TIMING="1"))
+            r = subprocess.run([phi, "-g", gfa, "-r", rd, "-o", fa], capture_output=True, text=True, env=dict(os.environ, PHI_TIMING="1", **leg_env))
             dt = time.perf_counter() - t0
             stages, info = bench._phi_stage_table(r.stderr)
             log = [l for l in r.stderr.splitlines() if not l.startswith("syn")]
-            rec = {"rc": r.returncode, "wall_s": dt, "spawn_to_fasta_closed_s": info.get("fasta_closed_epoch", t_spawn + dt) - t_spawn,
+            rec = {"leg": leg, "rc": r.returncode, "wall_s": dt, "spawn_to_fasta_closed_s": info.get("fasta_closed_epoch", t_spawn + dt) - t_spawn,
                    "stages_s": {k: v for k, v in stages.items() if k != "detail"}, "detail_ms": stages.get("detail", {}),
                    "log": [l for l in log if not l.startswith("[phi timing] main: stage")][-160:]}
             for l in log:
@@ -73,10 +122,12 @@ def main():
                     rec["phi_line"] = l
                 if "resident now" in l:
                     rec["resident"] = l.split("main: ", 1)[1]
+                if "main: GFA: " in l:
+                    rec["gfa_route"] = l.split("main: GFA: ", 1)[1]
                 if l.startswith("Recombined haplotypes"):
                     rec["recombined"] = l[:300]
             runs.append(rec)
-            print(json.dumps({k: rec.get(k) for k in ("rc", "wall_s", "spawn_to_fasta_closed_s", "phi_line", "resident", "stages_s")}), flush=True)
+            print(json.dumps({k: rec.get(k) for k in ("leg", "rc", "wall_s", "gfa_route", "spawn_to_fasta_closed_s", "phi_line", "resident", "stages_s")}), flush=True)
             if r.returncode != 0:
                 print(r.stderr[-3000:])
                 break
