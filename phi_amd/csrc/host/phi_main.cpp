@@ -28,6 +28,7 @@
 // harness that starts the next GPU job at once would find them still held.
 // Exit status: 0; 1 on any error; 3 when --dp-budget was given and ran out before the path was proven optimal.
 #include <errno.h>
+#include <stdarg.h>
 #include <getopt.h>
 #include <signal.h>
 #include <stdio.h>
@@ -93,6 +94,7 @@ struct StageMarks {
         std::lock_guard<std::mutex> lk(mu);
         marks.push_back(M{name, b - t0_real, e - t0_real});
     }
+    void clear() { std::lock_guard<std::mutex> lk(mu); marks.clear(); }
     void print()
     {
         if (!on) return;
@@ -139,14 +141,129 @@ struct Options {
     bool detached = false;
 };
 
-// ---- the queue of raw text chunks between the reader thread and the device thread(s)
+// ---- the PHI_* knobs of a run, read once
+struct Knobs {
+    static bool off(const char *name) { const char *e = getenv(name); return e && atoi(e) == 0; }      // set to 0
+    static int64_t num(const char *name, int64_t dflt) { const char *e = getenv(name); return e ? atoll(e) : dflt; }
+    bool allow_same_device = getenv("PHI_ALLOW_SAME_DEVICE") != nullptr;      // (the tests run two contexts on one GPU)
+    bool read_chunk_set = getenv("PHI_READ_CHUNK") != nullptr;                // unset: the chunk is sized by the files (chunk_size)
+    int64_t read_chunk = read_chunk_set ? std::max<int64_t>(256, num("PHI_READ_CHUNK", 0)) : ((int64_t)64 << 20);
+    bool text_park = !off("PHI_TEXT_PARK");                                   // 0: neither the park nor the device inflater
+    int64_t text_park_min = num("PHI_TEXT_PARK_MIN", (int64_t)256 << 20);
+    int64_t text_park_max = num("PHI_TEXT_PARK_MAX", (int64_t)96 << 30);
+    bool inflate = text_park && !off("PHI_INFLATE");
+    int64_t inflate_min = num("PHI_INFLATE_MIN", (int64_t)16 << 20);
+    bool gfa_inflate = !off("PHI_GFA_INFLATE");
+    int64_t gfa_inflate_min = num("PHI_GFA_INFLATE_MIN", (int64_t)256 << 20);
+    bool walks_host = getenv("PHI_WALKS") && !strcmp(getenv("PHI_WALKS"), "host");
+    int64_t walk_text_min = num("PHI_WALK_TEXT_MIN", (int64_t)1 << 30);      // (see load_graph)
+    bool exchange_peers = getenv("PHI_EXCHANGE") && !strcmp(getenv("PHI_EXCHANGE"), "peers");
+    bool full_teardown = getenv("PHI_FULL_TEARDOWN") != nullptr;
+};
+
+// ---- what a file is: regular, its size, gzip (the 2-byte magic) and BGZF (a gzip header with the BC extra field)
+struct FileProbe { bool regular = false; int64_t size = 0; bool gzip = false, bgzf = false; };
+static FileProbe probe_file(const std::string &path)
+{
+    FileProbe p;
+    struct stat st;
+    if (stat(path.c_str(), &st) != 0 || !S_ISREG(st.st_mode)) return p;      // (nothing is read from a pipe)
+    p.regular = true; p.size = (int64_t)st.st_size;
+    if (FILE *fp = p.size > 0 ? fopen(path.c_str(), "rb") : nullptr) {
+        unsigned char u[14];
+        const size_t got = fread(u, 1, sizeof u, fp); fclose(fp);
+        p.gzip = got >= 2 && u[0] == 0x1f && u[1] == 0x8b;
+        p.bgzf = p.gzip && got == sizeof u && (u[3] & 4) && u[12] == 'B' && u[13] == 'C';
+    }
+    return p;
+}
+// a single-stream gzip file (not BGZF: that is the host pool's) of at least `least` bytes: one of the device inflaters' inputs
+static bool single_gzip(const FileProbe &p, int64_t least) { return p.regular && p.size >= std::max<int64_t>(least, 18) && p.gzip && !p.bgzf; }
+static bool read_file(const std::string &path, int64_t size, std::vector<char> &out)
+{
+    FILE *fp = fopen(path.c_str(), "rb");
+    if (!fp) return false;
+    out.resize((size_t)size);
+    const bool ok = fread(out.data(), 1, out.size(), fp) == out.size();
+    fclose(fp);
+    return ok;
+}
+
+// PHI_READ_CHUNK bytes per chunk; unset, 64 MB -- or for small plain files one chunk of the file's size (of the largest file, when
+// there are several jobs).  A gzip file, BGZF included, keeps 64 MB.
+static int64_t chunk_size(const Knobs &kn, const std::vector<std::string> &files)
+{
+    if (kn.read_chunk_set) return kn.read_chunk;
+    int64_t need = 0;
+    for (const std::string &rf : files) {
+        const FileProbe p = probe_file(rf);
+        int64_t want = kn.read_chunk;
+        if (p.regular && p.size > 0 && !p.gzip) want = std::min<int64_t>(kn.read_chunk, (p.size + 4095) & ~(int64_t)4095);
+        need = std::max(need, want);
+    }
+    return need;
+}
+
+// ---- the reads file as raw text chunks, from the reader thread to the device thread(s)
+// The reads file is streamed as TEXT: a host thread fills chunk buffers with the file's (inflated) bytes while
+// the main thread parses the graph and builds the index; every chunk then goes to phi_add_reads_text, which finds the records on
+// the device -- chunk i + 1 crosses the link while chunk i is sketched, and no byte of a regular file is looked at by a host core.
+// Host memory stays bounded: 2 + GPUs buffers.
 struct Chunk { char *text = nullptr; int64_t n = 0; int32_t parked = -1; };      // parked >= 0: the bytes wait in device memory (phi_text_park_*), no host buffer
-struct ChunkQueue {
-    std::deque<Chunk> buf;                                    // (a deque: entries for parked pieces are added while others are in use)
-    std::mutex mu;
-    std::condition_variable cv;
+struct ReadsFeed {
+    // set before the reader thread first starts
+    const Knobs *kn = nullptr;
+    int device = 0, n_buf = 0;                                // the GPU of the park and of the device inflater (one-GPU runs); 2 + GPUs
+    int64_t chunk_bytes = 0;                                  //  buffers of chunk_bytes: one in flight per GPU, two with the reader
+    bool inflate_on = false;                                  // single-stream gzip reads: inflated on the device
+    // under mu
+    std::mutex mu; std::condition_variable cv;
+    std::deque<Chunk> buf;                                    // (a deque: entries for parked pieces are added -- by the reader thread only -- while others are in use)
     std::deque<int> q_free, q_full;                           // buffer indices; a full entry with n == 0 ends the stream
     bool stop = false;
+    // atomics (cv is notified when they change)
+    std::atomic<bool> gfa_parsed{false}, index_built{false};  // parking may begin / it ends
+    std::atomic<bool> park_pinned{false};                     // the reader thread pinned the chunk buffers (the feed threads then do not)
+    std::atomic<bool> pinned{true};                           // no buffer failed to register
+    // the reader thread's; the others read them once it is joined -- but park, which a taker of a parked piece reads after the
+    // queue's lock handed the piece over
+    phi_text_park *park = nullptr;
+    bool park_on = false;                                     // reads text parked in device memory until the index is built
+    int64_t parked_bytes = 0;
+    phi_inflate_info inflated{};                              // the device inflater's totals, over all read sets
+    int fly_slot = -1, fly_idx = -1;                          // the buffer whose copy to the park is on its way, and its piece
+    char err[512] = "";                                       // the reader's error (and the host reader's: host_reader)
+    // the feed threads' (one GPU's turn at a time: under turn_mu; of one read set)
+    std::mutex turn_mu;
+    std::vector<char> carry;                                  // several GPUs: the bytes the last turn left unfinished
+    bool stream_done = false;
+    int64_t stream_fed = 0;                                   // bytes of the stream taken from the queue so far
+    int64_t host_bases = 0;                                   // bases through the host reader
+    std::atomic<int> n_chunks{0};
+    std::once_flag pin_once;                                  // (over all read sets)
+    bool registered = false;                                  // under pin_once
+    std::future<int> reader;                                  // (last: joined before the rest goes)
+
+    bool alloc(const Knobs *knobs, int dev, int64_t bytes, int n, bool park_text, bool inflate)
+    {
+        kn = knobs; device = dev; chunk_bytes = bytes; n_buf = n; park_on = park_text; inflate_on = inflate;
+        buf.resize((size_t)n_buf);
+        for (auto &b : buf) if (!(b.text = (char *)malloc((size_t)chunk_bytes))) return false;
+        return true;
+    }
+    void start(const std::string &rf)                         // a read set: every buffer free, nothing queued, the reader thread on it
+    {
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            q_free.clear(); q_full.clear(); stop = false;
+            for (int i = 0; i < n_buf; i++) { buf[(size_t)i].n = 0; q_free.push_back(i); }
+        }
+        err[0] = 0;
+        carry.clear(); stream_done = false; stream_fed = host_bases = 0; n_chunks = 0;
+        reader = std::async(std::launch::async, [this, rf]() { return read_all(rf); });
+    }
+    void stop_reader() { { std::lock_guard<std::mutex> lk(mu); stop = true; } cv.notify_all(); if (reader.valid()) reader.wait(); }
+    void mark(std::atomic<bool> &stage) { stage = true; cv.notify_all(); }
     int take_full()                                           // blocks; the end marker stays in the queue for the other takers
     {
         std::unique_lock<std::mutex> lk(mu);
@@ -156,709 +273,591 @@ struct ChunkQueue {
         return s;
     }
     Chunk *at(int s) { std::lock_guard<std::mutex> lk(mu); return &buf[(size_t)s]; }      // (entries never move; the deque's index may, while one is added)
-    void give_free(int s)
+    void give_free(int s) { { std::lock_guard<std::mutex> lk(mu); if (buf[(size_t)s].text) q_free.push_back(s); } cv.notify_all(); }
+    void give_full(int s) { { std::lock_guard<std::mutex> lk(mu); q_full.push_back(s); } cv.notify_all(); }
+    // (the reader thread: the only one that adds entries) a parked piece to the queue / the copy on its way has landed: its buffer is free
+    void queue_parked(int64_t n, int32_t idx) { { std::lock_guard<std::mutex> lk(mu); buf.push_back(Chunk{nullptr, n, idx}); q_full.push_back((int)buf.size() - 1); } cv.notify_all(); }
+    void land_in_flight() { if (fly_slot >= 0) { (void)phi_text_park_wait(park, fly_idx); give_free(fly_slot); fly_slot = -1; } }
+    // a file of more than one chunk: the buffers are pinned, so that the device copy of every further chunk is a direct DMA
+    // (pinning takes milliseconds: not worth it for a single chunk)
+    void pin_buffers(phi_ctx *cx)
     {
-        { std::lock_guard<std::mutex> lk(mu); if (buf[(size_t)s].text) q_free.push_back(s); }
-        cv.notify_all();
+        std::call_once(pin_once, [&]() {
+            if (park_pinned.load()) return;                   // (the reader thread pinned them when it began to park chunks)
+            registered = true;
+            std::lock_guard<std::mutex> lk(mu);               // (the reader thread may be adding an entry for a parked chunk)
+            for (auto &b : buf) if (b.text && phi_host_register(cx, b.text, (size_t)chunk_bytes) != PHI_OK) pinned = false;
+        });
     }
-};
-
-// the rest of the stream for the host reader: blocks straight from the queue (phi_reads_stream_open_blocks)
-struct QueueBlocks { ChunkQueue *q; int held = -1; phi_text_park *const *park = nullptr; std::vector<char> fetched; };      // park: where the park's handle will stand once the reader thread has made it
-static int64_t next_block_from_queue(void *user, const char **block)
-{
-    QueueBlocks *qb = (QueueBlocks *)user;
-    if (qb->held >= 0) { qb->q->give_free(qb->held); qb->held = -1; }
-    const int s = qb->q->take_full();
-    const Chunk &c = *qb->q->at(s);
-    if (c.n <= 0) return c.n;                                 // 0: the end; negative: the reader thread failed
-    if (c.parked >= 0) {
-        // a piece that went to device memory before the graph was there: its bytes come back for the host reader
-        qb->fetched.resize((size_t)c.n);
-        if (!qb->park || phi_text_park_fetch(*qb->park, c.parked, qb->fetched.data(), c.n) != PHI_OK) return -1;
-        (void)phi_text_park_release(*qb->park, c.parked);
-        *block = qb->fetched.data();
-        return c.n;
-    }
-    qb->held = s;
-    *block = c.text;
-    return c.n;
-}
-
-static int run(const Options &o)
-{
-    const int k = o.k, w = o.w, recombination = o.recombination, is_qclp = o.is_qclp, is_mixed = o.is_mixed, debug = o.debug;
-    const std::string &gfa_file = o.gfa_file;
-    const int n_jobs = (int)o.reads_files.size();
-    std::string reads_file = o.reads_files[0], hap_file = o.hap_files[0];      // the job at hand
-    char err[512] = "";
-
-    // The device context (HIP initialisation) and the reads file are prepared by two host threads
-    // while this one parses the graph: the three are independent.
-    std::vector<int> devices = o.devices;
-    if (devices.empty()) devices.push_back(o.device);
-    for (size_t i = 0; i < devices.size(); i++)
-        for (size_t j = 0; j < i; j++)
-            if (devices[i] == devices[j] && !getenv("PHI_ALLOW_SAME_DEVICE")) { fprintf(stderr, "[E::main] --devices names GPU %d twice\n", devices[i]); return 1; }   // (the tests run two contexts on one GPU)
-    // a read set is sharded only over as many GPUs as it can keep busy: every further GPU costs an exchange (~tens of
-    // microseconds) and an index build, and one GPU scores 50 Mbases in a fifth of a millisecond
-    if (devices.size() > 1) {
-        struct stat st;
-        long long bytes = (stat(reads_file.c_str(), &st) == 0 && S_ISREG(st.st_mode)) ? (long long)st.st_size : -1;
-        if (bytes >= 0) {
-            const size_t want = (size_t)std::max<long long>(1, (bytes + o.shard_min_bases - 1) / std::max<long long>(1, o.shard_min_bases));
-            if (want < devices.size()) {
-                fprintf(stderr, "[M::main] reads file of %lld bytes: using %zu of the %zu GPUs given (--shard-min-bases %lld per GPU)\n", bytes, want, devices.size(), o.shard_min_bases);
-                devices.resize(want);
-            }
-        }
-    }
-    const int n_dev = (int)devices.size();
-    std::vector<phi_ctx *> ctxs((size_t)n_dev, nullptr);
-    const bool timing = g_marks.on;
-    std::shared_future<int> f_ctx = std::async(std::launch::async, [&]() {
-        Stage st("device context(s) [thread]");
-        // one host thread per GPU (each context initialises its own device)
-        std::vector<std::future<int>> fs;
-        for (int i = 0; i < n_dev; i++)
-            fs.push_back(std::async(std::launch::async, [&, i]() { return phi_ctx_create(devices[(size_t)i], &ctxs[(size_t)i]); }));
-        int r = 0;
-        for (auto &f : fs) { const int ri = f.get(); if (ri && !r) r = ri; }
-        return r;
-    }).share();
-
-    // The reads file is streamed as TEXT: a host thread fills chunk buffers with the file's (inflated)
-    // bytes while this thread parses the graph and builds the index; every chunk then goes to phi_add_reads_text, which
-    // finds the records on the device -- chunk i + 1 crosses the link while chunk i is sketched, and no byte of a
-    // regular file is looked at by a host core.  Host memory stays bounded: 2 + GPUs buffers.
-    int64_t chunk_bytes = getenv("PHI_READ_CHUNK") ? std::max<int64_t>(256, atoll(getenv("PHI_READ_CHUNK"))) : ((int64_t)64 << 20);
-    if (!getenv("PHI_READ_CHUNK")) {
-        // small plain files: one chunk of the file's size (of the largest file, when there are several jobs)
-        int64_t need = 0;
-        for (const std::string &rf : o.reads_files) {
-            struct stat st;
-            int64_t want = chunk_bytes;
-            if (stat(rf.c_str(), &st) == 0 && S_ISREG(st.st_mode) && st.st_size > 0) {
-                FILE *fp = fopen(rf.c_str(), "rb");
-                unsigned char m2[2] = {0, 0};
-                const bool gz = fp && fread(m2, 1, 2, fp) == 2 && m2[0] == 0x1f && m2[1] == 0x8b;
-                if (fp) fclose(fp);
-                if (!gz) want = std::min<int64_t>(chunk_bytes, ((int64_t)st.st_size + 4095) & ~(int64_t)4095);
-            }
-            need = std::max(need, want);
-        }
-        chunk_bytes = need;
-    }
-    ChunkQueue Q;
-    const int N_CHUNK_BUF = 2 + n_dev;                        // one in flight per GPU, two with the reader
-    Q.buf.resize((size_t)N_CHUNK_BUF);
-    for (int i = 0; i < N_CHUNK_BUF; i++) {
-        Q.buf[(size_t)i].text = (char *)malloc((size_t)chunk_bytes);
-        if (!Q.buf[(size_t)i].text) { fprintf(stderr, "[E::%s] out of memory\n", __func__); return 1; }
-        Q.q_free.push_back(i);
-    }
-    char rerr[512] = "";
-    std::future<int> f_reads;
-    // reads text parked in device memory until the index is built (the reader thread's side of it is in start_reads below)
-    phi_text_park *park = nullptr;
-    std::atomic<bool> graph_ready{false}, park_go{false};      // the GFA is parsed (parking may begin) / the index is built (it ends)
-    bool park_on = false;                                     // (the reader thread's)
-    std::atomic<bool> park_pinned{false};                     // the reader thread pinned the chunk buffers (main then does not)
-    int64_t parked_bytes = 0;
-    const int64_t park_limit = getenv("PHI_TEXT_PARK_MAX") ? atoll(getenv("PHI_TEXT_PARK_MAX")) : ((int64_t)96 << 30);
-    if (devices.size() == 1 && !(getenv("PHI_TEXT_PARK") && atoi(getenv("PHI_TEXT_PARK")) == 0)) {
-        struct stat st;
-        const int64_t least = getenv("PHI_TEXT_PARK_MIN") ? atoll(getenv("PHI_TEXT_PARK_MIN")) : ((int64_t)256 << 20);
-        park_on = stat(reads_file.c_str(), &st) == 0 && S_ISREG(st.st_mode) && (int64_t)st.st_size >= least;
+    void teardown(phi_ctx *cx)                                // (the reader thread stopped)
+    {
+        if (park) phi_text_park_destroy(park);                // (unpins the chunk buffers it pinned)
+        for (auto &cb : buf) { if (registered && cb.text) (void)phi_host_unregister(cx, cb.text); free(cb.text); }
     }
     // Single-stream gzip reads (not BGZF) of a one-GPU run, from PHI_INFLATE_MIN compressed bytes on: inflated on the device
     // (phi_text_park_gzip_*) instead of one host thread, the text parked in pieces of chunk_bytes that the
     // reads stage takes as it takes any parked chunk.  PHI_INFLATE=0 or PHI_TEXT_PARK=0 keeps the host inflater; a stream the
     // device finds corrupt goes to the host inflater too, which reports it as it always has.
-    const int64_t inflate_min = getenv("PHI_INFLATE_MIN") ? atoll(getenv("PHI_INFLATE_MIN")) : ((int64_t)16 << 20);
-    const bool inflate_on = devices.size() == 1 && !(getenv("PHI_INFLATE") && atoi(getenv("PHI_INFLATE")) == 0) &&
-                            !(getenv("PHI_TEXT_PARK") && atoi(getenv("PHI_TEXT_PARK")) == 0);
-    int64_t inflated_bytes = 0, inflated_in = 0, inflated_chunks = 0, inflated_confirmed = 0, inflated_again = 0;
-    auto device_inflate = [&](const std::string &rf) -> bool {
+    bool inflate_on_device(const std::string &rf)
+    {
         if (!inflate_on) return false;
-        struct stat st;
-        if (stat(rf.c_str(), &st) != 0 || !S_ISREG(st.st_mode) || (int64_t)st.st_size < std::max<int64_t>(inflate_min, 18)) return false;
-        FILE *fp = fopen(rf.c_str(), "rb");
-        if (!fp) return false;
-        unsigned char u[14];
-        if (fread(u, 1, sizeof u, fp) != sizeof u || u[0] != 0x1f || u[1] != 0x8b || ((u[3] & 4) && u[12] == 'B' && u[13] == 'C')) {
-            fclose(fp);                                       // not gzip, or BGZF (the host pool): today's path, nothing read
-            return false;
-        }
-        std::vector<char> gz((size_t)st.st_size);
-        memcpy(gz.data(), u, sizeof u);
-        const size_t got = sizeof u + fread(gz.data() + sizeof u, 1, gz.size() - sizeof u, fp);
-        fclose(fp);
-        if (got != gz.size()) return false;
-        {
-            // the device is free once the GFA is parsed (as for parking)
-            std::unique_lock<std::mutex> lk(Q.mu);
-            Q.cv.wait(lk, [&] { return park_go.load() || graph_ready.load() || Q.stop; });
-            if (Q.stop) return false;
-        }
-        if (!park && phi_text_park_create(devices[0], &park) != PHI_OK) return false;
+        const FileProbe p = probe_file(rf);
+        std::vector<char> gz;
+        if (!single_gzip(p, kn->inflate_min) || !read_file(rf, p.size, gz)) return false;      // (not gzip, or BGZF: nothing read)
+        std::unique_lock<std::mutex> lk(mu);                  // the device is free once the GFA is parsed (as for parking)
+        cv.wait(lk, [&] { return gfa_parsed.load() || index_built.load() || stop; });
+        if (stop) return false;
+        lk.unlock();
+        if (!park && phi_text_park_create(device, &park) != PHI_OK) return false;
         int32_t first = -1, count = 0;
         phi_inflate_info info;
         if (phi_text_park_gzip_begin(park, chunk_bytes) != PHI_OK || phi_text_park_gzip_add(park, gz.data(), (int64_t)gz.size()) != PHI_OK ||
             phi_text_park_gzip_end(park, &first, &count, &info) != PHI_OK)
             return false;
-        {
-            std::lock_guard<std::mutex> lk(Q.mu);
-            for (int32_t i = 0; i < count; i++) {
-                Q.buf.push_back(Chunk{nullptr, phi_text_park_bytes(park, first + i), first + i});
-                Q.q_full.push_back((int)Q.buf.size() - 1);
-            }
-        }
-        Q.cv.notify_all();
-        inflated_bytes += info.out_bytes; inflated_in += info.in_bytes; inflated_chunks += info.chunks;
-        inflated_confirmed += info.confirmed; inflated_again += info.redecoded;
+        for (int32_t i = 0; i < count; i++) queue_parked(phi_text_park_bytes(park, first + i), first + i);
+        inflated.out_bytes += info.out_bytes; inflated.in_bytes += info.in_bytes; inflated.chunks += info.chunks;
+        inflated.confirmed += info.confirmed; inflated.redecoded += info.redecoded;
         return true;
-    };
-    auto start_reads = [&]() {
-      f_reads = std::async(std::launch::async, [&, rf = reads_file]() {
+    }
+    // the chunk in `slot` to device memory (its buffer is the copy engine's until the copy has landed: the next chunk is read
+    // into another one meanwhile, and the buffer of the copy before -- done by now -- goes back to the free ones)
+    bool park_chunk(int slot, int64_t n)
+    {
+        bool ok = true;
+        if (!park) {
+            ok = phi_text_park_create(device, &park) == PHI_OK;
+            for (auto &b : buf) if (ok && b.text && phi_text_park_pin(park, b.text, (size_t)chunk_bytes) != PHI_OK) ok = false;
+            if (ok) park_pinned = true;
+        }
+        int32_t idx = -1;
+        if (!ok || phi_text_park_add_async(park, buf[(size_t)slot].text, n, &idx) != PHI_OK) return false;
+        parked_bytes += n;
+        queue_parked(n, idx);
+        land_in_flight();
+        fly_slot = slot; fly_idx = idx;
+        return true;
+    }
+    // the reader thread: the file's text into the queue, ended by an entry of n == 0 (n < 0: the reader failed)
+    int read_all(const std::string &rf)
+    {
         Stage st("reads file -> text chunks [thread]");
         phi_text_stream *ts = nullptr;
-        const bool on_device = device_inflate(rf);             // (then only the end of the stream is left to queue)
-        int r = on_device ? PHI_HOST_OK : phi_text_stream_open(rf.c_str(), &ts, rerr, sizeof rerr);
-        int slot = -1, fly_slot = -1;
-        int32_t fly_idx = -1;
+        const bool on_device = inflate_on_device(rf);         // (then only the end of the stream is left to queue)
+        int r = on_device ? PHI_HOST_OK : phi_text_stream_open(rf.c_str(), &ts, err, sizeof err);
+        int slot = -1;
         for (;;) {
             if (slot < 0) {
-                std::unique_lock<std::mutex> lk(Q.mu);
-                Q.cv.wait(lk, [&] { return !Q.q_free.empty() || Q.stop; });
-                if (Q.stop) break;
-                slot = Q.q_free.front(); Q.q_free.pop_front();
+                std::unique_lock<std::mutex> lk(mu);
+                cv.wait(lk, [&] { return !q_free.empty() || stop; });
+                if (stop) break;
+                slot = q_free.front(); q_free.pop_front();
             }
-            int64_t n = 0;
-            if (r == PHI_HOST_OK && on_device) {
-                n = 0;
-            } else if (r == PHI_HOST_OK) {
-                n = phi_text_stream_read(ts, Q.buf[(size_t)slot].text, chunk_bytes, rerr, sizeof rerr);
-                if (n < 0) { r = (int)n; }
-            } else n = r;
+            int64_t n = r != PHI_HOST_OK ? r : on_device ? 0 : phi_text_stream_read(ts, buf[(size_t)slot].text, chunk_bytes, err, sizeof err);
+            if (n < 0) r = (int)n;
             // While the graph is still being read and indexed the link and the HBM are idle: the chunk goes to device memory
             // now (phi_text_park_*), the host buffer is free for the next one at once, and when the index is there the reads
             // stage finds the text where the records are found anyway.  (One GPU; large files; until the index is built.)
-            if (n > 0 && park_on && !graph_ready.load() && !park_go.load()) {
+            if (n > 0 && park_on && !index_built.load() && !gfa_parsed.load()) {
                 // the GFA is still being read (all host threads, all of the memory bandwidth): chunks stay in their host buffers
                 // as long as two more are free (parking needs two: one is read into while the other's copy is on its way); with
                 // fewer, wait with this chunk in hand for the GFA or for a taker
-                std::unique_lock<std::mutex> lk(Q.mu);
-                Q.cv.wait(lk, [&] { return park_go.load() || graph_ready.load() || Q.q_free.size() >= 2 || Q.stop; });
+                std::unique_lock<std::mutex> lk(mu);
+                cv.wait(lk, [&] { return gfa_parsed.load() || index_built.load() || q_free.size() >= 2 || stop; });
             }
-            if (n > 0 && park_on && park_go.load() && !graph_ready.load() && parked_bytes + n <= park_limit) {
-                bool ok = true;
-                if (!park) {
-                    ok = phi_text_park_create(devices[0], &park) == PHI_OK;
-                    for (auto &b : Q.buf) if (ok && b.text && phi_text_park_pin(park, b.text, (size_t)chunk_bytes) != PHI_OK) ok = false;
-                    if (ok) park_pinned = true;
-                }
-                int32_t idx = -1;
-                if (ok && phi_text_park_add_async(park, Q.buf[(size_t)slot].text, n, &idx) == PHI_OK) {
-                    parked_bytes += n;
-                    {
-                        std::lock_guard<std::mutex> lk(Q.mu);
-                        Q.buf.push_back(Chunk{nullptr, n, idx});
-                        Q.q_full.push_back((int)Q.buf.size() - 1);
-                    }
-                    Q.cv.notify_all();
-                    // this buffer is the copy engine's until its copy has landed: the next chunk is read into another one
-                    // meanwhile, and the buffer of the copy before -- done by now -- goes back to the free ones
-                    if (fly_slot >= 0) { (void)phi_text_park_wait(park, fly_idx); Q.give_free(fly_slot); }
-                    fly_slot = slot; fly_idx = idx;
-                    slot = -1;
-                    continue;
-                }
+            if (n > 0 && park_on && gfa_parsed.load() && !index_built.load() && parked_bytes + n <= kn->text_park_max) {
+                if (park_chunk(slot, n)) { slot = -1; continue; }
                 park_on = false;                              // no room or no device yet: the usual way from here on
             }
-            if (fly_slot >= 0) { (void)phi_text_park_wait(park, fly_idx); Q.give_free(fly_slot); fly_slot = -1; }
-            Q.buf[(size_t)slot].n = n;                        // 0 ends the stream, a negative value ends it as failed
-            {
-                std::lock_guard<std::mutex> lk(Q.mu);
-                Q.q_full.push_back(slot);
-            }
-            Q.cv.notify_all();
+            land_in_flight();
+            buf[(size_t)slot].n = n;                          // 0 ends the stream, a negative value ends it as failed
+            give_full(slot);
             slot = -1;
             if (n <= 0) break;
         }
-        if (fly_slot >= 0) { (void)phi_text_park_wait(park, fly_idx); Q.give_free(fly_slot); }
+        land_in_flight();
         if (ts) phi_text_stream_close(ts);
         return r;
-      });
-    };
-    start_reads();
-    auto stop_reads = [&]() {
-        { std::lock_guard<std::mutex> lk(Q.mu); Q.stop = true; }
-        Q.cv.notify_all();
-        if (f_reads.valid()) f_reads.wait();
-    };
+    }
+    // the rest of the stream for the host reader: blocks straight from the queue (phi_reads_stream_open_blocks)
+    struct QueueBlocks { ReadsFeed *f; int held = -1; std::vector<char> fetched; };
+    static int64_t next_block_from_queue(void *user, const char **block)
+    {
+        QueueBlocks *qb = (QueueBlocks *)user;
+        if (qb->held >= 0) { qb->f->give_free(qb->held); qb->held = -1; }
+        const int s = qb->f->take_full();
+        const Chunk &c = *qb->f->at(s);
+        if (c.n <= 0) return c.n;                             // 0: the end; negative: the reader thread failed
+        if (c.parked < 0) { qb->held = s; *block = c.text; return c.n; }
+        // a piece that went to device memory before the graph was there: its bytes come back for the host reader
+        qb->fetched.resize((size_t)c.n);
+        if (phi_text_park_fetch(qb->f->park, c.parked, qb->fetched.data(), c.n) != PHI_OK) return -1;
+        (void)phi_text_park_release(qb->f->park, c.parked);
+        *block = qb->fetched.data();
+        return c.n;
+    }
+    // the host reader over `prefix` + (rest_of_queue) the rest of the queue -> phi_add_reads on cx (under turn_mu)
+    int host_reader(phi_ctx *cx, const char *prefix, int64_t n_prefix, bool rest_of_queue, int64_t stream_offset)
+    {
+        Stage st("host reader (kseq state machine)");
+        QueueBlocks qb{this, -1, {}};
+        phi_reads_stream *rs = nullptr;
+        if (phi_reads_stream_open_blocks(prefix, n_prefix, rest_of_queue ? next_block_from_queue : nullptr, &qb, stream_offset, &rs, err, sizeof err) != PHI_HOST_OK) return PHI_ERR_INVALID;
+        const int64_t cap_b = std::max<int64_t>((int64_t)1 << 20, std::min<int64_t>(chunk_bytes, (int64_t)64 << 20)), cap_r = cap_b / 32 + 1024;
+        std::vector<char> hb((size_t)cap_b);
+        std::vector<int64_t> ho((size_t)cap_r + 1);
+        int r = PHI_OK;
+        for (;;) {
+            const int64_t n = phi_reads_stream_next(rs, hb.data(), cap_b, ho.data(), cap_r, err, sizeof err);
+            if (n < 0) { r = PHI_ERR_INVALID; break; }
+            if (n == 0) break;
+            host_bases += ho[(size_t)n];
+            if ((r = phi_add_reads(cx, hb.data(), ho.data(), n))) break;
+        }
+        phi_reads_stream_close(rs);
+        if (qb.held >= 0) give_free(qb.held);
+        if (r == PHI_ERR_INVALID && err[0]) fprintf(stderr, "[E::main] %s\n", err);
+        return r;
+    }
+};
 
-    // ---- graph (main.cpp:101-115)
-    // One GPU: the walks stay TEXT in the reader (include/phi_host.h phi_gfa_read_deferred) and go to HBM as soon as the reader
-    // knows where they are -- while it still enters the segment names --, and the device resolves them (phi_walk_text_*): at
-    // chromosome scale the walks are 96% of the file.  Text the device path does not take (reverse steps, names of another form:
-    // walk_text.hip) is resolved by the host after all, with the reference's rules.  Small files (PHI_WALK_TEXT_MIN bytes of
-    // walk text, default 1 GB) and multi-GPU runs (every GPU needs the walks) stay with the host.
+// The walks of g, whose text is on the device (phi_walk_text_upload, phi_gfa_gzip_split), resolved there: PHI_OK (their offsets
+// are g's unless *irregular), phi_walk_text_resolve's error, or WALK_NAMES when the names are not <prefix><number>.
+static const int WALK_NAMES = 1;                              // (no phi_status is positive)
+static int resolve_walks_on_device(phi_ctx *ctx, phi_graph *g, uint32_t *irregular)
+{
+    const char *prefix = nullptr; int32_t prefix_n = 0; const int32_t *num2id = nullptr; int64_t n_num = 0;
+    *irregular = 0;
+    if (phi_graph_name_index(g, &prefix, &prefix_n, &num2id, &n_num) != PHI_HOST_OK) return WALK_NAMES;
+    std::vector<int64_t> woff((size_t)phi_graph_n_walks(g) + 1, 0);
+    const int r = phi_walk_text_resolve(ctx, prefix, prefix_n, num2id, n_num, phi_graph_n_vtx(g), woff.data(), irregular);
+    if (!r && !*irregular) phi_graph_set_walk_off(g, woff.data());
+    return r;
+}
+
+// ---- one run: the contexts, the reads feed and the graph, shared by every job
+struct Driver {
+    const Options &o;
+    const Knobs kn;
+    const bool timing = g_marks.on;
+    std::vector<int> devices;                                 // the GPUs used (n_dev), one context each
+    int n_dev = 0;
+    std::vector<phi_ctx *> ctxs;
+    std::shared_future<int> f_ctx;                            // made by threads of their own (joined before ctxs goes)
+    phi_ctx *ctx = nullptr;                                   // the context that solves and reports
+    ReadsFeed feed;
     phi_graph *g = nullptr;
-    struct WalkText { std::shared_future<int> *ctx_ready; std::vector<phi_ctx *> *ctxs; int64_t min_bytes; int64_t bytes = 0; int rc = 0; bool sent = false; } wt{&f_ctx, &ctxs, 0};
-    // (1 GB: the host threads resolve 70 MB of walk text -- a 49-walk MHC graph -- in 10 ms, hidden behind the 0.1 s the HIP runtime
-    //  takes to start, while the device path has to wait for that start before its first byte moves: measured at C2, 32 MB as
-    //  the threshold cost every process 40 ms)
-    wt.min_bytes = getenv("PHI_WALK_TEXT_MIN") ? atoll(getenv("PHI_WALK_TEXT_MIN")) : ((int64_t)1 << 30);
-    const bool defer_walks = n_dev == 1 && !(getenv("PHI_WALKS") && !strcmp(getenv("PHI_WALKS"), "host"));
-    auto gfa_failed = [&]() {
-        if (err[0] == 'E') fprintf(stderr, "%s\n", err);            // walk error text of ILP_index.cpp:105
-        else fprintf(stderr, "[E::%s] failed to load the GFA file\n", "main");
-        if (err[0] && err[0] != 'E') fprintf(stderr, "[E::%s] %s\n", "main", err);
-        f_ctx.wait(); stop_reads();
-        return 1;
-    };
-    // A single-stream gzip GFA (not BGZF) of a one-GPU run, from PHI_GFA_INFLATE_MIN compressed bytes on (default 256 MB):
-    // inflated and split on the device (phi_gfa_gzip_split, DESIGN.md 4.9).  The walk fields stay in HBM whatever
-    // PHI_WALK_TEXT_MIN says, and only the rest of the text -- S-lines, L-lines, W-line heads -- comes to the host reader.
-    // Whatever that route does not finish (a corrupt stream, a refused split, walks counted differently, names not
-    // <prefix><number>, a W-line among the S-lines, irregular walk text) is read again from the file, from scratch, as below:
-    // messages, exit status and output are those of PHI_GFA_INFLATE=0.
-    bool gfa_on_device = false;
-    {
-        const int64_t gfa_min = getenv("PHI_GFA_INFLATE_MIN") ? atoll(getenv("PHI_GFA_INFLATE_MIN")) : ((int64_t)256 << 20);
-        const bool gfa_inflate_on = n_dev == 1 && defer_walks && !(getenv("PHI_GFA_INFLATE") && atoi(getenv("PHI_GFA_INFLATE")) == 0);
-        std::vector<char> gz;
-        struct stat st;
-        if (gfa_inflate_on && stat(gfa_file.c_str(), &st) == 0 && S_ISREG(st.st_mode) && (int64_t)st.st_size >= std::max<int64_t>(gfa_min, 18)) {
-            if (FILE *fp = fopen(gfa_file.c_str(), "rb")) {
-                unsigned char u[14];
-                if (fread(u, 1, sizeof u, fp) == sizeof u && u[0] == 0x1f && u[1] == 0x8b && !((u[3] & 4) && u[12] == 'B' && u[13] == 'C')) {
-                    Stage st2("GFA gzip read (device context starting)");
-                    gz.resize((size_t)st.st_size);
-                    memcpy(gz.data(), u, sizeof u);
-                    if (sizeof u + fread(gz.data() + sizeof u, 1, gz.size() - sizeof u, fp) != gz.size()) std::vector<char>().swap(gz);
-                }
-                fclose(fp);
-            }
-        }
-        if (!gz.empty()) {
-            Stage st2("GFA on the device: inflate, split, parse, walks");
-            const char *why = nullptr;
-            char *host_text = nullptr;
-            int64_t host_n = 0;
-            phi_gfa_gzip_info gi;
-            memset(&gi, 0, sizeof gi);
-            if (f_ctx.get()) why = "no device context";
-            int r = why ? 0 : phi_gfa_gzip_split(ctxs[0], gz.data(), (int64_t)gz.size(), 0, &host_text, &host_n, &gi);
-            std::vector<char>().swap(gz);
-            if (!why && r) why = r == PHI_ERR_INVALID ? "gzip stream corrupt" : r == PHI_ERR_UNSUPPORTED ? "split refused" : "device error";
-            if (!why && phi_gfa_read_deferred_text(host_text, host_n, gfa_file.c_str(), &g, err, sizeof err) != PHI_HOST_OK) why = "host reader failed on the split text";
-            if (!why && phi_graph_n_walks(g) != gi.n_walks) why = "walk count differs from the host reader's";
-            const char *prefix = nullptr; int32_t prefix_n = 0; const int32_t *num2id = nullptr; int64_t n_num = 0;
-            if (!why && phi_graph_name_index(g, &prefix, &prefix_n, &num2id, &n_num) != PHI_HOST_OK) why = "names not <prefix><number>, or a W-line among the S-lines";
-            if (!why) {
-                std::vector<int64_t> woff((size_t)phi_graph_n_walks(g) + 1, 0);
-                uint32_t irregular = 0;
-                if (phi_walk_text_resolve(ctxs[0], prefix, prefix_n, num2id, n_num, phi_graph_n_vtx(g), woff.data(), &irregular) != PHI_OK) why = "walks on the device failed";
-                else if (irregular) why = "irregular walk text";
-                else { phi_graph_set_walk_off(g, woff.data()); gfa_on_device = true; }
-            }
-            if (!gfa_on_device) {
-                if (g) { phi_graph_free(g); g = nullptr; }
-                if (!f_ctx.get()) (void)phi_walk_text_upload(ctxs[0], nullptr, 0);          // (lets the text on the device go)
-                err[0] = 0;
-            }
-            phi_gfa_gzip_free(host_text);                            // (the reader borrowed it until the walks were resolved)
-            if (timing) {
-                if (gfa_on_device)
-                    fprintf(stderr, "[phi timing] main: GFA: %lld bytes inflated on the device from %lld gzip bytes (%lld chunks); %lld bytes to the host, %lld bytes of %d walks kept on the device\n",
-                            (long long)gi.text_bytes, (long long)gi.inflate.in_bytes, (long long)gi.inflate.chunks, (long long)gi.host_bytes, (long long)gi.walk_bytes, gi.n_walks);
-                else
-                    fprintf(stderr, "[phi timing] main: GFA: not on the device (%s): the host reader from the file\n", why);
-            }
-        }
-    }
-    if (!gfa_on_device) {
-        Stage st("GFA read + parse");
-        int r;
-        if (defer_walks)
-            r = phi_gfa_read_deferred(gfa_file.c_str(), &g, [](void *user, const phi_host_walk_text *walks, int32_t n) {
-                    WalkText &t = *static_cast<WalkText *>(user);
-                    for (int32_t i = 0; i < n; i++) t.bytes += walks[i].n;
-                    if (t.bytes < t.min_bytes) return;
-                    if (t.ctx_ready->get()) return;                              // (no device: main reports it)
-                    static_assert(sizeof(phi_host_walk_text) == sizeof(phi_walk_text), "the two libraries' walk text records");
-                    t.rc = phi_walk_text_upload((*t.ctxs)[0], reinterpret_cast<const phi_walk_text *>(walks), n);
-                    t.sent = t.rc == 0;
-                }, &wt, err, sizeof err);
-        else
-            r = phi_gfa_read(gfa_file.c_str(), &g, err, sizeof err);
-        if (r != PHI_HOST_OK) return gfa_failed();
-    }
-    park_go = true;                                           // (the reads text may go to device memory from here on: see start_reads)
-    Q.cv.notify_all();
-    if (defer_walks && !gfa_on_device) {
-        Stage st("walks");
-        bool on_device = false;
-        if (wt.rc) { fprintf(stderr, "[E::%s] walk text to the device: %s: %s\n", "main", phi_strerror(wt.rc), phi_last_error(ctxs[0])); stop_reads(); return 1; }
-        if (wt.sent) {
-            const char *prefix = nullptr; int32_t prefix_n = 0; const int32_t *num2id = nullptr; int64_t n_num = 0;
-            uint32_t irregular = 0;
-            if (phi_graph_name_index(g, &prefix, &prefix_n, &num2id, &n_num) == PHI_HOST_OK) {
-                std::vector<int64_t> woff((size_t)phi_graph_n_walks(g) + 1, 0);
-                const int r = phi_walk_text_resolve(ctxs[0], prefix, prefix_n, num2id, n_num, phi_graph_n_vtx(g), woff.data(), &irregular);
-                if (r) { fprintf(stderr, "[E::%s] walks on the device: %s: %s\n", "main", phi_strerror(r), phi_last_error(ctxs[0])); stop_reads(); return 1; }
-                if (!irregular) { phi_graph_set_walk_off(g, woff.data()); on_device = true; }
-            } else {
-                (void)phi_walk_text_upload(ctxs[0], nullptr, 0);                 // (lets the text on the device go)
-            }
-            if (timing) fprintf(stderr, "[phi] walks: %lld bytes of text %s\n", (long long)wt.bytes, on_device ? "resolved on the device" : irregular ? "irregular for the device: host" : "names not <prefix><number>: host");
-        }
-        if (!on_device && phi_graph_resolve_walks(g, err, sizeof err) != PHI_HOST_OK) return gfa_failed();
-    }
-    stamp("main");
-    fprintf(stderr, "Loaded graph from: %s\n", gfa_file.c_str());
+    char err[512] = "";
+    std::string reads_file, hap_file;                         // the job at hand, and the name in its FASTA
     char hap_name[4096];
-    if (phi_hap_name(gfa_file.c_str(), reads_file.c_str(), hap_name, sizeof hap_name) < 0) { fprintf(stderr, "[E::%s] output name too long\n", "main"); f_ctx.wait(); stop_reads(); return 1; }
+    std::atomic<bool> failed{false};                          // a GPU failed in the phase at hand (run_on_all)
+    bool use_peers = false;                                   // the exchange: peer-mapped memory or RCCL (comm_id)
+    void *peer_group = nullptr;
+    unsigned char comm_id[PHI_COMM_ID_BYTES];
+    struct { int64_t bytes = 0; int rc = 0; bool sent = false; } wt;      // the walk text the deferred GFA reader sent to the device
+    explicit Driver(const Options &opt) : o(opt), devices(opt.devices), reads_file(opt.reads_files[0]), hap_file(opt.hap_files[0]) {}
 
-    int rc;
+    // the one error exit: the message, the reader thread stopped, status 1
+    __attribute__((format(printf, 2, 3))) int fail(const char *fmt, ...)
     {
-        Stage st("wait for the device context");
-        rc = f_ctx.get();
+        va_list ap;
+        va_start(ap, fmt); vfprintf(stderr, fmt, ap); va_end(ap);
+        feed.stop_reader(); return 1;
     }
-    if (rc) { fprintf(stderr, "[E::%s] no usable MI355X (HIP) device %d: %s\n", "main", devices[0], phi_strerror(rc)); stop_reads(); return 1; }
-    phi_ctx *ctx = ctxs[0];                                   // the context that solves and reports
-    auto die_on = [&](phi_ctx *cx, const char *what, int code) {
-        fprintf(stderr, "[E::%s] %s: %s: %s\n", "main", what, phi_strerror(code), phi_last_error(cx));
-        stop_reads();
-        return 1;
-    };
-    auto die = [&](const char *what, int code) { return die_on(ctx, what, code); };
+    int fail_on(phi_ctx *cx, const char *what, int code) { return fail("[E::main] %s: %s: %s\n", what, phi_strerror(code), phi_last_error(cx)); }
+    int gfa_failed()
+    {
+        if (err[0] == 'E') return fail("%s\n", err);         // walk error text of ILP_index.cpp:105
+        if (!err[0]) return fail("[E::main] failed to load the GFA file\n");
+        return fail("[E::main] failed to load the GFA file\n[E::main] %s\n", err);
+    }
+    int name_job() { return phi_hap_name(o.gfa_file.c_str(), reads_file.c_str(), hap_name, sizeof hap_name) < 0 ? fail("[E::main] output name too long\n") : 0; }
+    void loaded() { stamp("main"); fprintf(stderr, "Loaded graph from: %s\n", o.gfa_file.c_str()); }
     // One phase of the job on every GPU, each on its own host thread.  All threads of a phase are joined before the next
     // begins, and a collective (RCCL) is a phase of its own that is entered only when the phase before returned 0 on every
     // GPU: a rank that failed can then never leave the others waiting inside ncclCommInitRank / ncclAllReduce.
-    std::atomic<bool> failed{false};
-    auto run_on_all = [&](const char *what, const std::function<int(int, phi_ctx *)> &fn) -> int {
-        if (n_dev == 1) { const int r = fn(0, ctx); if (r) failed = true; return r ? die(what, r) : 0; }
+    int run_on_all(const char *what, const std::function<int(int, phi_ctx *)> &fn)
+    {
+        if (n_dev == 1) { const int r = fn(0, ctx); if (r) failed = true; return r ? fail_on(ctx, what, r) : 0; }
         std::vector<std::future<int>> fs;
         for (int i = 0; i < n_dev; i++) fs.push_back(std::async(std::launch::async, [&, i]() { const int r = fn(i, ctxs[(size_t)i]); if (r) failed = true; return r; }));
         int bad = -1, brc = 0;
         for (int i = 0; i < n_dev; i++) { const int r = fs[(size_t)i].get(); if (r && bad < 0) { bad = i; brc = r; } }
         if (bad >= 0) {
             if (brc == PHI_ERR_WALK) fprintf(stderr, "Error: %s\n", phi_last_error(ctxs[(size_t)bad]));
-            return die_on(ctxs[(size_t)bad], what, brc);
+            return fail_on(ctxs[(size_t)bad], what, brc);
         }
         return 0;
-    };
-
-    const uint32_t flags = (is_qclp ? PHI_FLAG_QCLP : 0) | (is_mixed ? PHI_FLAG_MIXED : 0);
-    // the read shards of a multi-GPU run are merged by the library's own RCCL exchange (phi_comm_*)
-    unsigned char comm_id[PHI_COMM_ID_BYTES];
-
-    // ---- stage 1a: walks (ILP_index.cpp:556-611) on every GPU, while the reads are still being read
-    const int32_t n_walks = phi_graph_n_walks(g);
-    {
-        Stage st("phi_set_graph (index build)");
-        if (run_on_all("graph", [&](int, phi_ctx *cx) -> int {
-                int r = phi_set_params(cx, k, w, o.threshold, recombination, flags);
-                // the reference's model.optimize() has no limit (ILP_index.cpp:1412-1418): none here unless --dp-budget asks for one
-                if (!r) r = phi_set_solve_budget(cx, o.dp_budget >= 0 ? o.dp_budget : 0);
-                if (!r) r = phi_set_graph(cx, phi_graph_n_vtx(g), phi_graph_seq_concat(g), phi_graph_seq_off(g), phi_graph_adj_off(g),
-                                          phi_graph_adj(g), n_walks, phi_graph_walk_off(g), phi_graph_walk_vtx(g), phi_graph_topo_rank(g));
-                if (r == PHI_ERR_WALK && n_dev == 1) fprintf(stderr, "Error: %s\n", phi_last_error(cx));
-                return r;
-            })) return 1;
     }
-    graph_ready = true;                                       // (the reader thread stops parking chunks: they are taken as they come now)
-    Q.cv.notify_all();
+    // A single-stream gzip GFA (not BGZF) of a one-GPU run, from PHI_GFA_INFLATE_MIN compressed bytes on (default 256 MB):
+    // inflated and split on the device (phi_gfa_gzip_split, DESIGN.md 4.9).  The walk fields stay in HBM whatever
+    // PHI_WALK_TEXT_MIN says, and only the rest of the text -- S-lines, L-lines, W-line heads -- comes to the host reader.
+    // Whatever that route does not finish (a corrupt stream, a refused split, walks counted differently, names not
+    // <prefix><number>, a W-line among the S-lines, irregular walk text) is read again from the file, from scratch, by
+    // load_graph: messages, exit status and output are those of PHI_GFA_INFLATE=0.  True when g was made here.
+    bool gfa_on_device()
+    {
+        const FileProbe p = probe_file(o.gfa_file);
+        std::vector<char> gz;
+        if (!single_gzip(p, kn.gfa_inflate_min)) return false;
+        if (Stage st("GFA gzip read (device context starting)"); !read_file(o.gfa_file, p.size, gz)) return false;
+        Stage st("GFA on the device: inflate, split, parse, walks");
+        const char *why = f_ctx.get() ? "no device context" : nullptr;
+        char *host_text = nullptr; int64_t host_n = 0;
+        phi_gfa_gzip_info gi; memset(&gi, 0, sizeof gi);
+        int r = why ? 0 : phi_gfa_gzip_split(ctxs[0], gz.data(), (int64_t)gz.size(), 0, &host_text, &host_n, &gi);
+        std::vector<char>().swap(gz);
+        if (!why && r) why = r == PHI_ERR_INVALID ? "gzip stream corrupt" : r == PHI_ERR_UNSUPPORTED ? "split refused" : "device error";
+        if (!why && phi_gfa_read_deferred_text(host_text, host_n, o.gfa_file.c_str(), &g, err, sizeof err) != PHI_HOST_OK) why = "host reader failed on the split text";
+        if (!why && phi_graph_n_walks(g) != gi.n_walks) why = "walk count differs from the host reader's";
+        if (!why) {
+            uint32_t irregular = 0;
+            r = resolve_walks_on_device(ctxs[0], g, &irregular);
+            why = r == WALK_NAMES ? "names not <prefix><number>, or a W-line among the S-lines" : r ? "walks on the device failed" : irregular ? "irregular walk text" : nullptr;
+        }
+        if (why) {
+            if (g) { phi_graph_free(g); g = nullptr; }
+            if (!f_ctx.get()) (void)phi_walk_text_upload(ctxs[0], nullptr, 0);          // (lets the text on the device go)
+            err[0] = 0;
+        }
+        phi_gfa_gzip_free(host_text);                        // (the reader borrowed it until the walks were resolved)
+        if (timing && !why)
+            fprintf(stderr, "[phi timing] main: GFA: %lld bytes inflated on the device from %lld gzip bytes (%lld chunks); %lld bytes to the host, %lld bytes of %d walks kept on the device\n",
+                    (long long)gi.text_bytes, (long long)gi.inflate.in_bytes, (long long)gi.inflate.chunks, (long long)gi.host_bytes, (long long)gi.walk_bytes, gi.n_walks);
+        else if (timing)
+            fprintf(stderr, "[phi timing] main: GFA: not on the device (%s): the host reader from the file\n", why);
+        return !why;
+    }
+    static void upload_walk_text(void *user, const phi_host_walk_text *walks, int32_t n)      // (the GFA reader's callback: once there is enough text)
+    {
+        Driver &d = *static_cast<Driver *>(user);
+        for (int32_t i = 0; i < n; i++) d.wt.bytes += walks[i].n;
+        if (d.wt.bytes < d.kn.walk_text_min || d.f_ctx.get()) return;      // (no device: main reports it)
+        static_assert(sizeof(phi_host_walk_text) == sizeof(phi_walk_text), "the two libraries' walk text records");
+        d.wt.rc = phi_walk_text_upload(d.ctxs[0], reinterpret_cast<const phi_walk_text *>(walks), n);
+        d.wt.sent = d.wt.rc == 0;
+    }
+    // ---- graph (main.cpp:101-115)
+    // One GPU: the walks stay TEXT in the reader (include/phi_host.h phi_gfa_read_deferred) and go to HBM as soon as the reader
+    // knows where they are -- while it still enters the segment names --, and the device resolves them (phi_walk_text_*): at
+    // chromosome scale the walks are 96% of the file.  Text the device path does not take (reverse steps, names of another form:
+    // walk_text.hip) is resolved by the host after all, with the reference's rules.  Small files (PHI_WALK_TEXT_MIN bytes of
+    // walk text, default 1 GB) and multi-GPU runs (every GPU needs the walks) stay with the host.  (1 GB: the host threads resolve
+    // 70 MB of walk text -- a 49-walk MHC graph -- in 10 ms, hidden behind the 0.1 s the HIP runtime takes to start, while the device
+    // path has to wait for that start before its first byte moves: measured at C2, 32 MB as the threshold cost every process 40 ms)
+    int load_graph()
+    {
+        const bool defer_walks = n_dev == 1 && !kn.walks_host;
+        const bool on_device = defer_walks && kn.gfa_inflate && gfa_on_device();
+        if (!on_device) {
+            Stage st("GFA read + parse");
+            const int r = defer_walks ? phi_gfa_read_deferred(o.gfa_file.c_str(), &g, upload_walk_text, this, err, sizeof err)
+                                      : phi_gfa_read(o.gfa_file.c_str(), &g, err, sizeof err);
+            if (r != PHI_HOST_OK) return gfa_failed();
+        }
+        feed.mark(feed.gfa_parsed);                           // (the reads text may go to device memory from here on)
+        if (!defer_walks || on_device) return 0;
+        Stage st("walks");
+        bool walks_on_device = false;
+        if (wt.rc) return fail("[E::main] walk text to the device: %s: %s\n", phi_strerror(wt.rc), phi_last_error(ctxs[0]));
+        if (wt.sent) {
+            uint32_t irregular = 0;
+            const int r = resolve_walks_on_device(ctxs[0], g, &irregular);
+            if (r == WALK_NAMES) (void)phi_walk_text_upload(ctxs[0], nullptr, 0);      // (lets the text on the device go)
+            else if (r) return fail("[E::main] walks on the device: %s: %s\n", phi_strerror(r), phi_last_error(ctxs[0]));
+            walks_on_device = r == PHI_OK && !irregular;
+            if (timing) fprintf(stderr, "[phi] walks: %lld bytes of text %s\n", (long long)wt.bytes, walks_on_device ? "resolved on the device" : irregular ? "irregular for the device: host" : "names not <prefix><number>: host");
+        }
+        if (!walks_on_device && phi_graph_resolve_walks(g, err, sizeof err) != PHI_HOST_OK) return gfa_failed();
+        return 0;
+    }
+    // ---- stage 1a: walks (ILP_index.cpp:556-611) on every GPU, while the reads are still being read
+    int build_index()
+    {
+        const uint32_t flags = (o.is_qclp ? PHI_FLAG_QCLP : 0) | (o.is_mixed ? PHI_FLAG_MIXED : 0);
+        Stage st("phi_set_graph (index build)");
+        return run_on_all("graph", [&](int, phi_ctx *cx) -> int {
+            int r = phi_set_params(cx, o.k, o.w, o.threshold, o.recombination, flags);
+            // the reference's model.optimize() has no limit (ILP_index.cpp:1412-1418): none here unless --dp-budget asks for one
+            if (!r) r = phi_set_solve_budget(cx, o.dp_budget >= 0 ? o.dp_budget : 0);
+            if (!r) r = phi_set_graph(cx, phi_graph_n_vtx(g), phi_graph_seq_concat(g), phi_graph_seq_off(g), phi_graph_adj_off(g),
+                                      phi_graph_adj(g), phi_graph_n_walks(g), phi_graph_walk_off(g), phi_graph_walk_vtx(g), phi_graph_topo_rank(g));
+            if (r == PHI_ERR_WALK && n_dev == 1) fprintf(stderr, "Error: %s\n", phi_last_error(cx));
+            return r;
+        });
+    }
     // The exchange of a multi-GPU run: the library's RCCL all-reduce.  PHI_EXCHANGE=peers takes the peer-mapped OR-gather
     // instead (one kernel per GPU, no RCCL: made for hit vectors of a few MB, every MHC-sized graph) -- opt-in until a run on
     // two or more GPUs has compared the two bit for bit: its cross-GPU loads have only ever run between contexts on ONE GPU.
-    bool use_peers = false;
-    void *peer_group = nullptr;
-    if (n_dev > 1) {
+    int setup_exchange()
+    {
+        if (n_dev == 1) return 0;
         phi_index_info info;
-        if ((rc = phi_index_stats(ctx, &info))) return die("index", rc);
-        if (const char *e = getenv("PHI_EXCHANGE")) use_peers = strcmp(e, "peers") == 0;
-        if (use_peers && (rc = phi_peers_create(n_dev, &peer_group))) return die("peer group", rc);
+        int rc;
+        if ((rc = phi_index_stats(ctx, &info))) return fail_on(ctx, "index", rc);
+        use_peers = kn.exchange_peers;
+        if (use_peers && (rc = phi_peers_create(n_dev, &peer_group))) return fail_on(ctx, "peer group", rc);
         Stage st(use_peers ? "peer group (xGMI peer access)" : "RCCL communicator");
-        if (!use_peers && (rc = phi_comm_unique_id(comm_id, sizeof comm_id))) { fprintf(stderr, "[E::main] RCCL is not available: %s\n", phi_strerror(rc)); stop_reads(); return 1; }
+        if (!use_peers && (rc = phi_comm_unique_id(comm_id, sizeof comm_id))) return fail("[E::main] RCCL is not available: %s\n", phi_strerror(rc));
         if (run_on_all("communicator", [&](int i, phi_ctx *cx) -> int { return use_peers ? phi_peers_join(cx, peer_group, i) : phi_comm_init(cx, comm_id, i, n_dev); })) return 1;
         fprintf(stderr, "[M::main] %d GPUs; hit vector of %lld flags merged through %s\n", n_dev, (long long)info.n_distinct_minimizers, use_peers ? "peer-mapped memory (one OR-gather kernel per GPU)" : "RCCL all-reduce");
+        return 0;
     }
 
-    // ---- one job per read set (-r a -o a.fa -r b -o b.fa ...): the graph, its index and the communicator are made once
-    int status = 0;
-    std::atomic<bool> pinned{true};
-    std::once_flag pin_once;
-    bool registered = false;
-    for (int job = 0; job < n_jobs; job++) {
-    if (job > 0) {
-        // the next read set: clocks, names, the chunk queue and the reader thread start over; the contexts forget the reads
-        fflush(nullptr);
-        const double now = realtime();
-        cpu0 += cputime();
-        t0_real = now;
-        { std::lock_guard<std::mutex> lk(g_marks.mu); g_marks.marks.clear(); }
-        reads_file = o.reads_files[(size_t)job]; hap_file = o.hap_files[(size_t)job];
-        if (phi_hap_name(gfa_file.c_str(), reads_file.c_str(), hap_name, sizeof hap_name) < 0) { fprintf(stderr, "[E::%s] output name too long\n", "main"); return 1; }
-        {
-            std::lock_guard<std::mutex> lk(Q.mu);
-            Q.q_free.clear(); Q.q_full.clear(); Q.stop = false;
-            for (int i = 0; i < N_CHUNK_BUF; i++) { Q.buf[(size_t)i].n = 0; Q.q_free.push_back(i); }
+    // The device's text stream on cx ends (under the turn), and what it did not take goes through the host reader.  At the end of
+    // the stream (cb == nullptr) that is the file's last record, whose end only the end of the file shows; after text that is not
+    // one of the two regular layouts (cb: that chunk, in `slot`) it is the stream from the first byte not taken on.
+    int end_on_host(phi_ctx *cx, const Chunk *cb, int slot, bool irr_carry)
+    {
+        const char *pend = nullptr; int64_t n_pend = 0;
+        const int r = phi_reads_text_end(cx, &pend, &n_pend, nullptr);
+        std::vector<char> all;
+        if (!cb) {
+            if (!r && n_dev > 1) { pend = feed.carry.data(); n_pend = (int64_t)feed.carry.size(); }
+            if (r || !n_pend) return r;
+        } else {
+            if (!r && irr_carry) {                            // (the carry, fed as a piece of its own, was what did not fit: this chunk follows it)
+                all.assign(pend, pend + n_pend);
+                all.insert(all.end(), cb->text, cb->text + cb->n);
+                pend = all.data(); n_pend = (int64_t)all.size();
+            }
+            feed.give_free(slot);
+            if (r) return r;
+            if (timing) fprintf(stderr, "[phi timing] main: the reads text is not regular FASTA / 4-line FASTQ: host reader from the first byte not taken\n");
         }
-        rerr[0] = 0;
-        start_reads();
-        if (run_on_all("reset", [&](int, phi_ctx *cx) -> int { return phi_reset_reads(cx); })) return 1;
-        stamp("main");
-        fprintf(stderr, "Loaded graph from: %s\n", gfa_file.c_str());
+        return feed.host_reader(cx, pend, n_pend, cb != nullptr, feed.stream_fed - n_pend);
     }
-    // ---- reads (main.cpp:136-137) and stage 1b/2a (:615-655), chunk by chunk.  The chunks are taken in stream order,
-    //      one GPU at a time (a chunk needs the unfinished rest of the one before); the sketch of a chunk runs on
-    //      behind the turn.  Text that is not laid out regularly goes through the host reader from that byte on.
-    std::atomic<int> n_chunks{0};
-    std::mutex turn_mu;
-    std::vector<char> carry;                                  // several GPUs: the bytes the last turn left unfinished
-    bool stream_done = false;                                 // under turn_mu
-    int64_t stream_fed = 0;                                   // under turn_mu: bytes of the stream taken from the queue so far
-    int64_t host_parsed_bases = 0;
-    // the host reader over `prefix` + the rest of the queue -> phi_add_reads on this GPU (under turn_mu)
-    auto finish_on_host = [&](phi_ctx *cx, const char *prefix, int64_t n_prefix, bool rest_of_queue, int64_t stream_offset) -> int {
-        Stage st("host reader (kseq state machine)");
-        QueueBlocks qb{&Q, -1, &park, {}};
-        phi_reads_stream *rs = nullptr;
-        if (phi_reads_stream_open_blocks(prefix, n_prefix, rest_of_queue ? next_block_from_queue : nullptr, &qb, stream_offset, &rs, rerr, sizeof rerr) != PHI_HOST_OK) return PHI_ERR_INVALID;
-        const int64_t cap_b = std::max<int64_t>((int64_t)1 << 20, std::min<int64_t>(chunk_bytes, (int64_t)64 << 20)), cap_r = cap_b / 32 + 1024;
-        std::vector<char> hb((size_t)cap_b);
-        std::vector<int64_t> ho((size_t)cap_r + 1);
-        int r = PHI_OK;
-        for (;;) {
-            const int64_t n = phi_reads_stream_next(rs, hb.data(), cap_b, ho.data(), cap_r, rerr, sizeof rerr);
-            if (n < 0) { r = PHI_ERR_INVALID; break; }
-            if (n == 0) break;
-            host_parsed_bases += ho[(size_t)n];
-            if ((r = phi_add_reads(cx, hb.data(), ho.data(), n))) break;
+    // ---- reads (main.cpp:136-137) and stage 1b/2a (:615-655) on one GPU, chunk by chunk.  The chunks are taken in stream order,
+    //      one GPU at a time (a chunk needs the unfinished rest of the one before); the sketch of a chunk runs on behind the turn.
+    //      Text that is not laid out regularly goes through the host reader from that byte on.
+    int feed_reads(phi_ctx *cx)
+    {
+        ReadsFeed &f = feed;
+        int r = phi_reads_text_begin(cx, f.chunk_bytes);
+        bool open = r == PHI_OK;
+        while (!r) {
+            std::unique_lock<std::mutex> turn(f.turn_mu);
+            if (f.stream_done || failed) break;
+            const int slot = f.take_full();
+            Chunk &cb = *f.at(slot);
+            int32_t irr_carry = 0, irr = 0;
+            if (cb.n < 0) { f.stream_done = true; r = PHI_ERR_INVALID; fprintf(stderr, "[E::main] %s\n", f.err); break; }
+            if (cb.n > 0) {
+                if (++f.n_chunks >= 2) f.pin_buffers(cx);
+                f.stream_fed += cb.n;
+                if (n_dev > 1 && !f.carry.empty()) r = phi_add_reads_text(cx, f.carry.data(), (int64_t)f.carry.size(), &irr_carry);
+                if (!r && !irr_carry && cb.parked >= 0) {
+                    r = phi_add_reads_text_parked(cx, f.park, cb.parked, &irr);
+                    if (!r) (void)phi_text_park_release(f.park, cb.parked);
+                } else if (!r && !irr_carry) r = phi_add_reads_text(cx, cb.text, cb.n, &irr);
+            }
+            if (!r && (cb.n == 0 || irr_carry || irr)) {
+                // the end of the stream (left in the queue for the other GPUs), or the exact state machine takes the stream
+                f.stream_done = true;
+                open = false;
+                r = end_on_host(cx, cb.n ? &cb : nullptr, slot, irr_carry);
+                break;
+            }
+            const char *p = nullptr; int64_t n = 0;
+            if (!r && n_dev > 1 && !(r = phi_reads_text_detach_carry(cx, &p, &n))) f.carry.assign(p, p + n);
+            f.give_free(slot);
         }
-        phi_reads_stream_close(rs);
-        if (qb.held >= 0) Q.give_free(qb.held);
-        if (r == PHI_ERR_INVALID && rerr[0]) fprintf(stderr, "[E::main] %s\n", rerr);
+        if (open) { const int r2 = phi_reads_text_end(cx, nullptr, nullptr, nullptr); if (!r) r = r2; }
         return r;
-    };
-    {
-        Stage st("reads: text -> device, records, sketch");
-        if (run_on_all("reads", [&](int, phi_ctx *cx) -> int {
-                int r = phi_reads_text_begin(cx, chunk_bytes);
-                bool open = r == PHI_OK;
-                while (!r) {
-                    std::unique_lock<std::mutex> turn(turn_mu);
-                    if (stream_done || failed) break;
-                    const int slot = Q.take_full();
-                    Chunk &cb = *Q.at(slot);
-                    if (cb.n <= 0) {
-                        // the end of the stream (left in the queue for the other GPUs): what is still unfinished is the file's
-                        // last record, whose end only the end of the file shows -- the host reader's
-                        stream_done = true;
-                        if (cb.n < 0) { r = PHI_ERR_INVALID; fprintf(stderr, "[E::main] %s\n", rerr); break; }
-                        const char *pend = nullptr;
-                        int64_t n_pend = 0;
-                        r = phi_reads_text_end(cx, &pend, &n_pend, nullptr);
-                        open = false;
-                        if (!r && n_dev > 1) { pend = carry.data(); n_pend = (int64_t)carry.size(); }
-                        if (!r && n_pend) r = finish_on_host(cx, pend, n_pend, false, stream_fed - n_pend);
-                        break;
-                    }
-                    if (++n_chunks >= 2)
-                        // a file of more than one chunk: pin the buffers, so that the device copy of every further
-                        // chunk is a direct DMA (pinning takes milliseconds: not worth it for a single chunk)
-                        std::call_once(pin_once, [&]() {
-                            if (park_pinned.load()) return;    // (the reader thread pinned them when it began to park chunks)
-                            registered = true;
-                            std::lock_guard<std::mutex> lk(Q.mu);      // (the reader thread may be adding an entry for a parked chunk)
-                            for (auto &b : Q.buf) if (b.text && phi_host_register(cx, b.text, (size_t)chunk_bytes) != PHI_OK) pinned = false;
-                        });
-                    stream_fed += cb.n;
-                    int32_t irr_carry = 0, irr = 0;
-                    if (n_dev > 1 && !carry.empty()) r = phi_add_reads_text(cx, carry.data(), (int64_t)carry.size(), &irr_carry);
-                    if (!r && !irr_carry) {
-                        if (cb.parked >= 0) {
-                            r = phi_add_reads_text_parked(cx, park, cb.parked, &irr);
-                            if (!r) (void)phi_text_park_release(park, cb.parked);
-                        } else r = phi_add_reads_text(cx, cb.text, cb.n, &irr);
-                    }
-                    if (!r && (irr_carry || irr)) {
-                        // not one of the two regular layouts: the exact state machine takes the stream from the first byte not taken
-                        stream_done = true;
-                        const char *pend = nullptr;
-                        int64_t n_pend = 0;
-                        r = phi_reads_text_end(cx, &pend, &n_pend, nullptr);
-                        open = false;
-                        std::vector<char> all;
-                        if (!r && irr_carry) {                 // (the carry, fed as a piece of its own, was what did not fit: this chunk follows it)
-                            all.assign(pend, pend + n_pend);
-                            all.insert(all.end(), cb.text, cb.text + cb.n);
-                            pend = all.data(); n_pend = (int64_t)all.size();
-                        }
-                        Q.give_free(slot);
-                        if (!r) {
-                            if (timing) fprintf(stderr, "[phi timing] main: the reads text is not regular FASTA / 4-line FASTQ: host reader from the first byte not taken\n");
-                            r = finish_on_host(cx, pend, n_pend, true, stream_fed - n_pend);
-                        }
-                        break;
-                    }
-                    if (!r && n_dev > 1) {
-                        const char *p = nullptr;
-                        int64_t n = 0;
-                        r = phi_reads_text_detach_carry(cx, &p, &n);
-                        if (!r) carry.assign(p, p + n);
-                    }
-                    Q.give_free(slot);
-                }
-                if (open) { const int r2 = phi_reads_text_end(cx, nullptr, nullptr, nullptr); if (!r) r = r2; }
-                return r;
-            })) return 1;
     }
-    if (f_reads.get() != PHI_HOST_OK) { fprintf(stderr, "[E::%s] %s\n", "main", rerr); return 1; }
-    if (n_dev > 1) {
-        Stage st(use_peers ? "exchange (peer-mapped)" : "exchange (RCCL)");
-        if (run_on_all("exchange", [&](int, phi_ctx *cx) -> int { return use_peers ? phi_peers_exchange(cx) : phi_comm_exchange(cx); })) return 1;
-    }
-    int64_t total_reads = 0;
-    for (phi_ctx *cx : ctxs) {
-        int64_t nr = 0;
-        if ((rc = phi_reads_stats(cx, &nr, nullptr, nullptr, nullptr))) return die_on(cx, "reads", rc);
-        total_reads += nr;
-    }
-    stamp("ILP_function");
-    fprintf(stderr, "Graph has %d vertices, %d walks and read has %d reads\n", phi_graph_n_vtx(g), n_walks, (int)total_reads);
-    // ---- stages 2b-3 (:670-1525)
-    phi_result res;
-    {
-        Stage st("phi_solve (filter, exact solve, decode)");
-        if ((rc = phi_solve(ctx, &res))) return die("solve", rc);
-    }
-    const double t_report = realtime();
 
-    fprintf(stderr, "Number of Minimizers\n");
-    for (int32_t h = 0; h < n_walks; h++) fprintf(stderr, "%s : %d\n", phi_graph_hap_name(g, h), (int)res.n_minimizers[h]);
-    if (debug) {                                              // ILP_index.cpp:591-604
-        std::vector<int64_t> hist((size_t)n_walks + 1, 0);
-        int64_t n_distinct = 0;
-        if ((rc = phi_walk_sharing(ctx, hist.data(), n_walks + 1, &n_distinct))) return die("sharing histogram", rc);
-        fprintf(stderr, "Shared fraction of unique kmers by haplotypes\n");
-        for (int32_t i = 1; i <= n_walks; i++)
-            fprintf(stderr, "[Haplotypes: %d, fraction of unique shared kmers: %.5f]\n", i, (float)hist[i] / (float)n_distinct);
+    // ---- the log (ILP_index.cpp, stages 2b-3), the FASTA (:1577-1598) and the tail of the run
+    int report(const phi_result &res)
+    {
+        const double t_report = realtime();
+        const int32_t n_walks = phi_graph_n_walks(g);
+        int rc;
+        fprintf(stderr, "Number of Minimizers\n");
+        for (int32_t h = 0; h < n_walks; h++) fprintf(stderr, "%s : %d\n", phi_graph_hap_name(g, h), (int)res.n_minimizers[h]);
+        if (o.debug) {                                        // ILP_index.cpp:591-604
+            std::vector<int64_t> hist((size_t)n_walks + 1, 0);
+            int64_t n_distinct = 0;
+            if ((rc = phi_walk_sharing(ctx, hist.data(), n_walks + 1, &n_distinct))) return fail_on(ctx, "sharing histogram", rc);
+            fprintf(stderr, "Shared fraction of unique kmers by haplotypes\n");
+            for (int32_t i = 1; i <= n_walks; i++)
+                fprintf(stderr, "[Haplotypes: %d, fraction of unique shared kmers: %.5f]\n", i, (float)hist[i] / (float)n_distinct);
+        }
+        stamp("ILP_function"); fprintf(stderr, "Haplotypes sketched\n");
+        stamp("ILP_function"); fprintf(stderr, "Indexed reads with spectrum size: %d\n", (int)res.spectrum_size);
+        fprintf(stderr, "Number of Anchors\n");
+        for (int32_t h = 0; h < n_walks; h++) fprintf(stderr, "%s : %d\n", phi_graph_hap_name(g, h), (int)res.n_anchors[h]);
+        stamp("ILP_function");
+        fprintf(stderr, "Filtered/Retained Minimizers: %.2f/%.2f%%\n", (float)res.filtered / (float)res.spectrum_size * 100, (float)res.retained / (float)res.spectrum_size * 100);
+        stamp("ILP_function"); fprintf(stderr, "%s model started\n", o.is_qclp ? "QP" : "ILP");
+        stamp("ILP_function"); fprintf(stderr, "%.2f%% Minimizers are in ILP\n", (res.n_in_model * 100.0) / res.spectrum_size);
+        stamp("ILP_function"); fprintf(stderr, "Minimizer constraints added to the model\n");
+        stamp("ILP_function"); fprintf(stderr, "%s\n", o.is_mixed ? "Using Mixed Integer Programming" : "Using Integer Programming");
+        stamp("ILP_function"); fprintf(stderr, "Optimized expanded graph constructed\n");
+        stamp("ILP_function"); fprintf(stderr, "Model optimized\n");
+        if (o.debug || !res.optimal)
+            fprintf(stderr, "[M::%s] objective %lld (upper bound %lld, %s) after %d DP run(s); %lld minimisers covered, %d w-node(s)\n", "solve", (long long)res.objective,
+                    (long long)res.upper_bound, res.optimal ? "proven optimal" : "NOT proven optimal", res.n_dp_runs, (long long)res.n_covered, res.n_switches);
+        fprintf(stderr, "Recombination count: %d\nRecombined haplotypes: ", res.recombination_count);
+        print_recombinations(res);
+        g_marks.add("report (log lines)", t_report, realtime());
+        {
+            Stage st("FASTA write");
+            std::unique_ptr<char[]> seq(new char[(size_t)(res.hap_len > 0 ? res.hap_len : 1)]);      // (not zero-filled: every byte is written)
+            if ((rc = phi_path_sequence(ctx, seq.get(), res.hap_len))) return fail_on(ctx, "sequence", rc);
+            if (phi_write_fasta(hap_file.c_str(), hap_name, seq.get(), res.hap_len) != PHI_HOST_OK) return fail("[E::main] cannot write %s\n", hap_file.c_str());
+        }
+        stamp("ILP_function"); fprintf(stderr, "Haplotype of size: %d written to: %s\n", (int)res.hap_len, hap_file.c_str());
+        fprintf(stderr, "[M::%s] PHI Version: %s\n[M::%s] CMD:", "main", PHI_VERSION, "main");
+        for (int i = 0; i < o.argc; ++i) fprintf(stderr, " %s", o.argv[i]);
+        fprintf(stderr, "\n[M::%s] Real time: %.3f sec; CPU: %.3f sec; Peak RSS: %.3f GB\n", "main", realtime() - t0_real, cputime(), peakrss() / 1024.0 / 1024.0 / 1024.0);
+        if (!timing) return 0;
+        if (feed.parked_bytes) fprintf(stderr, "[phi timing] main: %lld bytes of the reads text waited in device memory for the index\n", (long long)feed.parked_bytes);
+        const phi_inflate_info &inf = feed.inflated;
+        if (inf.out_bytes)
+            fprintf(stderr, "[phi timing] main: %lld bytes inflated on the device from %lld gzip bytes (%lld chunks: %lld confirmed at their start, %lld decoded again)\n",
+                    (long long)inf.out_bytes, (long long)inf.in_bytes, (long long)inf.chunks, (long long)inf.confirmed, (long long)inf.redecoded);
+        fprintf(stderr, "[phi timing] main: %d text chunk(s) of up to %lld bytes%s on %d GPU(s); %lld bases through the host reader; FASTA closed at epoch %.6f%s\n",
+                feed.n_chunks.load(), (long long)feed.chunk_bytes, feed.n_chunks >= 2 && feed.pinned ? ", pinned" : "", n_dev, (long long)feed.host_bases, realtime(),
+                o.detached ? "; teardown detached" : "");
+        g_marks.print();
+        print_resident();
+        return 0;
     }
-    stamp("ILP_function");
-    fprintf(stderr, "Haplotypes sketched\n");
-    stamp("ILP_function");
-    fprintf(stderr, "Indexed reads with spectrum size: %d\n", (int)res.spectrum_size);
-    fprintf(stderr, "Number of Anchors\n");
-    for (int32_t h = 0; h < n_walks; h++) fprintf(stderr, "%s : %d\n", phi_graph_hap_name(g, h), (int)res.n_anchors[h]);
-    stamp("ILP_function");
-    fprintf(stderr, "Filtered/Retained Minimizers: %.2f/%.2f%%\n", (float)res.filtered / (float)res.spectrum_size * 100,
-            (float)res.retained / (float)res.spectrum_size * 100);
-    stamp("ILP_function");
-    fprintf(stderr, "%s model started\n", is_qclp ? "QP" : "ILP");
-    stamp("ILP_function");
-    fprintf(stderr, "%.2f%% Minimizers are in ILP\n", (res.n_in_model * 100.0) / res.spectrum_size);
-    stamp("ILP_function");
-    fprintf(stderr, "Minimizer constraints added to the model\n");
-    stamp("ILP_function");
-    fprintf(stderr, "%s\n", is_mixed ? "Using Mixed Integer Programming" : "Using Integer Programming");
-    stamp("ILP_function");
-    fprintf(stderr, "Optimized expanded graph constructed\n");
-    stamp("ILP_function");
-    fprintf(stderr, "Model optimized\n");
-    if (debug || !res.optimal)
-        fprintf(stderr, "[M::%s] objective %lld (upper bound %lld, %s) after %d DP run(s); %lld minimisers covered, %d w-node(s)\n", "solve",
-                (long long)res.objective, (long long)res.upper_bound, res.optimal ? "proven optimal" : "NOT proven optimal", res.n_dp_runs,
-                (long long)res.n_covered, res.n_switches);
-
     // ---- recombination report (:1508-1550): segments in output coordinates
-    fprintf(stderr, "Recombination count: %d\n", res.recombination_count);
-    fprintf(stderr, "Recombined haplotypes: ");
+    void print_recombinations(const phi_result &res)
     {
         const int64_t *so = phi_graph_seq_off(g);
         int64_t str_id = 0, prev_str_id = 0;
         int32_t prev_hap = res.n_path ? res.path_hap[0] : 0;
         for (int64_t i = 0; i < res.n_path; i++) {
             const int32_t v = res.path_vtx[i];
+            str_id += so[v + 1] - so[v];                      // (the reference adds the vertex length before testing the label: :1515-1523)
             if (i > 0 && res.path_hap[i] != prev_hap) {
-                // the reference adds the vertex length before testing the label (:1515-1523)
-                str_id += so[v + 1] - so[v];
                 fprintf(stderr, ">(%s,[%lld,%lld])", phi_graph_hap_name(g, prev_hap), (long long)prev_str_id, (long long)(str_id - 1));
-                prev_hap = res.path_hap[i];
-                prev_str_id = str_id;
-            } else {
-                str_id += so[v + 1] - so[v];
+                prev_hap = res.path_hap[i]; prev_str_id = str_id;
             }
         }
         if (res.n_path) fprintf(stderr, ">(%s,[%lld,%lld])", phi_graph_hap_name(g, prev_hap), (long long)prev_str_id, (long long)(str_id - 1));
         fprintf(stderr, "\n");
     }
-    g_marks.add("report (log lines)", t_report, realtime());
-
-    // ---- FASTA (:1577-1598)
+    // what the peak is made of: the mapped GFA file's own pages count as resident (RssFile / RssShmem), anonymous memory is the rest
+    static void print_resident()
     {
-        Stage st("FASTA write");
-        std::unique_ptr<char[]> seq(new char[(size_t)(res.hap_len > 0 ? res.hap_len : 1)]);      // (not zero-filled: every byte is written)
-        if ((rc = phi_path_sequence(ctx, seq.get(), res.hap_len))) return die("sequence", rc);
-        if (phi_write_fasta(hap_file.c_str(), hap_name, seq.get(), res.hap_len) != PHI_HOST_OK) {
-            fprintf(stderr, "[E::%s] cannot write %s\n", "main", hap_file.c_str());
-            return 1;
+        FILE *fp = fopen("/proc/self/status", "r");
+        if (!fp) return;
+        char line[256];
+        long hwm = -1, anon = -1, file = -1, shm = -1;
+        while (fgets(line, sizeof line, fp)) {
+            if (!strncmp(line, "VmHWM:", 6)) hwm = atol(line + 6);
+            else if (!strncmp(line, "RssAnon:", 8)) anon = atol(line + 8);
+            else if (!strncmp(line, "RssFile:", 8)) file = atol(line + 8);
+            else if (!strncmp(line, "RssShmem:", 9)) shm = atol(line + 9);
         }
+        fclose(fp);
+        fprintf(stderr, "[phi timing] main: resident now: anonymous %.3f GB, mapped files %.3f GB (the GFA among them); peak %.3f GB\n", anon / 1048576.0, (file + shm) / 1048576.0, hwm / 1048576.0);
     }
-    stamp("ILP_function");
-    fprintf(stderr, "Haplotype of size: %d written to: %s\n", (int)res.hap_len, hap_file.c_str());
-
-    fprintf(stderr, "[M::%s] PHI Version: %s\n", "main", PHI_VERSION);
-    fprintf(stderr, "[M::%s] CMD:", "main");
-    for (int i = 0; i < o.argc; ++i) fprintf(stderr, " %s", o.argv[i]);
-    fprintf(stderr, "\n[M::%s] Real time: %.3f sec; CPU: %.3f sec; Peak RSS: %.3f GB\n", "main", realtime() - t0_real, cputime(),
-            peakrss() / 1024.0 / 1024.0 / 1024.0);
-    if (timing) {
-        if (parked_bytes) fprintf(stderr, "[phi timing] main: %lld bytes of the reads text waited in device memory for the index\n", (long long)parked_bytes);
-        if (inflated_bytes)
-            fprintf(stderr, "[phi timing] main: %lld bytes inflated on the device from %lld gzip bytes (%lld chunks: %lld confirmed at their start, %lld decoded again)\n",
-                    (long long)inflated_bytes, (long long)inflated_in, (long long)inflated_chunks, (long long)inflated_confirmed, (long long)inflated_again);
-        fprintf(stderr, "[phi timing] main: %d text chunk(s) of up to %lld bytes%s on %d GPU(s); %lld bases through the host reader; FASTA closed at epoch %.6f%s\n",
-                n_chunks.load(), (long long)chunk_bytes, n_chunks >= 2 && pinned ? ", pinned" : "", n_dev, (long long)host_parsed_bases, realtime(),
-                o.detached ? "; teardown detached" : "");
-        g_marks.print();
-        // what the peak is made of: the mapped GFA file's own pages count as resident (RssFile / RssShmem), anonymous memory is the rest
-        if (FILE *fp = fopen("/proc/self/status", "r")) {
-            char line[256];
-            long hwm = -1, anon = -1, file = -1, shm = -1;
-            while (fgets(line, sizeof line, fp)) {
-                if (!strncmp(line, "VmHWM:", 6)) hwm = atol(line + 6);
-                else if (!strncmp(line, "RssAnon:", 8)) anon = atol(line + 8);
-                else if (!strncmp(line, "RssFile:", 8)) file = atol(line + 8);
-                else if (!strncmp(line, "RssShmem:", 9)) shm = atol(line + 9);
-            }
-            fclose(fp);
-            fprintf(stderr, "[phi timing] main: resident now: anonymous %.3f GB, mapped files %.3f GB (the GFA among them); peak %.3f GB\n", anon / 1048576.0, (file + shm) / 1048576.0, hwm / 1048576.0);
+    // ---- one read set against the graph and its index: 0, 3 (the path is not proven optimal) or 1 (an error)
+    int run_job(int job)
+    {
+        if (job > 0) {
+            // the next read set: clocks, names, the chunk queue and the reader thread start over; the contexts forget the reads
+            fflush(nullptr);
+            const double now = realtime();
+            cpu0 += cputime(); t0_real = now;
+            g_marks.clear();
+            reads_file = o.reads_files[(size_t)job]; hap_file = o.hap_files[(size_t)job];
+            if (name_job()) return 1;
+            feed.start(reads_file);
+            if (run_on_all("reset", [&](int, phi_ctx *cx) -> int { return phi_reset_reads(cx); })) return 1;
+            loaded();
         }
-    }
-    if (!res.optimal) {
+        if (Stage st("reads: text -> device, records, sketch"); run_on_all("reads", [&](int, phi_ctx *cx) -> int { return feed_reads(cx); })) return 1;
+        if (feed.reader.get() != PHI_HOST_OK) return fail("[E::main] %s\n", feed.err);
+        if (n_dev > 1) {
+            Stage st(use_peers ? "exchange (peer-mapped)" : "exchange (RCCL)");
+            if (run_on_all("exchange", [&](int, phi_ctx *cx) -> int { return use_peers ? phi_peers_exchange(cx) : phi_comm_exchange(cx); })) return 1;
+        }
+        int64_t total_reads = 0;
+        int rc;
+        for (phi_ctx *cx : ctxs) {
+            int64_t nr = 0;
+            if ((rc = phi_reads_stats(cx, &nr, nullptr, nullptr, nullptr))) return fail_on(cx, "reads", rc);
+            total_reads += nr;
+        }
+        stamp("ILP_function"); fprintf(stderr, "Graph has %d vertices, %d walks and read has %d reads\n", phi_graph_n_vtx(g), phi_graph_n_walks(g), (int)total_reads);
+        phi_result res;
+        if (Stage st("phi_solve (filter, exact solve, decode)"); (rc = phi_solve(ctx, &res))) return fail_on(ctx, "solve", rc);
+        if (report(res)) return 1;
+        if (res.optimal) return 0;
         // the reference returns only what model.optimize() proved (ILP_index.cpp:1418); here that can only fall short when
         // --dp-budget set a limit: the path written is feasible and within the printed bound, the exit status says so
-        fprintf(stderr, "[W::main] the path written is NOT proven optimal: the exact search used its budget of %d DP runs "
-                        "(objective %lld, proven upper bound %lld); raise it with --dp-budget N (0 = no limit, the default)\n",
-                res.n_dp_runs, (long long)res.objective, (long long)res.upper_bound);
-        status = 3;
+        fprintf(stderr, "[W::main] the path written is NOT proven optimal: the exact search used its budget of %d DP runs (objective %lld, proven upper bound %lld); "
+                        "raise it with --dp-budget N (0 = no limit, the default)\n", res.n_dp_runs, (long long)res.objective, (long long)res.upper_bound);
+        return 3;
     }
-    }   // jobs
-    if (getenv("PHI_FULL_TEARDOWN")) {                        // (leak checks: give everything back in order)
-        stop_reads();
-        if (park) phi_text_park_destroy(park);                 // (unpins the chunk buffers it pinned)
-        for (auto &cb : Q.buf) {
-            if (registered && cb.text) (void)phi_host_unregister(ctx, cb.text);
-            free(cb.text);
+    // PHI_FULL_TEARDOWN (leak checks): everything given back in order
+    void teardown() { feed.stop_reader(); feed.teardown(ctx); phi_graph_free(g); for (phi_ctx *cx : ctxs) phi_ctx_destroy(cx); }
+};
+
+// Every stage keeps its overlap: the device contexts are made while the GFA is parsed, the reads file is read while the graph
+// loads, its text is parked in device memory only between the GFA parsed and the index built, and the device inflater waits
+// for the GFA parsed.
+static int run(const Options &o)
+{
+    Driver d(o);
+    const Knobs &kn = d.kn;
+    std::vector<int> &devices = d.devices;
+    if (devices.empty()) devices.push_back(o.device);
+    for (size_t i = 0; i < devices.size(); i++)
+        for (size_t j = 0; j < i; j++)
+            if (devices[i] == devices[j] && !kn.allow_same_device) { fprintf(stderr, "[E::main] --devices names GPU %d twice\n", devices[i]); return 1; }
+    // a read set is sharded only over as many GPUs as it can keep busy: every further GPU costs an exchange (~tens of
+    // microseconds) and an index build, and one GPU scores 50 Mbases in a fifth of a millisecond
+    if (const FileProbe p = devices.size() > 1 ? probe_file(d.reads_file) : FileProbe(); p.regular) {
+        const long long bytes = (long long)p.size;
+        const size_t want = (size_t)std::max<long long>(1, (bytes + o.shard_min_bases - 1) / std::max<long long>(1, o.shard_min_bases));
+        if (want < devices.size()) {
+            fprintf(stderr, "[M::main] reads file of %lld bytes: using %zu of the %zu GPUs given (--shard-min-bases %lld per GPU)\n", bytes, want, devices.size(), o.shard_min_bases);
+            devices.resize(want);
         }
-        phi_graph_free(g);
-        for (phi_ctx *cx : ctxs) phi_ctx_destroy(cx);
     }
+    const int n_dev = d.n_dev = (int)devices.size();
+
+    // The device context (HIP initialisation) and the reads file are prepared by two host threads while this one parses the
+    // graph: the three are independent.  One host thread per GPU: each context initialises its own device.
+    d.ctxs.assign((size_t)n_dev, nullptr);
+    d.f_ctx = std::async(std::launch::async, [&d, n_dev]() {
+        Stage st("device context(s) [thread]");
+        std::vector<std::future<int>> fs;
+        for (int i = 0; i < n_dev; i++)
+            fs.push_back(std::async(std::launch::async, [&d, i]() { return phi_ctx_create(d.devices[(size_t)i], &d.ctxs[(size_t)i]); }));
+        int r = 0;
+        for (auto &f : fs) { const int ri = f.get(); if (ri && !r) r = ri; }
+        return r;
+    }).share();
+    const FileProbe rp = probe_file(d.reads_file);
+    if (!d.feed.alloc(&kn, devices[0], chunk_size(kn, o.reads_files), 2 + n_dev, n_dev == 1 && kn.text_park && rp.regular && rp.size >= kn.text_park_min,
+                      n_dev == 1 && kn.inflate))
+        { fprintf(stderr, "[E::%s] out of memory\n", __func__); return 1; }
+    d.feed.start(d.reads_file);
+
+    if (d.load_graph()) return 1;
+    d.loaded();
+    if (d.name_job()) return 1;
+    int rc;
+    if (Stage st("wait for the device context"); (rc = d.f_ctx.get())) return d.fail("[E::main] no usable MI355X (HIP) device %d: %s\n", devices[0], phi_strerror(rc));
+    d.ctx = d.ctxs[0];
+    if (d.build_index()) return 1;
+    d.feed.mark(d.feed.index_built);                         // (the reader thread stops parking chunks: they are taken as they come now)
+    if (d.setup_exchange()) return 1;
+
+    // ---- one job per read set (-r a -o a.fa -r b -o b.fa ...): the graph, its index and the communicator are made once
+    int status = 0;
+    for (int job = 0; job < (int)o.reads_files.size(); job++) {
+        const int r = d.run_job(job);
+        if (r == 1) return 1;
+        if (r) status = r;
+    }
+    if (kn.full_teardown) d.teardown();
     return status;
 }
 
