@@ -731,9 +731,13 @@ __global__ void __launch_bounds__(TPB, MODE == PHI_MODE_PROBE ? 6 : 1) phi_sketc
 // LDS of a wave (phi_win_mp_u64): read rl's k-mers lie in s = G + ceil(w / Q) rows of 9 u64 (8 slots + the pad word SM
 // keeps), k-mer t in slot 8 s rl + 1 + t, so that lane j reads its Q + w k-mers at constant offsets from one address, as in
 // base space; once they are read, the lanes' minima go to slots 8 lane + i (rows 0 .. 64, the layout phases 4 - 5 and the
-// items expect) and the 16-bit items behind them.  With the staged words and bitmap of bases outside ACGTacgt that is at
-// most what the base-space kernel takes for the same (k, w): phi_sketch_win_reads picks R so.  At L = 150, (31, 25):
-// G = 12, s = 16, R = 5 (480 windows a wave instead of ~330), 6 144 B a wave (base space: 6 560 B).
+// items expect) and the 16-bit items behind them.  The SWW staged words and the SBW bitmap words of bases outside ACGTacgt
+// take no room of their own: the staged words lie at the start of the region until every lane has taken its two extracts
+// (phase 1), and the bitmap is only needed on the rare path of a wave whose bases are not all ACGTacgt (chunk_bad): there
+// it is staged again, from global memory, into a part of the region that is dead at that point (before phase 3 and after
+// the rounds).  At L = 150, (31, 25): G = 12, s = 16, R = 5 (480 windows a wave instead of ~330), 5 760 B a wave (768 u64
+// with the staging behind the k-mers; base space: 6 560 B) -- seven workgroups of four waves per CU instead of six, so
+// that the 6 880 waves of C2 are resident at once.
 __host__ __device__ static inline int phi_win_items_u64(int w, int k) { return ((phi_wave_items(w, k) + 4) * 2 + 7) / 8; }
 __host__ __device__ static inline int phi_win_mp_u64(int R, int s, int w, int k)
 {
@@ -741,7 +745,23 @@ __host__ __device__ static inline int phi_win_mp_u64(int R, int s, int w, int k)
     const int minima = 9 * (64 + 1) + phi_win_items_u64(w, k);    // minima of 64 lanes (rows 0 .. 64), then the items
     return kmers > minima ? kmers : minima;
 }
-__host__ __device__ static inline int phi_win_region_u64(int R, int s, int w, int k) { return phi_win_mp_u64(R, s, w, k) + SWW + SBW; }
+__host__ __device__ static inline int phi_win_region_u64(int R, int s, int w, int k) { return phi_win_mp_u64(R, s, w, k); }
+
+// The bitmap of bases outside ACGTacgt for local bits 0 .. 64 SBW (bases c0 - 64 ..), as phase 0 of the base-space kernel
+// lays it out: lane < 62 -> bits 64 + 16 lane .. + 15 (its 16 staged bases); the first 32 bits are 0.  Staged again from
+// global memory on the rare path that needs it (see phi_win_mp_u64); the caller syncs the wave around it.
+__device__ __forceinline__ void stage_bad_bits(const uint8_t *__restrict__ ascii, int64_t N, int64_t c0, int lane,
+                                               unsigned long long *s_bad)
+{
+    uint32_t bad = 0;
+    if (lane < 62) {
+        const uint4 v = load_bases16<1>(ascii, N, c0, lane);
+        const uint32_t x[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int b = 0; b < 16; b++) bad |= (uint32_t)(!phi_is_acgt((x[b >> 2] >> (8 * (b & 3))) & 0xFFu)) << b;
+    }
+    reinterpret_cast<uint16_t *>(s_bad)[lane < 62 ? lane + 2 : lane - 62] = (uint16_t)bad;
+}
 
 // The byte-wise routine for the windows of this wave's reads that touch a base outside ACGTacgt (window, or its predecessor:
 // the same partition as in base space).  Window q of the wave = window v of read rl: base (r0 + rl) L + v.
@@ -775,7 +795,7 @@ __device__ __forceinline__ void slow_windows_reads(const PhiSketchArgs &A, int64
 }
 
 template <bool WIDE, int KT, int WT>
-__global__ void __launch_bounds__(TPB, 6) phi_sketch_win_kernel(PhiSketchArgs A)   // (six waves per SIMD, at most 80 VGPRs)
+__global__ void __launch_bounds__(TPB, 7) phi_sketch_win_kernel(PhiSketchArgs A)   // (seven waves per SIMD, at most 72 VGPRs)
 {
     constexpr int MODE = PHI_MODE_PROBE;
     constexpr bool NEED_POS = false;                     // (names of the shared phases)
@@ -809,13 +829,13 @@ __global__ void __launch_bounds__(TPB, 6) phi_sketch_win_kernel(PhiSketchArgs A)
     constexpr uint32_t ITEM_FIRST = 1u << 15;            // the first window of its read
     constexpr uint32_t ITEM_NOEMIT = 1u << 14;           // only its hash is needed (the window before a candidate)
     uint64_t *s_mp = s_dyn + (size_t)wid * phi_win_region_u64(R, s, w, k);   // k-mers; later the window minima and the items
-    uint64_t *s_words = s_mp + phi_win_mp_u64(R, s, w, k);
-    unsigned long long *s_bad = (unsigned long long *)(s_words + SWW);
+    uint64_t *s_words = s_mp;                             // staged words: until phase 1 has taken its extracts
+    unsigned long long *s_bad = (unsigned long long *)s_mp;   // bitmap (chunk_bad only): staged where the region is dead
     MetaT *s_meta = (MetaT *)(s_mp + 9 * (64 + 1));      // items: behind the minima
     uint64_t *s_q = s_mp + (live ? 9 * (rl * s + j) : 0);   // k-mer 8j - 1 + x of the lane's read: s_q[x + (x >> 3)]
 
     // ---- phase 0: lane -> the 16 bases c0 - 32 + 16 lane .. + 15: one 32-bit half of a packed word + 16 flags of bases
-    //      outside ACGTacgt (the text of sketch_phases.inc, phase 0)
+    //      outside ACGTacgt (the text of sketch_phases.inc, phase 0); the flags only decide chunk_bad here (stage_bad_bits)
     bool chunk_bad;
     {
         const uint4 v = load_bases16<1>(A.ascii, N, c0, lane);
@@ -832,24 +852,29 @@ __global__ void __launch_bounds__(TPB, 6) phi_sketch_win_kernel(PhiSketchArgs A)
             }
         }
         reinterpret_cast<uint32_t *>(s_words)[lane ^ 1] = code;
-        uint16_t *s_bad16 = reinterpret_cast<uint16_t *>(s_bad);
-        if (lane < 62) s_bad16[lane + 2] = (uint16_t)bad;
-        else { s_bad16[lane - 62] = 0; bad = 0; }
-        chunk_bad = __ballot(bad != 0) != 0ull;          // wave-uniform
+        chunk_bad = __ballot(lane < 62 && bad != 0) != 0ull;   // wave-uniform
     }
     wave_sync();
 
-    // ---- phase 1: the read's L - k + 1 canonical k-mers, P consecutive per lane of its group
-    if (live) {
-        const int n_km = L - k + 1, P = (n_km + G - 1) / G;
-        const int t0 = j * P;
-        const int n = n_km - t0 < P ? n_km - t0 : P;
+    // ---- phase 1: the read's L - k + 1 canonical k-mers, P consecutive per lane of its group.  Every lane takes its two
+    //      extracts of the staged words first: the k-mers go over them
+    {
+        int n = 0, u = 0;
+        uint64_t F = 0, Rc = 0, nxt = 0;
+        if (live) {
+            const int n_km = L - k + 1, P = (n_km + G - 1) / G;
+            const int t0 = j * P;
+            n = n_km - t0 < P ? n_km - t0 : P;
+            if (n > 0) {
+                const int lb = (int)((rd0 + rl) * (int64_t)L + t0 - c0) + 32;
+                F = lds_extract64(s_words, lb) >> (64 - 2 * k);
+                nxt = lds_extract64(s_words, lb + k);                 // the bases after the first k-mer
+                u = 8 * s * rl + 1 + t0;                               // slot of k-mer t0
+            }
+        }
+        wave_sync();
         if (n > 0) {
-            const int lb = (int)((rd0 + rl) * (int64_t)L + t0 - c0) + 32;
-            uint64_t F = lds_extract64(s_words, lb) >> (64 - 2 * k);
-            uint64_t Rc = phi_revcomp(F, k);
-            uint64_t nxt = lds_extract64(s_words, lb + k);         // the bases after the first k-mer
-            int u = 8 * s * rl + 1 + t0;                              // slot of k-mer t0
+            Rc = phi_revcomp(F, k);
             for (int i = 0; i < n; i++, u++) {
                 if (i) {
                     const uint64_t b = nxt >> 62;
@@ -867,6 +892,11 @@ __global__ void __launch_bounds__(TPB, 6) phi_sketch_win_kernel(PhiSketchArgs A)
 #include "sketch_minima.inc"
 
     // ---- phase 3: candidate windows i = 1..Q of this lane (window 8j + i - 1 of its read)
+    if (chunk_bad) {                                      // (wave-uniform, rare) every lane has read its k-mers: the bitmap over them
+        wave_sync();
+        stage_bad_bits(A.ascii, N, c0, lane, s_bad);
+        wave_sync();
+    }
     uint32_t cflag = 0, fflag = 0, pflag = 0;             // candidates; first windows; candidates that carry their predecessor
     if (live) {
         const int imax = V - Q * j < Q ? V - Q * j : Q;   // windows i <= imax exist
@@ -931,18 +961,28 @@ __global__ void __launch_bounds__(TPB, 6) phi_sketch_win_kernel(PhiSketchArgs A)
 #include "sketch_rounds.inc"
 
     if (chunk_bad) {
+        // (the wave's region from a scalar: its vector address would be one register too many around the byte-wise routine)
+        unsigned long long *s_bad_s = (unsigned long long *)(s_dyn + (size_t)__builtin_amdgcn_readfirstlane(wid) * phi_win_region_u64(R, s, w, k));
+        wave_sync();                                      // the rounds have read the minima and the items: the bitmap over them
+        stage_bad_bits(A.ascii, N, c0, lane, s_bad_s);
+        wave_sync();
         int n_emit_slow = 0;
-        slow_windows_reads(A, rd0, nr, L, V, c0, lane, k, w, s_bad, n_emit_slow, n_nov_slow);
+        slow_windows_reads(A, rd0, nr, L, V, c0, lane, k, w, s_bad_s, n_emit_slow, n_nov_slow);
         n_emit += n_emit_slow;
     }
-    if (A.q_clean) clean_finish(A, chunk, (int64_t)gridDim.x * (TPB / 64), lane);
-    if (lane == 0) {
-        const int cap = 1 << A.nov_shift;
-        A.nov_cnt[A.log_base + chunk] = (uint16_t)(n_log < cap ? n_log : cap);
-        const int n_nov_wave = n_log + n_nov_slow;
-        const int stripe = (int)(chunk & (PHI_STRIPES - 1)) * 8;
-        if (n_nov_wave && A.n_logged) atomicAdd(A.n_logged + stripe, (unsigned long long)n_nov_wave);
-        if (n_emit && A.n_emitted) atomicAdd(A.n_emitted + stripe, (unsigned long long)n_emit);
+    {
+        // (the arguments of the epilogue are loaded now, not kept in scalar registers from the start: seven waves per SIMD
+        //  leave 94 of them, and each one too many is a v_writelane / v_readlane pair in a lane of a vector register)
+        const KArgs P = kargs_now();
+        if (P->q_clean) clean_finish(*P, chunk, (int64_t)gridDim.x * (TPB / 64), lane);
+        if (lane == 0) {
+            const int cap = 1 << P->nov_shift;
+            P->nov_cnt[P->log_base + chunk] = (uint16_t)(n_log < cap ? n_log : cap);
+            const int n_nov_wave = n_log + n_nov_slow;
+            const int stripe = (int)(chunk & (PHI_STRIPES - 1)) * 8;
+            if (n_nov_wave && P->n_logged) atomicAdd(P->n_logged + stripe, (unsigned long long)n_nov_wave);
+            if (n_emit && P->n_emitted) atomicAdd(P->n_emitted + stripe, (unsigned long long)n_emit);
+        }
     }
 }
 
@@ -1292,7 +1332,8 @@ int phi_sketch_win_reads(int k, int w, int64_t uniform_len, int64_t n_reads, int
     if (G > 64 || (L - k + 1 + G - 1) / G > 32) return 0;
     int R = 64 / G;
     if (R > 928 / L) R = (int)(928 / L);
-    while (R > 0 && phi_win_region_u64(R, s, w, k) > phi_wave_region_u64(w, k, false)) R--;
+    // (R as when the staged words and bitmap lay behind the k-mers: the reads of a wave do not change with the smaller region)
+    while (R > 0 && phi_win_region_u64(R, s, w, k) + SWW + SBW > phi_wave_region_u64(w, k, false)) R--;
     if (R < 1) return 0;
     if (force != 1 && (R * L < WCH + WCH / 8 || (getenv("PHI_SKETCH_POOL_MIN") && phi_sketch_num_blocks(n_bases) >= pool_min_chunks()))) return 0;
     return R;
