@@ -177,6 +177,10 @@ int phi_reads_stats(phi_ctx *ctx, int64_t *n_reads, int64_t *n_bases, int64_t *n
  *   phi_spectrum_set_size  alternatively, override |Sp_R| used in the log counters
  */
 int phi_hits_buffer(phi_ctx *ctx, void **d_hits, int64_t *n);
+/* The read table the read kernels probe (diagnostics, tests): device pointer to n_buckets 32-byte buckets of two slots,
+ * u64 words [key 0, id 0 | flags << 32, key 1, id 1] (empty key UINT64_MAX; flag 1: a key whose home bucket this is lies
+ * in a later bucket), home bucket key & (n_buckets - 1); valid until the next phi_set_graph on this context. */
+int phi_read_table(phi_ctx *ctx, void **d_table, int64_t *n_buckets);
 int phi_spectrum_export(phi_ctx *ctx, void **d_hashes, int64_t *n);
 int phi_spectrum_import(phi_ctx *ctx, const void *d_hashes, int64_t n);
 int phi_spectrum_set_size(phi_ctx *ctx, int64_t global_size);

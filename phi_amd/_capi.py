@@ -18,7 +18,7 @@ PHI_COMM_ID_BYTES = 128
 # every symbol include/phi_amd.h declares
 SYMBOLS = [
     "phi_strerror", "phi_last_error", "phi_ctx_create", "phi_ctx_destroy", "phi_set_stream", "phi_set_params",
-    "phi_set_graph", "phi_add_reads", "phi_add_reads_device", "phi_reset_reads", "phi_reads_stats", "phi_hits_buffer",
+    "phi_set_graph", "phi_add_reads", "phi_add_reads_device", "phi_reset_reads", "phi_reads_stats", "phi_hits_buffer", "phi_read_table",
     "phi_spectrum_export", "phi_spectrum_import", "phi_spectrum_set_size", "phi_solve", "phi_path_sequence",
     "phi_sketch", "phi_walk_minimizers", "phi_walk_sharing", "phi_kept_anchors", "phi_prof_enable", "phi_prof_read",
     "phi_host_register", "phi_host_unregister", "phi_set_solve_budget", "phi_device_synchronize", "phi_walk_text_upload", "phi_walk_text_resolve", "phi_walk_entries",
@@ -113,6 +113,7 @@ def load():
     L.phi_add_reads_text_parked.argtypes = [vp, vp, i32, C.POINTER(i32)]
     L.phi_reads_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
     L.phi_hits_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(i64)]
+    L.phi_read_table.argtypes = [vp, C.POINTER(vp), C.POINTER(i64)]
     L.phi_spectrum_export.argtypes = [vp, C.POINTER(vp), C.POINTER(i64)]
     L.phi_spectrum_import.argtypes = [vp, vp, i64]
     L.phi_spectrum_set_size.argtypes = [vp, i64]

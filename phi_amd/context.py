@@ -158,6 +158,12 @@ class Context:
         self._chk(self._L.phi_hits_buffer(self._h, C.byref(p), C.byref(n)))
         return p.value, n.value
 
+    def read_table(self):
+        """Device pointer and bucket count of the read table the read kernels probe (phi_read_table)."""
+        p, n = C.c_void_p(), C.c_int64()
+        self._chk(self._L.phi_read_table(self._h, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
     def spectrum_export(self):
         p, n = C.c_void_p(), C.c_int64()
         self._chk(self._L.phi_spectrum_export(self._h, C.byref(p), C.byref(n)))

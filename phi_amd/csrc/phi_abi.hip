@@ -496,7 +496,7 @@ void phi_ctx_destroy(phi_ctx *c)
     DevBuf *all[] = {&c->d_anchors, &c->d_cov_all, &c->d_cov_w, &c->d_slots, &c->d_slots2, &c->d_segs, &c->d_ctr, &c->d_vmax, &c->d_lane_walk, &c->d_walk_lane, &c->d_coff, &c->d_blk_ncls, &c->d_rownew, &c->d_blk_bad, &c->d_seg_lo, &c->d_seg_row, &c->d_seg_S, &c->wtext.d_text, &c->d_sel_off, &c->d_sel_tri, &c->d_blk_lo, &c->d_blk_ev, &c->d_blk_S, &c->d_row_out, &c->d_rowend, &c->d_blk_keys, &c->d_blk_carry, &c->d_cov, &c->d_cov2, &c->d_stepdiff, &c->alt.hit, &c->hit_extra[0], &c->hit_extra[1], &c->alt.stripes, &c->d_sp_cnt, &c->d_novlog, &c->d_novcnt, &c->d_ovlist, &c->d_vlen, &c->d_ent_cls, &c->d_cls_rep, &c->d_cls_left, &c->d_cls_mult, &c->d_cls_base, &c->d_cls_rec_off, &c->d_rec_cls, &c->d_rec_rel, &c->d_u_replist, &c->d_adj_off, &c->d_adj, &c->d_topo_rank, &c->d_cnt_edge, &c->d_walk_err, &c->d_sa_cnt, &c->d_sa_cur, &c->d_sa_off, &c->d_sa_idx, &c->d_seq, &c->d_seq_off, &c->d_walk_vtx, &c->d_walk_off, &c->d_topo, &c->d_in_off,
                      &c->d_in_src, &c->d_e_out, &c->d_st_rec, &c->d_st_mask, &c->d_in_packed, &c->d_word, &c->d_wwords, &c->d_wbad,
                      &c->d_wascii, &c->d_wstarts, &c->d_rec_hash, &c->d_rec_pos, &c->d_rec_slot,
-                     &c->d_rec_e0, &c->d_rec_e1, &c->d_u_keys, &c->d_u_rep, &c->d_u_uid, &c->d_u_kv, &c->d_in_s, &c->d_last_walk, &c->d_rowdiag, &c->d_wpre, &c->d_hit, &c->d_sp_keys, &c->d_rbases,
+                     &c->d_rec_e0, &c->d_rec_e1, &c->d_u_keys, &c->d_u_rep, &c->d_u_uid, &c->d_rt, &c->d_in_s, &c->d_last_walk, &c->d_rowdiag, &c->d_wpre, &c->d_hit, &c->d_sp_keys, &c->d_rbases,
                      &c->d_roff, &c->d_roff_made, &c->d_peer_send, &c->d_export, &c->d_scalars, &c->d_stripes, &c->d_blk_cnt,
                      &c->d_blk_off, &c->d_flags, &c->d_flags2, &c->d_list, &c->d_list2, &c->d_list3, &c->d_walk_last, &c->d_m_rec, &c->d_m_group,
                      &c->d_g_keys, &c->d_g_rep, &c->d_g_cnt, &c->d_slot_maxcnt, &c->d_slot_multi, &c->d_a_e1,
@@ -577,6 +577,36 @@ static int sketch_records(phi_ctx *c, const uint64_t *words, const unsigned long
 
 
 }  // extern "C" (helpers below are C++)
+
+// The read table of the read probes (phi_launch_read_table) from the walk-minimiser table's keys and dense ids.  At most
+// 3/16 key per bucket: a read probe then takes a second trip when the key it looks for sits past its home bucket (0.25 %
+// of the keys at C2's 0.127 a bucket, 0.54 % at 3/16) or when a novel hash's home bucket has overflowed (3e-4 / 1e-3 of
+// the buckets); C2's 533 074 keys get 2^22 buckets, the 134 MB the one-slot table of pairs had.  A key that finds no
+// room within PHI_MAX_PROBE buckets: built again at twice the buckets.  PHI_READ_TABLE_BUCKETS (tests): the first try's
+// buckets -- high loads, overflow chains, the full table.
+static int build_read_table(phi_ctx *c)
+{
+    uint64_t nb = pow2_at_least(std::max<uint64_t>(64, (16 * (uint64_t)c->n_unique + 2) / 3));
+    if (const char *e = getenv("PHI_READ_TABLE_BUCKETS")) nb = pow2_at_least(std::max<long long>(atoll(e), 1));
+    uint32_t err0 = 0;                                  // (a table overflow raised before this one: reported by phi_sync_check)
+    HIPCHK(hipMemcpyAsync(&err0, scalar(c, S_ERR), 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int attempt = 0;; attempt++) {
+        PHICHK(phi_dev_ensure(c, c->d_rt, nb * 32));
+        phi_launch_read_table(c->stream, c->d_u_keys.as<uint64_t>(), c->d_u_uid.as<uint32_t>(), (int64_t)c->u_cap,
+                              c->d_rt.as<uint64_t>(), (int64_t)nb, (uint32_t *)scalar(c, S_ERR));
+        uint32_t err = 0;
+        HIPCHK(hipMemcpyAsync(&err, scalar(c, S_ERR), 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if ((err0 & PHI_KERR_TABLE_FULL) || !(err & PHI_KERR_TABLE_FULL)) break;
+        if (attempt >= 40) return phi_fail(c, PHI_ERR_OVERFLOW, "read table overflow at %llu buckets (internal error)", (unsigned long long)nb);
+        err &= ~PHI_KERR_TABLE_FULL;
+        HIPCHK(phi_copy_sync(c, scalar(c, S_ERR), &err, 4, hipMemcpyHostToDevice));
+        nb *= 2;
+    }
+    c->rt_buckets = nb; c->rt_mask = nb - 1;
+    return PHI_OK;
+}
 
 // Classes of walk entries with equal context, their sketch in class space and the class records
 // (contexts.hip).  Leaves d_vlen, d_ent_cls, d_cls_*, d_rec_{hash,cls,rel,e0,e1}, n_cls, n_rec,
@@ -946,7 +976,8 @@ int phi_set_graph(phi_ctx *c, int32_t n_vtx, const char *seq_concat, const int64
         const int64_t nr = std::max<int64_t>(c->n_rec, 1);
         PHICHK(phi_dev_ensure(c, c->d_rec_slot, (size_t)nr * 4));
         // The table is built over the class records (nearly all distinct) at twice their number, then
-        // re-inserted at 8x the distinct keys (load ~12 %: read probes settle on the first slot).
+        // re-inserted at 8x the distinct keys (load ~12 %).  The read probes go to the read table built from it
+        // (build_read_table).
         const uint64_t cap_full = pow2_at_least(std::max<uint64_t>(1024, 2 * (uint64_t)c->n_rec));
         const uint64_t UMULT = 8;
         PHICHK(phi_dev_ensure(c, c->d_flags, (size_t)nr));
@@ -988,9 +1019,7 @@ int phi_set_graph(phi_ctx *c, int32_t n_vtx, const char *seq_concat, const int64
                                     c->d_u_uid.as<uint32_t>());
             }
         }
-        PHICHK(phi_dev_ensure(c, c->d_u_kv, c->u_cap * 16));
-        phi_launch_table_pairs(c->stream, c->d_u_keys.as<uint64_t>(), c->d_u_uid.as<uint32_t>(), (int64_t)c->u_cap,
-                               c->d_u_kv.as<uint64_t>());
+        PHICHK(build_read_table(c));
         // records of each walk ("Number of Minimizers", ILP_index.cpp:563) = sum over its entries of their class's records
         {
             PHICHK(phi_dev_ensure(c, c->d_list2, (size_t)(n_walks + 1) * 8));
@@ -1354,7 +1383,7 @@ int phi_add_reads_device_impl(phi_ctx *c, const void *d_bases, const void *d_rea
     A.n_bases = n_bases; A.k = c->k; A.w = c->w;
     A.n_logged = replay ? nullptr : logged_stripes(c);
     A.n_emitted = replay ? nullptr : emit_stripes(c);
-    A.u_kv = c->d_u_kv.as<uint64_t>(); A.u_mask = c->u_cap - 1;
+    A.u_rt = c->d_rt.as<uint64_t>(); A.u_bmask = c->rt_mask;
     A.hit = c->d_hit.as<uint8_t>();
     A.err = (uint32_t *)scalar(c, S_ERR);
     A.nov_log = c->d_novlog.as<uint64_t>(); A.nov_cnt = c->d_novcnt.as<uint16_t>(); A.log_base = c->log_chunks; A.nov_shift = c->nov_shift;
@@ -1945,6 +1974,15 @@ int phi_hits_buffer(phi_ctx *c, void **d_hits, int64_t *n)
     PHICHK(phi_flush_reset(c));
     *d_hits = c->d_hit.p;
     *n = c->n_unique;
+    return PHI_OK;
+}
+
+int phi_read_table(phi_ctx *c, void **d_table, int64_t *n_buckets)
+{
+    if (!c || !d_table || !n_buckets) return PHI_ERR_INVALID;
+    if (!c->have_graph) return phi_fail(c, PHI_ERR_STATE, "phi_read_table before phi_set_graph");
+    *d_table = c->d_rt.p;
+    *n_buckets = (int64_t)c->rt_buckets;
     return PHI_OK;
 }
 

@@ -118,7 +118,8 @@ struct phi_ctx {
     DevBuf d_rec_hash, d_rec_pos, d_rec_cls, d_rec_rel, d_rec_slot, d_rec_e0, d_rec_e1;
     int64_t n_rec = 0;
     DevBuf d_u_keys, d_u_rep, d_u_uid, d_u_replist;   // walk-minimiser table: keys, first record, dense id; dense id -> first record
-    DevBuf d_u_kv;                                    // the same table as (key, id) pairs, for the read probes
+    DevBuf d_rt;                                      // the same keys with their ids as the read table of the read probes (phi_launch_read_table)
+    uint64_t rt_buckets = 0, rt_mask = 0;             // its 32-byte buckets (a power of two) and the mask of the bucket index
     void *h_stage[2] = {nullptr, nullptr};            // pinned staging buffers of large uploads from pageable memory (phi_abi.hip upload_staged)
     hipEvent_t stage_ev[2] = {nullptr, nullptr};
     DevBuf d_wpre;                                    // per DP run: prefix sums of the anchor weights (dp_events.hip)

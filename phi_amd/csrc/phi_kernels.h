@@ -12,6 +12,7 @@
 #define PHI_MAX_K 64              // k-mers of up to 32 bases are 2-bit values in 64 bits (the fast kernels); 33 .. 64 take the
 #define PHI_MAX_K_PACKED 32       // exact byte-wise routine for every window (slow, exact: the reference is string based, any k)
 #define PHI_MAX_PROBE 4096     // linear-probe bound of the open-addressed tables
+#define PHI_RT_OVERFLOWED 1u   // read table: flag of a bucket (upper word of its slot 0) -- a key whose home it is lies in a later bucket
 // log of the read hashes that are not walk minimisers: 1 << shift entries per chunk of 512 windows, 1.5x what random
 // sequence emits at this w (2 / (w + 1) per window), a power of two in [16, 512]; what a chunk has beyond goes to the
 // generation's overflow list
@@ -67,7 +68,7 @@ struct PhiSketchArgs {
     // PHI_MODE_PROBE
     unsigned long long *n_logged;          // [PHI_STRIPES][8] striped counter of novel hashes logged (with duplicates: an upper bound of the set's growth)
     unsigned long long *n_emitted;         // [PHI_STRIPES][8] striped counter of emitted records
-    const uint64_t *u_kv; uint64_t u_mask; // walk-minimiser table as (key, dense id) pairs: one 16-byte load per probe
+    const uint64_t *u_rt; uint64_t u_bmask; // read table of the walk minimisers (phi_launch_read_table): 32-byte buckets, mask of the bucket index
     uint8_t *hit;                          // per distinct walk minimiser (dense id)
     uint32_t *err;
     // PHI_MODE_PROBE: log of the NOVEL read hashes (emitted, not walk minimisers): 1 << nov_shift entries per chunk,
@@ -126,8 +127,14 @@ void phi_launch_table_compact(hipStream_t st, const int32_t *rep_list, int64_t n
 void phi_launch_share_hist(hipStream_t st, const uint64_t *keys, int64_t cap, const int32_t *n_walks_of, unsigned long long *hist);
 void phi_launch_slot_uid(hipStream_t st, const int32_t *rep_list, int64_t n_unique, const uint32_t *rec_slot,
                          uint32_t *u_uid);
-// (key, id) pairs of the walk-minimiser table for the read probes: kv[2s] = keys[s], kv[2s+1] = uid[s]
-void phi_launch_table_pairs(hipStream_t st, const uint64_t *keys, const uint32_t *uid, int64_t cap, uint64_t *kv);
+// The read table: the keys of the walk-minimiser table (slots of `keys` that hold one, cap of them) with their dense ids
+// uid, re-inserted for the read probes into n_buckets (a power of two) aligned 32-byte buckets of two slots,
+//   rt[4b] = key 0, rt[4b+1] = id 0 | flags << 32, rt[4b+2] = key 1, rt[4b+3] = id 1,
+// home bucket key & (n_buckets - 1), linear probing over buckets (slot 1 of a bucket is taken only after slot 0).  Flag
+// PHI_RT_OVERFLOWED of a bucket: a key whose home it is lies in a later bucket.  A key that finds no room within
+// PHI_MAX_PROBE buckets raises PHI_KERR_TABLE_FULL in *err (the host rebuilds at twice the buckets).
+void phi_launch_read_table(hipStream_t st, const uint64_t *keys, const uint32_t *uid, int64_t cap, uint64_t *rt,
+                           int64_t n_buckets, uint32_t *err);
 void phi_launch_fill_u64(hipStream_t st, uint64_t *p, int64_t n, uint64_t v);
 void phi_launch_fill_u32(hipStream_t st, uint32_t *p, int64_t n, uint32_t v);
 void phi_launch_iota_i64(hipStream_t st, int64_t *p, int64_t n, int64_t step);   // p[i] = i * step

@@ -207,25 +207,41 @@ __device__ __forceinline__ MinEnt take_right(MinEnt a, MinEnt b) { return (b.v <
 // per novel hash into a 64-MB table, a second dependent round trip behind the probe and ~100 bytes of write traffic per
 // 8-byte key: 45 % of the launch on long noisy reads): the wave appends them to its LOG, coalesced, and the set is made
 // from the log once, when somebody asks for |Sp_R| (phi_abi.hip sp_flush).
+// The table is the read table of table.hip (phi_launch_read_table): aligned 32-byte buckets of two (key, id) slots, home
+// bucket h & bmask.  A lookup loads its whole home bucket -- both slots, keys and ids, issued before one wait -- and is done
+// unless the bucket's OVERFLOWED flag says that a key whose home it is lies in a later bucket (3e-4 of the buckets at
+// C2); only then does it walk on, bucket by bucket, to a match or to a bucket with a free slot.  The old one-slot table
+// took a dependent trip per displaced slot in most waves.
 // returns true when h is NOT a walk minimiser
-struct ProbeArgs { const uint64_t *u_kv; uint64_t u_mask; uint8_t *hit; uint32_t *err; };
+struct ProbeArgs { const uint64_t *u_rt; uint64_t u_bmask; uint8_t *hit; uint32_t *err; };
+// one bucket: both keys, both ids and the flags in registers.  (Every half made live here: left alone the compiler loads
+// the keys, and each id in a second, dependent load inside the branch of its match.)
+__device__ __forceinline__ void rt_bucket(const uint64_t *rt, uint64_t b, ulonglong2 &s0, uint3 &s1)
+{
+    const uint64_t *p = rt + 4 * b;
+    s0 = *reinterpret_cast<const ulonglong2 *>(p);               // key 0, id 0 | flags << 32
+    s1 = *reinterpret_cast<const uint3 *>(p + 2);                // key 1 (x, y), id 1 (z): the word after it carries nothing
+    asm volatile("" : "+v"(s0.x), "+v"(s0.y), "+v"(s1.x), "+v"(s1.y), "+v"(s1.z));
+}
 __device__ __forceinline__ bool probe_table(const ProbeArgs &A, uint64_t h)
 {
     if (h == PHI_EMPTY_KEY) { atomicOr(A.err, PHI_KERR_SENTINEL); return false; }
-    uint64_t su = h & A.u_mask;
-    const ulonglong2 *kv = reinterpret_cast<const ulonglong2 *>(A.u_kv);
-    ulonglong2 e0 = kv[su];                            // key and dense id in one round trip
-    // (both halves made live here: left alone the compiler loads the key, and the id in a second, dependent load
-    //  inside the branch of a match -- 85 % of the probes)
-    asm volatile("" : "+v"(e0.x), "+v"(e0.y));
+    uint64_t b = h & A.u_bmask;
+    ulonglong2 s0;
+    uint3 s1;
+    rt_bucket(A.u_rt, b, s0, s1);
     // walk-minimiser table: lookup, mark the minimiser as hit
-    if (e0.x == h) { A.hit[(uint32_t)e0.y] = 1; return false; }
-    if (e0.x != PHI_EMPTY_KEY) {
+    const uint64_t k1 = ((uint64_t)s1.y << 32) | s1.x;
+    if (s0.x == h) { A.hit[(uint32_t)s0.y] = 1; return false; }
+    if (k1 == h) { A.hit[s1.z] = 1; return false; }
+    if ((s0.y >> 32) & PHI_RT_OVERFLOWED) {
         for (int probes = 1; probes <= PHI_MAX_PROBE; probes++) {
-            su = (su + 1) & A.u_mask;
-            const ulonglong2 e = kv[su];
-            if (e.x == h) { A.hit[(uint32_t)e.y] = 1; return false; }
-            if (e.x == PHI_EMPTY_KEY) break;
+            b = (b + 1) & A.u_bmask;
+            rt_bucket(A.u_rt, b, s0, s1);
+            const uint64_t n1 = ((uint64_t)s1.y << 32) | s1.x;
+            if (s0.x == h) { A.hit[(uint32_t)s0.y] = 1; return false; }
+            if (n1 == h) { A.hit[s1.z] = 1; return false; }
+            if (n1 == PHI_EMPTY_KEY) break;                      // a bucket with room ends every chain through it
         }
     }
     return true;
@@ -233,7 +249,7 @@ __device__ __forceinline__ bool probe_table(const ProbeArgs &A, uint64_t h)
 
 __device__ __forceinline__ bool probe_table(const PhiSketchArgs &A, uint64_t h)
 {
-    const ProbeArgs P{A.u_kv, A.u_mask, A.hit, A.err};
+    const ProbeArgs P{A.u_rt, A.u_bmask, A.hit, A.err};
     return probe_table(P, h);
 }
 
@@ -1107,7 +1123,7 @@ __global__ void __launch_bounds__(TPB, 6) phi_sketch_pool_kernel(PhiSketchArgs A
             asm volatile("" :: "v"(h));                   // (experiment: hash, no probe)
 #else
             if (emit) {
-                const ProbeArgs P{R->u_kv, R->u_mask, R->hit, R->err};
+                const ProbeArgs P{R->u_rt, R->u_bmask, R->hit, R->err};
                 novel = probe_table(P, h);
             }
 #endif

@@ -28,19 +28,45 @@ static inline unsigned grid_for(int64_t n, int tpb)
     return (unsigned)nb;
 }
 
-__global__ void __launch_bounds__(256) phi_table_pairs_kernel(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ uid,
-                                                              int64_t cap, ulonglong2 *__restrict__ kv)
+// The read table (phi_kernels.h phi_launch_read_table): every slot empty, every id and flag word 0
+__global__ void __launch_bounds__(256) phi_read_table_clear_kernel(ulonglong2 *__restrict__ rt, int64_t n_slots)
+{
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_slots; i += (int64_t)gridDim.x * blockDim.x)
+        rt[i] = make_ulonglong2(PHI_EMPTY_KEY, 0ull);
+}
+// One lane per slot of the walk-minimiser table that holds a key: the first free slot from its home bucket on (slot 0 of a
+// bucket before slot 1, so a bucket with a free slot has its slot 1 free), then its id; a key that lands past its home
+// flags the home bucket.  Ids and flags share a word and are both OR-ed in: no order between the lanes matters.
+__global__ void __launch_bounds__(256) phi_read_table_insert_kernel(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ uid,
+                                                                    int64_t cap, unsigned long long *__restrict__ rt, uint64_t bmask,
+                                                                    uint32_t *__restrict__ err)
 {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cap; i += (int64_t)gridDim.x * blockDim.x) {
         const uint64_t key = keys[i];
-        kv[i] = make_ulonglong2(key, key == PHI_EMPTY_KEY ? 0ull : (unsigned long long)uid[i]);
+        if (key == PHI_EMPTY_KEY) continue;
+        const uint64_t home = key & bmask;
+        uint64_t b = home;
+        int probes = 0;
+        for (;;) {
+            unsigned long long *s = rt + 4 * b;
+            if (atomicCAS(&s[0], PHI_EMPTY_KEY, key) == PHI_EMPTY_KEY) { atomicOr(&s[1], (unsigned long long)uid[i]); break; }
+            if (atomicCAS(&s[2], PHI_EMPTY_KEY, key) == PHI_EMPTY_KEY) { atomicOr(&s[3], (unsigned long long)uid[i]); break; }
+            b = (b + 1) & bmask;
+            if (++probes > PHI_MAX_PROBE) { atomicOr(err, PHI_KERR_TABLE_FULL); break; }
+        }
+        if (b != home) atomicOr(&rt[4 * home + 1], (unsigned long long)PHI_RT_OVERFLOWED << 32);
     }
 }
 
-void phi_launch_table_pairs(hipStream_t st, const uint64_t *keys, const uint32_t *uid, int64_t cap, uint64_t *kv)
+void phi_launch_read_table(hipStream_t st, const uint64_t *keys, const uint32_t *uid, int64_t cap, uint64_t *rt,
+                           int64_t n_buckets, uint32_t *err)
 {
-    if (cap > 0)
-        hipLaunchKernelGGL(phi_table_pairs_kernel, dim3(grid_for(cap, 256)), dim3(256), 0, st, keys, uid, cap, (ulonglong2 *)kv);
+    if (n_buckets > 0)
+        hipLaunchKernelGGL(phi_read_table_clear_kernel, dim3(grid_for(2 * n_buckets, 256)), dim3(256), 0, st, (ulonglong2 *)rt,
+                           2 * n_buckets);
+    if (cap > 0 && n_buckets > 0)
+        hipLaunchKernelGGL(phi_read_table_insert_kernel, dim3(grid_for(cap, 256)), dim3(256), 0, st, keys, uid, cap,
+                           (unsigned long long *)rt, (uint64_t)n_buckets - 1, err);
 }
 
 void phi_launch_fill_u64(hipStream_t st, uint64_t *p, int64_t n, uint64_t v)
