@@ -736,6 +736,7 @@ __global__ void __launch_bounds__(TPB, MODE == PHI_MODE_PROBE ? 6 : 1) phi_sketc
         }
     }
 }
+#endif
 
 // ---- read batches of ONE length in WINDOW space (phi_launch_sketch: uniform_len > 0, k <= 32, phi_sketch_win_reads > 0)
 // A read of length L has V = L - (k + w - 1) + 1 windows; the base-space kernel above spends its lanes on all L positions
@@ -810,6 +811,7 @@ __device__ __forceinline__ void slow_windows_reads(const PhiSketchArgs &A, int64
     }
 }
 
+#ifndef PHI_SKETCH_POOLED_TU
 template <bool WIDE, int KT, int WT>
 __global__ void __launch_bounds__(TPB, 7) phi_sketch_win_kernel(PhiSketchArgs A)   // (seven waves per SIMD, at most 72 VGPRs)
 {
@@ -1002,7 +1004,7 @@ __global__ void __launch_bounds__(TPB, 7) phi_sketch_win_kernel(PhiSketchArgs A)
     }
 }
 
-#else
+#elif !defined(PHI_SKETCH_WIN_FIXED_TU)
 // The read kernel (PHI_MODE_PROBE) for batches of 12 Mbases and more, k <= 32 (phi_launch_sketch); compiled in
 // sketch_pooled.hip only.  Wave g of A.wave_stride takes the chunks g, g + stride, g + 2 stride, ... and hashes their items
 // in rounds of 64 FULL lanes -- the items a round leaves over (fewer than 64) wait in one register pair per lane for the
@@ -1186,7 +1188,9 @@ __global__ void __launch_bounds__(TPB, 6) phi_sketch_pool_kernel(PhiSketchArgs A
 
 #endif
 
-#ifdef PHI_SKETCH_POOLED_TU
+#ifdef PHI_SKETCH_WIN_FIXED_TU
+// sketch_win_fixed.hip: this file again, for its helpers alone (the kernel and its launcher follow there)
+#elif defined(PHI_SKETCH_POOLED_TU)
 // sketch_pooled.hip: this file again, compiled for the POOLED instances of the read kernel alone, with machine LICM off --
 // their loop over a wave's chunks runs at the 80-register bound of six waves per SIMD, and constants and addresses hoisted
 // out of it stay in registers through every turn (106 VGPRs in scratch).  The one-chunk instances keep the default.
@@ -1198,6 +1202,7 @@ void phi_launch_sketch_pooled(hipStream_t st, unsigned nb, size_t lds, const Phi
 }
 #else
 void phi_launch_sketch_pooled(hipStream_t st, unsigned nb, size_t lds, const PhiSketchArgs &A, hipEvent_t t0, hipEvent_t t1);   // sketch_pooled.hip
+bool phi_launch_sketch_win_fixed(hipStream_t st, unsigned nb, size_t lds, const PhiSketchArgs &A, hipEvent_t t0, hipEvent_t t1);   // sketch_win_fixed.hip
 
 // Exact byte-wise kernel: every wave walks chunks in a grid-stride loop.
 //   allslow = 0 (reads): launched after the 2-bit kernel with a small grid; leaves at once when the
@@ -1376,6 +1381,7 @@ void phi_launch_sketch(hipStream_t st, int mode, const PhiSketchArgs &A0, hipEve
             const int V = (int)(A.uniform_len - (A.k + A.w - 1) + 1);
             const int s = (V + Q - 1) / Q + (A.w + Q - 1) / Q;
             const size_t lds = (size_t)phi_win_region_u64(R, s, A.w, A.k) * 8 * (TPB / 64);
+            if (phi_launch_sketch_win_fixed(st, nb, lds, A, t0, t1)) return;      // (a geometry with an instance of its own)
             if (A.k == 31 && A.w == 25) hipExtLaunchKernelGGL((phi_sketch_win_kernel<true, 31, 25>), dim3(nb), dim3(TPB), lds, st, t0, t1, 0, A);
             else if (A.w > Q) hipExtLaunchKernelGGL((phi_sketch_win_kernel<true, 0, 0>), dim3(nb), dim3(TPB), lds, st, t0, t1, 0, A);
             else hipExtLaunchKernelGGL((phi_sketch_win_kernel<false, 0, 0>), dim3(nb), dim3(TPB), lds, st, t0, t1, 0, A);
