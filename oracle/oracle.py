@@ -45,8 +45,8 @@ def lib():
         L.orc_sketch.restype = C.c_int64
         L.orc_sketch.argtypes = [C.c_char_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64]
         L.orc_run.restype = C.c_void_p
-        L.orc_run.argtypes = [C.c_int32, C.c_char_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
-                              C.c_char_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_float]
+        L.orc_run.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                              C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_float]
         L.orc_free.argtypes = [C.c_void_p]
         L.orc_stage_seconds.restype = C.c_double
         L.orc_stage_seconds.argtypes = [C.c_void_p, C.c_int]
@@ -55,6 +55,14 @@ def lib():
         L.orc_max_threads.restype = C.c_int
         L.orc_sketch_reads.restype = C.c_int64
         L.orc_sketch_reads.argtypes = [C.c_char_p, C.c_void_p, C.c_int64, C.c_int, C.c_int]
+        L.orc_spectrum_new.restype = C.c_void_p
+        L.orc_spectrum_new.argtypes = []
+        L.orc_spectrum_add_reads.restype = None
+        L.orc_spectrum_add_reads.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int]
+        L.orc_spectrum_finish.restype = C.c_int64
+        L.orc_spectrum_finish.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+        L.orc_spectrum_free.restype = None
+        L.orc_spectrum_free.argtypes = [C.c_void_p]
         for name in ("spectrum_size", "filtered", "retained", "n_in_model", "n_kept"):
             f = getattr(L, "orc_" + name)
             f.restype = C.c_int64
@@ -477,6 +485,18 @@ def _arr(ptr, n, dtype):
     return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ct)), shape=(n,)).copy()
 
 
+def _bytes_view(x):
+    """bytes / bytearray / uint8 array as a contiguous uint8 array over the same memory (a copy only when the array is
+    strided or of another type)."""
+    if isinstance(x, np.ndarray):
+        return np.ascontiguousarray(x, np.uint8)
+    return np.frombuffer(x, np.uint8)
+
+
+def _base_ptr(a):
+    return a.ctypes.data if a.size else None
+
+
 def run_stage12(g: Graph, reads, k=31, w=25, threshold=1.0) -> Stage12:
     """reads: list of sequences (bytes) or of (name, seq)."""
     L = lib()
@@ -485,9 +505,10 @@ def run_stage12(g: Graph, reads, k=31, w=25, threshold=1.0) -> Stage12:
     read_off = np.zeros(len(seqs) + 1, np.int64)
     np.cumsum([len(s) for s in seqs], out=read_off[1:])
     reads_concat = b"".join(seqs)
-    h = L.orc_run(g.n_vtx, A["seq_concat"], A["seq_off"].ctypes.data, g.n_walks,
+    seq, raw = _bytes_view(A["seq_concat"]), _bytes_view(reads_concat)
+    h = L.orc_run(g.n_vtx, _base_ptr(seq), A["seq_off"].ctypes.data, g.n_walks,
                   A["walk_off"].ctypes.data, A["walk_vtx"].ctypes.data,
-                  reads_concat, read_off.ctypes.data, len(seqs), k, w, C.c_float(threshold))
+                  _base_ptr(raw), read_off.ctypes.data, len(seqs), k, w, C.c_float(threshold))
     try:
         nk = L.orc_n_kept(h)
         nw = g.n_walks
@@ -517,12 +538,10 @@ def run_stage12_arrays(A, bases, read_off, k=31, w=25, threshold=1.0, threads=No
     walk_off = np.ascontiguousarray(A["walk_off"], np.int64)
     walk_vtx = np.ascontiguousarray(A["walk_vtx"], np.int32)
     read_off = np.ascontiguousarray(read_off, np.int64)
-    seq = A["seq_concat"]
-    seq = seq.tobytes() if isinstance(seq, np.ndarray) else bytes(seq)
-    raw = bases.tobytes() if isinstance(bases, np.ndarray) else bytes(bases)
+    seq, raw = _bytes_view(A["seq_concat"]), _bytes_view(bases)                 # views: neither sequence is copied
     nw = len(walk_off) - 1
-    h = L.orc_run(len(seq_off) - 1, seq, seq_off.ctypes.data, nw, walk_off.ctypes.data, walk_vtx.ctypes.data,
-                  raw, read_off.ctypes.data, len(read_off) - 1, k, w, C.c_float(threshold))
+    h = L.orc_run(len(seq_off) - 1, _base_ptr(seq), seq_off.ctypes.data, nw, walk_off.ctypes.data, walk_vtx.ctypes.data,
+                  _base_ptr(raw), read_off.ctypes.data, len(read_off) - 1, k, w, C.c_float(threshold))
     try:
         nk = L.orc_n_kept(h)
         m_off = _arr(L.orc_m_off(h), nw + 1, np.int64)
@@ -540,3 +559,58 @@ def run_stage12_arrays(A, bases, read_off, k=31, w=25, threshold=1.0, threads=No
         return st
     finally:
         L.orc_free(h)
+
+
+# ---------------------------------------------------------------------------- stage 1b alone
+
+class SpectrumAccumulator:
+    """The read spectrum (ILP_index.cpp:615-638) on its own, fed batch by batch: nothing but the distinct hashes is kept
+    between batches, so a read set never has to be held whole."""
+
+    def __init__(self, k, w, threads=None):
+        self._L = lib()
+        if threads:
+            self._L.orc_set_threads(int(threads))
+        self.k, self.w = k, w
+        self._h = self._L.orc_spectrum_new()
+
+    def add(self, bases, read_off):
+        raw = _bytes_view(bases)
+        read_off = np.ascontiguousarray(read_off, np.int64)
+        if len(read_off) > 1:
+            assert read_off[0] >= 0 and read_off[-1] <= raw.size and np.all(np.diff(read_off) >= 0)
+        self._L.orc_spectrum_add_reads(self._h, _base_ptr(raw), read_off.ctypes.data, len(read_off) - 1, self.k, self.w)
+
+    def finish(self):
+        """(sorted distinct hashes as uint64, emitted minimisers with repeats); the accumulator is freed."""
+        p, e = C.c_void_p(), C.c_int64()
+        n = self._L.orc_spectrum_finish(self._h, C.byref(p), C.byref(e))
+        out = _arr(p.value, n, np.uint64)
+        self.close()
+        return out, e.value
+
+    def close(self):
+        if self._h:
+            self._L.orc_spectrum_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def read_spectrum(batches, k, w, threads=None):
+    """(sorted uint64 array of the distinct read hashes, emitted minimisers) over an iterable of (bases, read_off)."""
+    acc = SpectrumAccumulator(k, w, threads)
+    for bases, read_off in batches:
+        acc.add(bases, read_off)
+    return acc.finish()
+
+
+def sketch_reads_count(bases, read_off, k, w):
+    """orc_sketch_reads: the minimisers a batch of reads emits."""
+    raw = _bytes_view(bases)
+    read_off = np.ascontiguousarray(read_off, np.int64)
+    return int(lib().orc_sketch_reads(raw.ctypes.data_as(C.c_char_p), read_off.ctypes.data, len(read_off) - 1, k, w))

@@ -148,6 +148,26 @@ int64_t orc_sketch_reads(const char *reads_concat, const int64_t *read_off, int6
     return total;
 }
 
+/* compute_hashes over a batch of reads with every emitted hash kept, in read order (ILP_index.cpp:617-621): the loop of
+ * stage 1b, shared by orc_run and the spectrum accumulator.  Returns a malloc'ed array, *n_out = the emitted minimisers. */
+static uint64_t *sketch_reads_hashes(const char *reads_concat, const int64_t *read_off, int64_t n_reads, int k, int w,
+                                     int64_t *n_out)
+{
+    int64_t *r_off = (int64_t *)calloc((size_t)n_reads + 1, 8);
+#pragma omp parallel for schedule(dynamic, 256)
+    for (int64_t r = 0; r < n_reads; r++)
+        r_off[r + 1] = orc_sketch(reads_concat + read_off[r], read_off[r + 1] - read_off[r], k, w, 0, 0, 0);
+    for (int64_t r = 0; r < n_reads; r++) r_off[r + 1] += r_off[r];
+    int64_t sp_n = r_off[n_reads];
+    uint64_t *sp = (uint64_t *)malloc(8 * (size_t)(sp_n + 1));
+#pragma omp parallel for schedule(dynamic, 256)
+    for (int64_t r = 0; r < n_reads; r++)
+        orc_sketch(reads_concat + read_off[r], read_off[r + 1] - read_off[r], k, w, sp + r_off[r], 0, r_off[r + 1] - r_off[r]);
+    free(r_off);
+    *n_out = sp_n;
+    return sp;
+}
+
 /* ------------------------------------------------------------------ stages 1-2 driver */
 
 typedef struct {
@@ -270,17 +290,8 @@ orc_result_t *orc_run(int32_t n_vtx, const char *seq_concat, const int64_t *seq_
 
     R->stage_s[0] = omp_get_wtime() - t_stage; t_stage = omp_get_wtime();
     /* ---- stage 1b: reads (compute_hashes, OpenMP over reads as :617) + spectrum (:615-638) */
-    int64_t *r_off = (int64_t *)calloc((size_t)n_reads + 1, 8);
-#pragma omp parallel for schedule(dynamic, 256)
-    for (int64_t r = 0; r < n_reads; r++)
-        r_off[r + 1] = orc_sketch(reads_concat + read_off[r], read_off[r + 1] - read_off[r], k, w, 0, 0, 0);
-    for (int64_t r = 0; r < n_reads; r++) r_off[r + 1] += r_off[r];
-    int64_t sp_n = r_off[n_reads];
-    uint64_t *sp = (uint64_t *)malloc(8 * (size_t)(sp_n + 1));
-#pragma omp parallel for schedule(dynamic, 256)
-    for (int64_t r = 0; r < n_reads; r++)
-        orc_sketch(reads_concat + read_off[r], read_off[r + 1] - read_off[r], k, w, sp + r_off[r], 0, r_off[r + 1] - r_off[r]);
-    free(r_off);
+    int64_t sp_n = 0;
+    uint64_t *sp = sketch_reads_hashes(reads_concat, read_off, n_reads, k, w, &sp_n);
     qsort(sp, (size_t)sp_n, 8, cmp_u64);
     int64_t u = 0;
     for (int64_t i = 0; i < sp_n; i++) if (i == 0 || sp[i] != sp[i - 1]) sp[u++] = sp[i];
@@ -424,3 +435,90 @@ const int64_t *orc_a_pos(const orc_result_t *R) { return R->a_pos; }
 const int64_t *orc_m_off(const orc_result_t *R) { return R->m_off; }
 const uint64_t *orc_m_hash(const orc_result_t *R) { return R->m_hash; }
 const int64_t *orc_m_pos(const orc_result_t *R) { return R->m_pos; }
+
+/* ------------------------------------------------------------------ read spectrum on its own, batch by batch */
+
+/* Sort a[0 .. n) and drop duplicates in place; returns the distinct count.  The hashes are spread evenly over 64 bits, so
+ * the top bits cut them into ranges of nearly equal size: count and scatter over fixed chunks of the input, sort every
+ * range on its own thread, and the ranges in order are the sorted whole. */
+static int64_t sort_unique_u64(uint64_t *a, int64_t n)
+{
+    enum { BITS = 10, P = 1 << BITS, NCH = 64 };
+    int64_t u = 0;
+    if (n < (1 << 16)) {
+        qsort(a, (size_t)n, 8, cmp_u64);
+        for (int64_t i = 0; i < n; i++) if (i == 0 || a[i] != a[i - 1]) a[u++] = a[i];
+        return u;
+    }
+    uint64_t *tmp = (uint64_t *)malloc(8 * (size_t)n);
+    int64_t *cnt = (int64_t *)calloc((size_t)NCH * P, 8);         /* cnt[chunk][range], then the write cursor */
+    int64_t *p_off = (int64_t *)calloc((size_t)P + 1, 8), *p_u = (int64_t *)calloc((size_t)P, 8);
+#pragma omp parallel for schedule(static, 1)
+    for (int c = 0; c < NCH; c++) {
+        int64_t *cc = cnt + (size_t)c * P;
+        for (int64_t i = n * c / NCH; i < n * (c + 1) / NCH; i++) cc[a[i] >> (64 - BITS)]++;
+    }
+    int64_t at = 0;
+    for (int p = 0; p < P; p++) {
+        p_off[p] = at;
+        for (int c = 0; c < NCH; c++) { int64_t m = cnt[(size_t)c * P + p]; cnt[(size_t)c * P + p] = at; at += m; }
+    }
+    p_off[P] = at;
+#pragma omp parallel for schedule(static, 1)
+    for (int c = 0; c < NCH; c++) {
+        int64_t *cc = cnt + (size_t)c * P;
+        for (int64_t i = n * c / NCH; i < n * (c + 1) / NCH; i++) tmp[cc[a[i] >> (64 - BITS)]++] = a[i];
+    }
+#pragma omp parallel for schedule(dynamic, 1)
+    for (int p = 0; p < P; p++) {
+        uint64_t *b = tmp + p_off[p];
+        int64_t m = p_off[p + 1] - p_off[p], v = 0;
+        qsort(b, (size_t)m, 8, cmp_u64);
+        for (int64_t i = 0; i < m; i++) if (i == 0 || b[i] != b[i - 1]) b[v++] = b[i];
+        p_u[p] = v;
+    }
+    for (int p = 0; p < P; p++) { memcpy(a + u, tmp + p_off[p], 8 * (size_t)p_u[p]); u += p_u[p]; }
+    free(tmp); free(cnt); free(p_off); free(p_u);
+    return u;
+}
+
+/* Stage 1b alone (ILP_index.cpp:615-638), fed in batches: the distinct hashes so far, sorted, and the emitted count. */
+typedef struct { uint64_t *sp; int64_t u, n_emitted; } orc_spectrum_t;
+
+orc_spectrum_t *orc_spectrum_new(void) { return (orc_spectrum_t *)calloc(1, sizeof(orc_spectrum_t)); }
+
+void orc_spectrum_add_reads(orc_spectrum_t *S, const char *reads_concat, const int64_t *read_off, int64_t n_reads, int k, int w)
+{
+    int64_t n = 0;
+    uint64_t *b = sketch_reads_hashes(reads_concat, read_off, n_reads, k, w, &n);
+    S->n_emitted += n;
+    int64_t bu = sort_unique_u64(b, n);
+    if (!S->sp) { S->sp = b; S->u = bu; return; }
+    /* union of two sorted duplicate-free lists */
+    uint64_t *m = (uint64_t *)malloc(8 * (size_t)(S->u + bu + 1));
+    int64_t i = 0, j = 0, o = 0;
+    while (i < S->u && j < bu) {
+        uint64_t x = S->sp[i], y = b[j];
+        m[o++] = x < y ? x : y;
+        i += x <= y; j += y <= x;
+    }
+    while (i < S->u) m[o++] = S->sp[i++];
+    while (j < bu) m[o++] = b[j++];
+    free(S->sp); free(b);
+    S->sp = m; S->u = o;
+}
+
+/* Sorted distinct hashes (owned by the accumulator until orc_spectrum_free) and their number; *n_emitted = every
+ * minimiser the reads emitted, repeats included. */
+int64_t orc_spectrum_finish(const orc_spectrum_t *S, const uint64_t **hashes, int64_t *n_emitted)
+{
+    if (hashes) *hashes = S->sp;
+    if (n_emitted) *n_emitted = S->n_emitted;
+    return S->u;
+}
+
+void orc_spectrum_free(orc_spectrum_t *S)
+{
+    if (!S) return;
+    free(S->sp); free(S);
+}

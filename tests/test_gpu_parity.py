@@ -1249,14 +1249,23 @@ def test_full_size_vs_oracle(oracle, ctx_factory, monkeypatch, config):
     with the reads scored by the one-chunk kernel AND by the pooled kernel (PHI_SKETCH_POOL_MIN picks; the default is
     the one-chunk kernel below 12.6 Mbases per batch), handed over whole and in three batches.  C2r = C2's model over REAL
     sequence (the CHM13 MHC contig of the reference's test data as the backbone: low complexity, tandem repeats)."""
-    import torch
-    from phi_amd import dist as pdist
     from phi_amd import synth
     gk, rk = synth.CONFIGS[config]
     g = synth.make_graph(**gk)
     bases, off, truth = synth.make_reads(g, **rk)
+    _stage12_vs_oracle(oracle, ctx_factory, monkeypatch, g, bases, off)
+
+
+def _stage12_vs_oracle(oracle, ctx_factory, monkeypatch, g, bases, off):
+    """What test_full_size_vs_oracle and test_chromosome_scale_vs_oracle[C5n-mid] check (see the former's docstring), for a
+    graph and a read set the oracle holds whole.  Returns wall times: the oracle's run, the rest."""
+    import time
+    import torch
+    from phi_amd import dist as pdist
+    t_all = time.perf_counter()
     A = g.arrays()
     st = oracle.run_stage12_arrays(A, bases, off, 31, 25, 1.0)
+    t_oracle = time.perf_counter() - t_all
     all_walk_hashes = np.unique(st.m_hash)
     want_missing = st.spectrum[~np.isin(st.spectrum, all_walk_hashes)]
     want_kept = _sorted_anchor_table(st.spectrum[st.a_r], st.a_h, st.a_t0, st.a_t1)
@@ -1293,17 +1302,19 @@ def test_full_size_vs_oracle(oracle, ctx_factory, monkeypatch, config):
                 assert np.array_equal(gp, st.m_pos[lo:hi]), f"walk {h} positions"
         assert res["optimal"] == 1
         ctx.close()
+    return {"oracle_s": t_oracle, "oracle_stage_s": list(st.stage_s), "rest_s": time.perf_counter() - t_all - t_oracle,
+            "spectrum_size": len(st.spectrum), "n_kept_anchors": len(st.a_r), "n_walk_minimizers": int(st.m_off[-1])}
 
 
 @pytest.mark.parametrize("config", ["C2", "C3", "C4", "C5s", "C2r"])
-def test_full_size_properties(ctx_factory, config):
+def test_full_size_properties(oracle, ctx_factory, config):
     """At the sizes of BASELINE.json's configurations (synMHC-49: 49 walks x 5.2 Mbp with 1x / 10x short reads
     and 5x long noisy reads; 200 walks with 30x reads at the MHC's length) the CPU oracle checks stages 1-2
     (test_full_size_vs_oracle); no CPU solver finishes the exact solve at these sizes, and
     the domain's size-independent properties stand in for it: the read set is a SET of canonical k-mers (order,
     strand, batching and repetition of reads change nothing), the solve carries its own certificate
     (objective == proven bound), the path's objective is recounted in numpy from the kept anchors, the
-    per-walk minimisers of the index equal a direct sketch of the walk's sequence, and the generator's truth
+    per-walk minimisers of the index equal the CPU oracle's sketch of the walk's sequence, and the generator's truth
     walks come back."""
     from phi_amd import synth
     gk, rk = synth.CONFIGS[config]
@@ -1326,7 +1337,7 @@ def test_full_size_properties(ctx_factory, config):
             # two walks of the index against the stand-alone sketch of their sequences
             for h in (0, g.n_walks - 1):
                 wh, wp = ctx.walk_minimizers(h)
-                sh, sp, _ = ctx.sketch([g.walk_sequence(h).tobytes()], 31, 25)
+                sh, sp = oracle.sketch(g.walk_sequence(h).tobytes(), 31, 25)
                 assert np.array_equal(wh, sh) and np.array_equal(wp, sp)
                 assert len(wh) == res["n_minimizers"][h]
             seq = ctx.path_sequence(res["hap_len"])
@@ -1416,12 +1427,12 @@ def test_native_generator_small_vs_oracle_and_highs(oracle, ctx_factory):
 
 
 @pytest.mark.parametrize("config", ["C5n-mid", "C5"])
-def test_chromosome_scale_properties(ctx_factory, config):
+def test_chromosome_scale_properties(oracle, ctx_factory, config):
     """BASELINE.json's config 5 (synthetic 200-walk chr6-scale GFA, 30x reads) from the native generator, at a
     tenth of its size and at its stated size (170 Mbp backbone: 34 Gbases of walks, 1.2 G walk entries, 5.1 Gbases
     of reads).  Size-independent properties: the solve's certificate, the numpy recount of the path's objective
-    from the kept anchors, truth walks recovered, per-walk minimisers of the de-duplicated index against a direct
-    sketch of a walk's sequence, and batch-order independence (the reads in three batches, last batch first)."""
+    from the kept anchors, truth walks recovered, per-walk minimisers of the de-duplicated index against the CPU
+    oracle's sketch of a walk's sequence, and batch-order independence (the reads in three batches, last batch first)."""
     from phi_amd import synth
     gk, s_seed, n_mosaic, r_seed, cov = synth.NATIVE_CONFIGS[config]
     g = synth.NativeGraph(**gk)
@@ -1449,7 +1460,7 @@ def test_chromosome_scale_properties(ctx_factory, config):
             del kept
             h = g.n_walks - 1
             wh, wp = ctx.walk_minimizers(h)
-            sh, sp, _ = ctx.sketch([g.walk_sequence(h).tobytes()], 31, 25)
+            sh, sp = oracle.sketch(g.walk_sequence(h).tobytes(), 31, 25)
             assert np.array_equal(wh, sh) and np.array_equal(wp, sp) and len(wh) == res["n_minimizers"][h]
         ctx.close()
         hap = res["path_hap"]
@@ -1461,6 +1472,157 @@ def test_chromosome_scale_properties(ctx_factory, config):
     assert base[0][2] == 1 and base[0][0] == base[0][1]              # proven optimal
     assert base[1] == truth["walks"]                                  # the mosaic is recovered
     assert solve([2, 0, 1], False) == base                            # the reads in another order of batches
+
+
+def _oracle_walk_sketches(oracle, g, walks, k, w):
+    """{h: (hash, position)} of the oracle's sketch of whole walk sequences, one walk per thread (at most 16)."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    def one(h):
+        return oracle.sketch(g.walk_sequence(h).tobytes(), k, w)
+    with ThreadPoolExecutor(max_workers=max(1, min(16, len(walks)))) as pool:
+        return dict(zip(walks, pool.map(one, walks)))
+
+
+@pytest.mark.parametrize("config", ["C5n-mid", "C5"])
+def test_chromosome_scale_vs_oracle(oracle, ctx_factory, monkeypatch, config):
+    """BASELINE.json's config 5 from the native generator against the CPU oracle.
+
+    C5n-mid (a tenth: 20-Mbp backbone, 200 walks, 4 Gbases of walks) fits the oracle whole and gets everything
+    test_full_size_vs_oracle checks.
+
+    C5 at its stated size (170-Mbp backbone, 1.2 G walk entries, 35 M reads) gets the parts the oracle can hold:
+      * walks: the first, the last (the highest entries), the one holding entry n_entries // 2 and the three truth walks:
+        (hash, position) of ctx.walk_minimizers against oracle.sketch of the walk's sequence, the per-walk count of the
+        solve, and every hash a key of the read table;
+      * reads: the whole read spectrum, element for element (spectrum_check: hit keys + novel list == the oracle's
+        spectrum as sets, emitted count, the read table's structure), the reads fed in thirds to the context and to the
+        oracle's accumulator;
+      * every route: the same thirds scored again after reset_reads() by the generic window kernel
+        (PHI_SKETCH_WIN_FIXED=0) and in base space by the pooled kernel (PHI_SKETCH_WINDOWS=0, PHI_SKETCH_POOL_MIN=1); the
+        first pass takes what the environment selects, the fixed-geometry window kernel by default.
+    Not compared at C5: the other 194 walks, the kept anchors, the filter's counters (test_chromosome_scale_properties
+    recounts the objective from the kept anchors).  PHI_C5_ORACLE_TIMES names a file that receives the wall times."""
+    import time
+    import spectrum_check as sc
+    from phi_amd import synth
+    gk, s_seed, n_mosaic, r_seed, cov = synth.NATIVE_CONFIGS[config]
+    g = synth.NativeGraph(**gk)
+    truth = g.sample(s_seed, n_mosaic)
+    n = g.n_reads(cov)
+    A = g.arrays()
+    # the native graph's arrays are views of the library's memory: what the oracle and the context take without a copy
+    for name, dt in (("seq_concat", np.uint8), ("seq_off", np.int64), ("walk_off", np.int64), ("walk_vtx", np.int32)):
+        assert A[name].dtype == dt and A[name].flags.c_contiguous, name
+    for v in ("PHI_SKETCH_WINDOWS", "PHI_SKETCH_WIN_FIXED", "PHI_SKETCH_POOL_MIN", "PHI_SKETCH_WAVES", "PHI_READ_TABLE_BUCKETS"):
+        monkeypatch.delenv(v, raising=False)
+    times = {"config": config}
+    t_test = time.perf_counter()
+
+    def progress(stage):                              # (seen with pytest -s: the stages of the large case take minutes)
+        print(f"[{config}] {stage}: {time.perf_counter() - t_test:.1f} s", flush=True)
+    if config != "C5":
+        bases, off = g.reads(r_seed, 0, n)
+        times.update(_stage12_vs_oracle(oracle, ctx_factory, monkeypatch, g, bases, off))
+    else:
+        k, w = 31, 25
+        cuts = [0, n // 3, 2 * n // 3, n]
+        t0 = time.perf_counter()
+        ctx = ctx_factory(k=k, w=w, threshold=1.0, recombination=100)
+        ctx.set_graph(A["seq_concat"], A["seq_off"], A["adj_off"], A["adj"], A["walk_off"], A["walk_vtx"], A["top_rank"])
+        times["set_graph_s"] = time.perf_counter() - t0
+        progress("set_graph")
+        acc = oracle.SpectrumAccumulator(k, w)
+        thirds = []                                   # kept on the host (5.3 GB) for the three routes of this test only
+        times["generate_reads_s"] = times["add_reads_s"] = times["oracle_reads_s"] = 0.0
+        for a, b in zip(cuts[:-1], cuts[1:]):
+            t0 = time.perf_counter()
+            third = g.reads(r_seed, a, b)
+            t1 = time.perf_counter()
+            ctx.add_reads(third)
+            ctx.device_synchronize()
+            t2 = time.perf_counter()
+            acc.add(*third)
+            t3 = time.perf_counter()
+            thirds.append(third)
+            times["generate_reads_s"] += t1 - t0
+            times["add_reads_s"] += t2 - t1
+            times["oracle_reads_s"] += t3 - t2
+            progress("a third of the reads scored and sketched")
+        t0 = time.perf_counter()
+        S, n_emitted = acc.finish()
+        times["oracle_reads_s"] += time.perf_counter() - t0
+        times["spectrum_size"], times["n_emitted"] = len(S), int(n_emitted)
+        n_bases = sum(len(b) for b, _ in thirds)
+        assert n_bases == n * 150
+
+        def solve_and_check(route, table):
+            t0 = time.perf_counter()
+            res = ctx.solve()
+            t1 = time.perf_counter()
+            keys, ids, n_hit = sc.check_context(ctx, S, n_emitted, n, n_bases, res["spectrum_size"], table)
+            times[f"solve_{route}_s"], times[f"compare_{route}_s"] = t1 - t0, time.perf_counter() - t1
+            progress(f"read side compared, route {route}")
+            return res, (keys, ids), n_hit
+        res, table, n_hit = solve_and_check("default", None)
+        times["n_table_keys"], times["n_table_buckets"], times["n_hit_keys"] = len(table[0]), ctx.read_table()[1], n_hit
+        assert res["optimal"] == 1 and res["objective"] == res["upper_bound"]
+        hap = res["path_hap"]
+        assert [int(x) for x in hap[np.r_[True, hap[1:] != hap[:-1]]]] == truth["walks"]
+        base_key = tuple(int(res[f]) for f in ("objective", "spectrum_size", "filtered", "retained", "n_in_model", "n_covered", "hap_len"))
+        # ---- walks
+        n_entries = len(A["walk_vtx"])
+        assert ctx.index_stats()["n_entries"] == n_entries
+        mid = int(np.searchsorted(A["walk_off"], n_entries // 2, side="right")) - 1
+        walks = sorted({0, g.n_walks - 1, mid, *truth["walks"]})
+        assert len(walks) >= 3 and A["walk_off"][mid] <= n_entries // 2 < A["walk_off"][mid + 1]
+        t0 = time.perf_counter()
+        want = _oracle_walk_sketches(oracle, g, walks, k, w)
+        times["oracle_walks_s"], times["walks"] = time.perf_counter() - t0, walks
+        progress("walks sketched by the oracle")
+        t0 = time.perf_counter()
+        sorted_keys = np.sort(table[0])
+        for h in walks:
+            oh, op = want[h]
+            gh, gp = ctx.walk_minimizers(h)
+            assert np.array_equal(gh, oh), f"walk {h} hashes"
+            assert np.array_equal(gp, op), f"walk {h} positions"
+            assert res["n_minimizers"][h] == len(oh) > 0
+            assert sc._is_member(sorted_keys, np.sort(oh)).all(), f"walk {h}: a minimiser that is no key of the read table"      # (sorted: the lookups walk the keys in order)
+        del want, sorted_keys
+        times["compare_walks_s"] = time.perf_counter() - t0
+        # ---- the other routes, in the same context after a reset
+        for route, env in (("win_generic", {"PHI_SKETCH_WIN_FIXED": "0"}),
+                           ("base_pooled", {"PHI_SKETCH_WINDOWS": "0", "PHI_SKETCH_POOL_MIN": "1"})):
+            for kk, vv in env.items():
+                monkeypatch.setenv(kk, vv)
+            t0 = time.perf_counter()
+            ctx.reset_reads()
+            assert ctx.reads_stats() == dict(n_reads=0, n_bases=0, n_emitted=0, n_distinct=0)
+            for third in thirds:
+                ctx.add_reads(third)
+            ctx.device_synchronize()
+            times[f"add_reads_{route}_s"] = time.perf_counter() - t0
+            res2, _, n_hit2 = solve_and_check(route, table)
+            for kk in env:
+                monkeypatch.delenv(kk)
+            assert n_hit2 == n_hit
+            assert tuple(int(res2[f]) for f in ("objective", "spectrum_size", "filtered", "retained", "n_in_model", "n_covered", "hap_len")) == base_key
+            assert np.array_equal(res2["n_anchors"], res["n_anchors"]) and np.array_equal(res2["n_minimizers"], res["n_minimizers"])
+        ctx.close()
+        times["oracle_s"] = times["oracle_reads_s"] + times["oracle_walks_s"]
+        times["gpu_side_s"] = (times["set_graph_s"] + times["generate_reads_s"] + times["add_reads_s"] + times["add_reads_win_generic_s"]
+                               + times["add_reads_base_pooled_s"] + sum(v for f, v in times.items() if f.startswith("solve_")))
+    times["test_s"] = time.perf_counter() - t_test
+    try:
+        import resource
+        times["peak_rss_gb"] = resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 2 ** 20
+    except ImportError:
+        pass
+    print("chromosome_scale_vs_oracle", json.dumps(times))
+    if os.environ.get("PHI_C5_ORACLE_TIMES"):
+        with open(os.environ["PHI_C5_ORACLE_TIMES"], "a") as f:
+            f.write(json.dumps(times) + "\n")
 
 
 @pytest.mark.parametrize("pooled", [False, True])

@@ -10,6 +10,7 @@ for the keys, which raises the table-full flag and is built again at twice the b
 import numpy as np
 import pytest
 
+import spectrum_check
 from graphgen import mosaic_reads, random_graph, walk_sequence
 
 pytestmark = pytest.mark.gpu
@@ -144,6 +145,9 @@ def test_read_table_layout_and_hits_of_every_read_kernel(oracle, ctx_factory, mo
             p, m = ctx.spectrum_export()
             sp = torch.as_tensor(pdist.DevArray(p, m, "<i8"), device="cuda").clone().cpu().numpy().view(np.uint64)
             assert np.array_equal(np.sort(sp), want_missing), (name, lay)
+            # the same through the vectorised helper of the chromosome-scale tests (its decode against _check_table's)
+            keys, ids, _ = spectrum_check.check_context(ctx, read_h, sum(len(x) for x in sk), len(reads), sum(len(r) for r in reads), len(read_h))
+            assert np.array_equal(uniq[ids], keys)
             ctx.close()
         for lay, hits in hits_of.items():
             assert np.array_equal(hits, want_hits), (name, lay)
