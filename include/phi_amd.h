@@ -20,7 +20,8 @@
  * at most 2^32 - 64 walk entries (2.5 G solved: profiles/wide_entries.py), fewer than 2^31 minimisers of the distinct walk
  * contexts, anchors in the model and walk entries on vertices with recombination edges, at most
  * 254 out-edges and 255 recombination in-edges per vertex, no walk through a segment without
- * sequence, no graph whose walks both start and end at interior vertices.
+ * sequence, no graph whose walks both start and end at interior vertices.  phi_set_graph_chopped: the same limits hold
+ * for the CHOPPED graph (at most 2^31 - 1 pieces, at most 2^32 - 64 chopped walk entries).
  */
 #ifndef PHI_AMD_H
 #define PHI_AMD_H
@@ -84,6 +85,41 @@ int phi_set_params(phi_ctx *ctx, int32_t k, int32_t w, float threshold, int32_t 
 int phi_set_graph(phi_ctx *ctx, int32_t n_vtx, const char *seq_concat, const int64_t *seq_off,
                   const int64_t *adj_off, const int32_t *adj, int32_t n_walks,
                   const int64_t *walk_off, const int32_t *walk_vtx, const int32_t *topo_rank);
+
+/*
+ * The same with the graph chopped first (data/chop_graph.sh:3 `hal2vg --chop 30`, :62 `gfa2gbwt -m 30`: the reference's
+ * pipeline never hands PHI a graph as the builder wrote it, since the model switches haplotypes at vertex borders only and
+ * ignores anchors inside one vertex).  A vertex of L bases becomes max(1, ceil(L / max_len)) pieces, full pieces first;
+ * the pieces of vertex v get the consecutive ids first[v] + j (first = exclusive prefix sum of the piece counts in vertex
+ * order); edges piece j -> j + 1, and last piece of u -> first piece of v for every edge (u, v), a vertex's out-edges in
+ * their order; topological rank = prefix sum of the counts in topological order + j; every walk entry is replaced by its
+ * vertex's pieces.  The per-vertex arrays are chopped on the host, the walk entries on the device (chop.hip): walk_vtx may
+ * be host entries (uploaded unchopped) or NULL after phi_walk_text_resolve (expanded where they lie).  walk_off_out
+ * [n_walks + 1] (may be NULL) receives the chopped walks' offsets.  max_len < 1: PHI_ERR_INVALID.  More than 2^31 - 1
+ * pieces or more than 2^32 - 64 chopped entries: PHI_ERR_UNSUPPORTED, decided from the counts before the chopped entries
+ * are allocated; the context stays usable.  Whatever phi_set_graph refuses is refused the same way (vertex ids in such a
+ * message are the chopped graph's); on failure the context holds no graph.  max_len >= the longest vertex: the graph as
+ * passed in, same ids, same result as phi_set_graph.  Everything downstream (phi_solve's path_vtx, phi_kept_anchors, ...)
+ * speaks of the chopped graph.
+ */
+int phi_set_graph_chopped(phi_ctx *ctx, int32_t n_vtx, const char *seq_concat, const int64_t *seq_off,
+                          const int64_t *adj_off, const int32_t *adj, int32_t n_walks,
+                          const int64_t *walk_off, const int32_t *walk_vtx, const int32_t *topo_rank,
+                          int32_t max_len, int64_t *walk_off_out);
+/* data/chop_graph.sh:3,62 undone for reporting: chopped vertex id vtx[i] -> the vertex as passed to phi_set_graph_chopped
+ * (orig_vtx[i]) and the base offset of the piece inside it (orig_off[i]); either output may be NULL.  PHI_ERR_STATE when
+ * the context's graph was not set chopped, PHI_ERR_INVALID for an id outside the chopped graph. */
+int phi_chop_origin(phi_ctx *ctx, const int32_t *vtx, int64_t n, int32_t *orig_vtx, int32_t *orig_off);
+/* What the chop (data/chop_graph.sh:3,62) did: vertices and walk entries before and after, and expand_gpu_ms = count + scan +
+ * expand of the walk entries by HIP events on the context's stream (0 when nothing had to be chopped).  PHI_ERR_STATE when
+ * the context's graph was not set chopped. */
+typedef struct {
+    int64_t n_vtx_in, n_vtx_out;
+    int64_t n_entries_in, n_entries_out;
+    int32_t max_len;
+    double expand_gpu_ms;
+} phi_chop_info;
+int phi_chop_stats(phi_ctx *ctx, phi_chop_info *out);
 
 /*
  * Stage 1b/2a of ILP_function (:617-655) for one batch of reads: sketch, spectrum insert,

@@ -32,6 +32,7 @@ SYMBOLS = [
     "phi_inflate", "phi_inflate_alloc", "phi_inflate_free", "phi_gzip_header", "phi_crc32_combine",
     "phi_text_park_gzip_begin", "phi_text_park_gzip_add", "phi_text_park_gzip_end",
     "phi_gfa_gzip_split", "phi_gfa_gzip_free",
+    "phi_set_graph_chopped", "phi_chop_origin", "phi_chop_stats",
 ]
 PHI_INFLATE_NO_FINDER = 1
 PHI_INFLATE_CHUNK_DEFAULT = 64 << 10          # include/phi_amd.h
@@ -45,6 +46,11 @@ class PhiIndexInfo(C.Structure):
 class PhiSolveInfo(C.Structure):
     _fields_ = [("n_dp_anchors", C.c_int64), ("n_events", C.c_int64), ("n_steps", C.c_int32), ("n_blocks", C.c_int32),
                 ("dp_mode", C.c_int32), ("max_classes", C.c_int32), ("mean_classes", C.c_double)]
+
+
+class PhiChopInfo(C.Structure):
+    _fields_ = [("n_vtx_in", C.c_int64), ("n_vtx_out", C.c_int64), ("n_entries_in", C.c_int64), ("n_entries_out", C.c_int64),
+                ("max_len", C.c_int32), ("expand_gpu_ms", C.c_double)]
 
 
 class PhiResult(C.Structure):
@@ -91,6 +97,9 @@ def load():
     L.phi_set_stream.argtypes = [vp, vp]
     L.phi_set_params.argtypes = [vp, i32, i32, C.c_float, i32, C.c_uint32]
     L.phi_set_graph.argtypes = [vp, i32, vp, vp, vp, vp, i32, vp, vp, vp]
+    L.phi_set_graph_chopped.argtypes = [vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, vp]
+    L.phi_chop_origin.argtypes = [vp, vp, i64, vp, vp]
+    L.phi_chop_stats.argtypes = [vp, C.POINTER(PhiChopInfo)]
     L.phi_add_reads.argtypes = [vp, vp, vp, i64]
     L.phi_add_reads_device.argtypes = [vp, vp, vp, i64, i64]
     L.phi_reset_reads.argtypes = [vp]

@@ -65,8 +65,10 @@ class Context:
         self._chk(self._L.phi_set_params(self._h, k, w, C.c_float(threshold), recombination, flags))
         self.k, self.w = k, w
 
-    def set_graph(self, seq_concat, seq_off, adj_off, adj, walk_off, walk_vtx, top_rank):
-        """Arrays of phi_set_graph: bytes + int64/int32 numpy arrays."""
+    def set_graph(self, seq_concat, seq_off, adj_off, adj, walk_off, walk_vtx, top_rank, chop=None):
+        """Arrays of phi_set_graph: bytes + int64/int32 numpy arrays.  chop=N: every vertex is first cut into pieces of at
+        most N bases (phi_set_graph_chopped: what `hal2vg --chop N` does in the reference's pipeline); returns the chopped
+        walks' offsets, and path_vtx, kept_anchors ... then speak of the chopped graph (chop_origin maps back)."""
         seq_off = np.ascontiguousarray(seq_off, np.int64)
         adj_off = np.ascontiguousarray(adj_off, np.int64)
         adj = np.ascontiguousarray(adj, np.int32)
@@ -75,8 +77,28 @@ class Context:
         top_rank = np.ascontiguousarray(top_rank, np.int32)
         buf = np.frombuffer(seq_concat, np.uint8) if not isinstance(seq_concat, np.ndarray) else seq_concat
         self.n_vtx, self.n_walks = len(seq_off) - 1, len(walk_off) - 1
+        if chop is not None:
+            walk_off_out = np.zeros(self.n_walks + 1, np.int64)
+            self._chk(self._L.phi_set_graph_chopped(self._h, self.n_vtx, _ptr(buf), _ptr(seq_off), _ptr(adj_off), _ptr(adj),
+                                                    self.n_walks, _ptr(walk_off), _ptr(walk_vtx), _ptr(top_rank), int(chop),
+                                                    _ptr(walk_off_out)))
+            return walk_off_out
         self._chk(self._L.phi_set_graph(self._h, self.n_vtx, _ptr(buf), _ptr(seq_off), _ptr(adj_off), _ptr(adj),
                                         self.n_walks, _ptr(walk_off), _ptr(walk_vtx), _ptr(top_rank)))
+        return None
+
+    def chop_origin(self, vtx):
+        """Chopped vertex ids -> (vertex as passed to set_graph(chop=N), base offset of the piece inside it)."""
+        vtx = np.ascontiguousarray(vtx, np.int32)
+        ov, oo = np.zeros(len(vtx), np.int32), np.zeros(len(vtx), np.int32)
+        self._chk(self._L.phi_chop_origin(self._h, _ptr(vtx), len(vtx), _ptr(ov), _ptr(oo)))
+        return ov, oo
+
+    def chop_stats(self):
+        """What set_graph(chop=N) did: vertices and walk entries before and after, N, GPU time of the expansion."""
+        r = _capi.PhiChopInfo()
+        self._chk(self._L.phi_chop_stats(self._h, C.byref(r)))
+        return {n: getattr(r, n) for n, _ in _capi.PhiChopInfo._fields_}
 
     def index_stats(self):
         """Sizes of the de-duplicated walk index (classes of walk entries with equal context) and its GPU time."""

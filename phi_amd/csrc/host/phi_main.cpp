@@ -130,6 +130,7 @@ static void usage(FILE *fp, int k, int w, int R, int q, int m, float T, int t, c
 struct Options {
     int k = 31, w = 25, n_threads = 4, recombination = 100, is_qclp = 1, is_naive = 0, is_mixed = 1, debug = 0;
     int device = 0, max_occ = 5000;
+    int chop = 0;                                             // --chop N: segments cut into pieces of at most N bases inside "set graph" (data/chop_graph.sh:3)
     std::vector<int> devices;                                 // --devices: one context (and host thread) per GPU
     long long dp_budget = -1;                                 // --dp-budget: DP runs of the exact search; not given: no limit, as model.optimize()
     long long shard_min_bases = 50000000;                     // --shard-min-bases: text bytes of reads a further GPU must be worth
@@ -575,15 +576,26 @@ struct Driver {
     {
         const uint32_t flags = (o.is_qclp ? PHI_FLAG_QCLP : 0) | (o.is_mixed ? PHI_FLAG_MIXED : 0);
         Stage st("phi_set_graph (index build)");
-        return run_on_all("graph", [&](int, phi_ctx *cx) -> int {
+        const int rc = run_on_all("graph", [&](int, phi_ctx *cx) -> int {
             int r = phi_set_params(cx, o.k, o.w, o.threshold, o.recombination, flags);
             // the reference's model.optimize() has no limit (ILP_index.cpp:1412-1418): none here unless --dp-budget asks for one
             if (!r) r = phi_set_solve_budget(cx, o.dp_budget >= 0 ? o.dp_budget : 0);
-            if (!r) r = phi_set_graph(cx, phi_graph_n_vtx(g), phi_graph_seq_concat(g), phi_graph_seq_off(g), phi_graph_adj_off(g),
-                                      phi_graph_adj(g), phi_graph_n_walks(g), phi_graph_walk_off(g), phi_graph_walk_vtx(g), phi_graph_topo_rank(g));
+            if (!r && o.chop)
+                r = phi_set_graph_chopped(cx, phi_graph_n_vtx(g), phi_graph_seq_concat(g), phi_graph_seq_off(g), phi_graph_adj_off(g), phi_graph_adj(g),
+                                          phi_graph_n_walks(g), phi_graph_walk_off(g), phi_graph_walk_vtx(g), phi_graph_topo_rank(g), o.chop, nullptr);
+            else if (!r)
+                r = phi_set_graph(cx, phi_graph_n_vtx(g), phi_graph_seq_concat(g), phi_graph_seq_off(g), phi_graph_adj_off(g),
+                                  phi_graph_adj(g), phi_graph_n_walks(g), phi_graph_walk_off(g), phi_graph_walk_vtx(g), phi_graph_topo_rank(g));
             if (r == PHI_ERR_WALK && n_dev == 1) fprintf(stderr, "Error: %s\n", phi_last_error(cx));
             return r;
         });
+        phi_chop_info ci;
+        if (!rc && o.chop && !phi_chop_stats(ctx, &ci)) {
+            stamp("main");
+            fprintf(stderr, "Graph chopped to %d bases: %lld -> %lld vertices, %lld -> %lld walk entries\n", ci.max_len, (long long)ci.n_vtx_in,
+                    (long long)ci.n_vtx_out, (long long)ci.n_entries_in, (long long)ci.n_entries_out);
+        }
+        return rc;
     }
     // The exchange of a multi-GPU run: the library's RCCL all-reduce.  PHI_EXCHANGE=peers takes the peer-mapped OR-gather
     // instead (one kernel per GPU, no RCCL: made for hit vectors of a few MB, every MHC-sized graph) -- opt-in until a run on
@@ -728,9 +740,17 @@ struct Driver {
         const int64_t *so = phi_graph_seq_off(g);
         int64_t str_id = 0, prev_str_id = 0;
         int32_t prev_hap = res.n_path ? res.path_hap[0] : 0;
+        // --chop: the path's vertices are pieces; their segments and offsets, so that the lengths come from g's segments
+        std::vector<int32_t> seg, at;
+        if (o.chop) {
+            seg.resize((size_t)res.n_path); at.resize((size_t)res.n_path);
+            const int rc = phi_chop_origin(ctx, res.path_vtx, res.n_path, seg.data(), at.data());
+            if (rc) { fprintf(stderr, "\n[E::main] recombination report: %s: %s\n", phi_strerror(rc), phi_last_error(ctx)); return; }
+        }
         for (int64_t i = 0; i < res.n_path; i++) {
-            const int32_t v = res.path_vtx[i];
-            str_id += so[v + 1] - so[v];                      // (the reference adds the vertex length before testing the label: :1515-1523)
+            const int32_t v = o.chop ? seg[(size_t)i] : res.path_vtx[i];
+            const int64_t len = o.chop ? std::max<int64_t>(0, std::min<int64_t>(o.chop, so[v + 1] - so[v] - at[(size_t)i])) : so[v + 1] - so[v];
+            str_id += len;                                    // (the reference adds the vertex length before testing the label: :1515-1523)
             if (i > 0 && res.path_hap[i] != prev_hap) {
                 fprintf(stderr, ">(%s,[%lld,%lld])", phi_graph_hap_name(g, prev_hap), (long long)prev_str_id, (long long)(str_id - 1));
                 prev_hap = res.path_hap[i]; prev_str_id = str_id;
@@ -866,7 +886,7 @@ int main(int argc, char *argv[])
     Options o;
     int help = 0;
     static struct option long_options[] = {{"version", no_argument, 0, 300}, {"device", required_argument, 0, 301}, {"dp-budget", required_argument, 0, 302},
-                                           {"devices", required_argument, 0, 303}, {"shard-min-bases", required_argument, 0, 304}, {0, 0, 0, 0}};
+                                           {"devices", required_argument, 0, 303}, {"shard-min-bases", required_argument, 0, 304}, {"chop", required_argument, 0, 305}, {0, 0, 0, 0}};
     int c;
     // main.cpp:38 declares -h with an argument; a bare -h falls into the usage branch either way
     while ((c = getopt_long(argc, argv, "x:d:c:l:s:m:R:q:T:N:h:k:w:t:g:r:o:DS", long_options, nullptr)) >= 0) {
@@ -887,6 +907,7 @@ int main(int argc, char *argv[])
         else if (c == 300) { fprintf(stderr, "PHI version: %s\n", PHI_VERSION); return 0; }
         else if (c == 301) o.device = atoi(optarg);
         else if (c == 302) o.dp_budget = atoll(optarg);
+        else if (c == 305) { o.chop = atoi(optarg); if (o.chop < 1) { fprintf(stderr, "[E::main] --chop takes a segment length of at least 1\n"); return 1; } }
         else if (c == 304) o.shard_min_bases = std::max<long long>(1, atoll(optarg));
         else if (c == 303) {                                   // --devices 0,1,2,...: shard the reads over these GPUs
             o.devices.clear();

@@ -774,11 +774,12 @@ static int build_classes(phi_ctx *c, int32_t n_vtx, int32_t n_walks, int64_t n_e
 
 extern "C" {
 
-int phi_set_graph(phi_ctx *c, int32_t n_vtx, const char *seq_concat, const int64_t *seq_off, const int64_t *adj_off,
-                  const int32_t *adj, int32_t n_walks, const int64_t *walk_off, const int32_t *walk_vtx,
-                  const int32_t *topo_rank)
+// What phi_set_graph and phi_set_graph_chopped check before anything else, with the same words: the arguments, the state
+// the device-resident walks need (this clears the graph the context held), then the offset arrays both index with.
+static int set_graph_check_args(phi_ctx *c, int32_t n_vtx, const char *seq_concat, const int64_t *seq_off, const int64_t *adj_off,
+                                const int32_t *adj, int32_t n_walks, const int64_t *walk_off, const int32_t *walk_vtx,
+                                const int32_t *topo_rank)
 {
-    if (!c) return PHI_ERR_INVALID;
     // walk_vtx == NULL: the entries are on the device already, resolved there from the W-lines' text (phi_walk_text_resolve)
     const bool dev_walks = walk_vtx == nullptr;
     if (dev_walks && c && walk_off && n_walks > 0 && !(c->walks_on_device && c->walks_on_device_n == walk_off[n_walks] && (int32_t)(c->wtext.ends.size() / 2) == n_walks))
@@ -789,7 +790,29 @@ int phi_set_graph(phi_ctx *c, int32_t n_vtx, const char *seq_concat, const int64
     HIPCHK(hipSetDevice(c->device));
     if (c->ipc) return phi_fail(c, PHI_ERR_STATE, "phi_set_graph on a context in a group of processes: phi_ipc_destroy first (the peers have this context's hit vectors mapped)");
     c->have_graph = false;
+    c->chop.on = false;
     c->solved = false;
+    return PHI_OK;
+}
+static int set_graph_check_offsets(phi_ctx *c, int32_t n_vtx, const int64_t *seq_off, const int64_t *adj_off, int32_t n_walks, const int64_t *walk_off)
+{
+    if (seq_off[0] != 0 || adj_off[0] != 0 || walk_off[0] != 0) return phi_fail(c, PHI_ERR_INVALID, "offset arrays must start at 0");
+    for (int32_t v = 0; v < n_vtx; v++)
+        if (seq_off[v + 1] < seq_off[v] || adj_off[v + 1] < adj_off[v]) return phi_fail(c, PHI_ERR_INVALID, "offsets not monotone at vertex %d", v);
+    for (int32_t h = 0; h < n_walks; h++)
+        if (walk_off[h + 1] <= walk_off[h]) return phi_fail(c, PHI_ERR_INVALID, "walk %d is empty", h);
+    if (walk_off[n_walks] > PHI_MAX_ENTRIES) return phi_fail(c, PHI_ERR_UNSUPPORTED, "more than 2^32 - 64 walk entries");
+    return PHI_OK;
+}
+
+// the body of phi_set_graph, and of phi_set_graph_chopped once the graph is chopped
+static int set_graph_impl(phi_ctx *c, int32_t n_vtx, const char *seq_concat, const int64_t *seq_off, const int64_t *adj_off,
+                          const int32_t *adj, int32_t n_walks, const int64_t *walk_off, const int32_t *walk_vtx,
+                          const int32_t *topo_rank)
+{
+    if (!c) return PHI_ERR_INVALID;
+    const bool dev_walks = walk_vtx == nullptr;
+    PHICHK(set_graph_check_args(c, n_vtx, seq_concat, seq_off, adj_off, adj, n_walks, walk_off, walk_vtx, topo_rank));
 
     PhiStageTimer tm("set_graph");
     // the solve downloads its kept anchors (12 bytes each, a fraction of the walk entries) into pinned
@@ -813,16 +836,11 @@ int phi_set_graph(phi_ctx *c, int32_t n_vtx, const char *seq_concat, const int64
         }
     }
     // ---- validate and keep host copies
-    if (seq_off[0] != 0 || adj_off[0] != 0 || walk_off[0] != 0) return phi_fail(c, PHI_ERR_INVALID, "offset arrays must start at 0");
-    for (int32_t v = 0; v < n_vtx; v++)
-        if (seq_off[v + 1] < seq_off[v] || adj_off[v + 1] < adj_off[v]) return phi_fail(c, PHI_ERR_INVALID, "offsets not monotone at vertex %d", v);
-    for (int32_t h = 0; h < n_walks; h++)
-        if (walk_off[h + 1] <= walk_off[h]) return phi_fail(c, PHI_ERR_INVALID, "walk %d is empty", h);
+    PHICHK(set_graph_check_offsets(c, n_vtx, seq_off, adj_off, n_walks, walk_off));
     const int64_t n_edges = adj_off[n_vtx], n_entries = walk_off[n_walks];
     // (the first and the last vertex of a walk are all the host pass looks at of the walk entries)
     auto walk_first = [&](int32_t h) -> int32_t { return dev_walks ? c->wtext.ends[(size_t)h * 2] : walk_vtx[walk_off[h]]; };
     auto walk_last = [&](int32_t h) -> int32_t { return dev_walks ? c->wtext.ends[(size_t)h * 2 + 1] : walk_vtx[walk_off[h + 1] - 1]; };
-    if (n_entries > PHI_MAX_ENTRIES) return phi_fail(c, PHI_ERR_UNSUPPORTED, "more than 2^32 - 64 walk entries");
     // The DP's per-entry buffers of a chromosome-scale graph (5 x 4-8 bytes per walk entry: 26 GB at 1.3 G entries) are
     // allocated now, on a thread of their own: the driver clears device memory as it hands it out (tens of GB/s), which
     // otherwise shows up as half a second at the start of phi_solve.  Joined before this call returns.
@@ -1285,6 +1303,189 @@ int phi_set_graph(phi_ctx *c, int32_t n_vtx, const char *seq_concat, const int64
         tm.lap("wait for the DP buffers");
     }
     c->have_graph = true;
+    return PHI_OK;
+}
+
+int phi_set_graph(phi_ctx *c, int32_t n_vtx, const char *seq_concat, const int64_t *seq_off, const int64_t *adj_off,
+                  const int32_t *adj, int32_t n_walks, const int64_t *walk_off, const int32_t *walk_vtx,
+                  const int32_t *topo_rank)
+{
+    return set_graph_impl(c, n_vtx, seq_concat, seq_off, adj_off, adj, n_walks, walk_off, walk_vtx, topo_rank);
+}
+
+// data/chop_graph.sh:3,62 inside "set graph": the per-vertex arrays chopped here on the host threads, the walk entries on the
+// device (chop.hip), then set_graph_impl on the chopped graph with its walks where the expansion left them.
+int phi_set_graph_chopped(phi_ctx *c, int32_t n_vtx, const char *seq_concat, const int64_t *seq_off, const int64_t *adj_off,
+                          const int32_t *adj, int32_t n_walks, const int64_t *walk_off, const int32_t *walk_vtx,
+                          const int32_t *topo_rank, int32_t max_len, int64_t *walk_off_out)
+{
+    if (!c) return PHI_ERR_INVALID;
+    const bool dev_walks = walk_vtx == nullptr;
+    // (the offsets the chop itself indexes with are checked there; what else it indexes with -- topo_rank, the edge targets --
+    //  below; the rest by set_graph_impl on the chopped graph)
+    PHICHK(set_graph_check_args(c, n_vtx, seq_concat, seq_off, adj_off, adj, n_walks, walk_off, walk_vtx, topo_rank));
+    if (max_len < 1) return phi_fail(c, PHI_ERR_INVALID, "phi_set_graph_chopped: max_len %d (a piece holds at least one base)", max_len);
+    PhiStageTimer tm("set_graph_chopped");
+    PHICHK(set_graph_check_offsets(c, n_vtx, seq_off, adj_off, n_walks, walk_off));
+    const int64_t n_edges = adj_off[n_vtx], n_in = walk_off[n_walks];
+    // ---- pieces of every vertex, first piece of every vertex
+    const int64_t N = max_len;
+    std::vector<int64_t> first64((size_t)n_vtx + 1, 0);
+    for (int32_t v = 0; v < n_vtx; v++) {
+        const int64_t L = seq_off[v + 1] - seq_off[v];
+        first64[(size_t)v + 1] = first64[(size_t)v] + std::max<int64_t>(1, (L + N - 1) / N);
+    }
+    const int64_t nv2 = first64[(size_t)n_vtx];
+    if (nv2 > INT32_MAX)
+        return phi_fail(c, PHI_ERR_UNSUPPORTED, "chopped to %d bases the graph has %lld vertices: more than 2^31 - 1", max_len, (long long)nv2);
+    auto &first = c->chop.first;
+    first.resize((size_t)n_vtx + 1);
+    for (int32_t v = 0; v <= n_vtx; v++) first[(size_t)v] = (int32_t)first64[(size_t)v];
+    std::vector<int64_t>().swap(first64);
+    phi_chop_info info{};
+    info.n_vtx_in = n_vtx; info.n_vtx_out = nv2; info.n_entries_in = n_in; info.n_entries_out = n_in; info.max_len = max_len;
+    if (nv2 == n_vtx) {
+        // nothing to chop: the graph as passed in
+        PHICHK(set_graph_impl(c, n_vtx, seq_concat, seq_off, adj_off, adj, n_walks, walk_off, walk_vtx, topo_rank));
+        if (walk_off_out) memcpy(walk_off_out, walk_off, ((size_t)n_walks + 1) * 8);
+        c->chop.info = info; c->chop.on = true;
+        return PHI_OK;
+    }
+    // ---- the per-vertex arrays (all host threads; everything is a closed form of first[])
+    std::vector<int32_t> topo_inv((size_t)n_vtx, -1);
+    {
+        PhiHostError verr;
+        phi_parallel_chunks(n_vtx, 1 << 16, [&](int64_t lo, int64_t hi, int) {
+            for (int64_t v = lo; v < hi && !verr.failed(); v++) {
+                const int32_t r = topo_rank[v];
+                int32_t none = -1;
+                if (r < 0 || r >= n_vtx || !__atomic_compare_exchange_n(&topo_inv[(size_t)r], &none, (int32_t)v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {
+                    verr.set(PHI_ERR_INVALID, "topo_rank is not a permutation (vertex %d): is the graph cyclic?", (int)v);
+                    return;
+                }
+                for (int64_t x = adj_off[v]; x < adj_off[v + 1]; x++)
+                    if (adj[x] < 0 || adj[x] >= n_vtx) { verr.set(PHI_ERR_INVALID, "edge target %d out of range", adj[x]); return; }
+            }
+        });
+        if (verr.failed()) return phi_fail(c, verr.code, "%s", verr.msg.c_str());
+    }
+    const int64_t n_edges2 = n_edges + (nv2 - n_vtx);
+    std::vector<int64_t> seq_off2((size_t)nv2 + 1), adj_off2((size_t)nv2 + 1), rank0((size_t)n_vtx);
+    std::vector<int32_t> adj2((size_t)std::max<int64_t>(n_edges2, 1)), topo2((size_t)nv2);
+    {
+        int64_t run = 0;                                       // first rank of every vertex: the counts summed in topological order
+        for (int32_t r = 0; r < n_vtx; r++) {
+            const int32_t v = topo_inv[(size_t)r];
+            rank0[(size_t)v] = run;
+            run += first[(size_t)v + 1] - first[(size_t)v];
+        }
+    }
+    phi_parallel_chunks(n_vtx, 1 << 14, [&](int64_t lo, int64_t hi, int) {
+        for (int64_t v = lo; v < hi; v++) {
+            const int64_t p0 = first[(size_t)v], np = first[(size_t)v + 1] - p0;
+            const int64_t a0 = adj_off[v] + (p0 - v);          // (every piece but a vertex's last has one edge more than the graph had)
+            for (int64_t j = 0; j < np; j++) {
+                seq_off2[(size_t)(p0 + j)] = seq_off[v] + j * N;
+                adj_off2[(size_t)(p0 + j)] = a0 + j;
+                topo2[(size_t)(p0 + j)] = (int32_t)(rank0[(size_t)v] + j);
+                if (j + 1 < np) adj2[(size_t)(a0 + j)] = (int32_t)(p0 + j + 1);
+            }
+            int64_t a = a0 + np - 1;
+            for (int64_t x = adj_off[v]; x < adj_off[v + 1]; x++) adj2[(size_t)a++] = first[(size_t)adj[x]];
+        }
+    });
+    seq_off2[(size_t)nv2] = seq_off[n_vtx];
+    adj_off2[(size_t)nv2] = n_edges2;
+    std::vector<int32_t>().swap(topo_inv);
+    std::vector<int64_t>().swap(rank0);
+    tm.lap("chop: per-vertex arrays");
+    // ---- the walk entries, on the device
+    DevBuf d_in_own, d_first, d_cnt, d_off, d_woff_in, d_woff_out, d_ends, d_bad, d_out;
+    struct Guard { std::vector<DevBuf *> b; ~Guard() { for (DevBuf *x : b) dev_free(*x); } } guard{{&d_in_own, &d_first, &d_cnt, &d_off, &d_woff_in, &d_woff_out, &d_ends, &d_bad, &d_out}};
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int i = 0; i < 4; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } evg{ev};
+    for (int i = 0; i < 4; i++) HIPCHK(hipEventCreate(&ev[i]));
+    if (!dev_walks) PHICHK(upload(c, d_in_own, walk_vtx, (size_t)n_in));
+    const int32_t *d_in = dev_walks ? c->d_walk_vtx.as<int32_t>() : d_in_own.as<int32_t>();
+    PHICHK(upload(c, d_first, first.data(), first.size()));
+    PHICHK(upload(c, d_woff_in, walk_off, (size_t)n_walks + 1));
+    PHICHK(phi_dev_ensure(c, d_cnt, (size_t)n_in * 4));
+    PHICHK(phi_dev_ensure(c, d_off, ((size_t)n_in + 1) * 8));
+    PHICHK(phi_dev_ensure(c, d_bad, 8));
+    PHICHK(phi_dev_ensure(c, d_woff_out, ((size_t)n_walks + 1) * 8));
+    PHICHK(phi_dev_ensure(c, d_ends, (size_t)n_walks * 8));
+    HIPCHK(hipMemsetAsync(d_bad.p, 0xFF, 8, c->stream));
+    HIPCHK(hipEventRecord(ev[0], c->stream));
+    phi_launch_chop_count(c->stream, d_in, n_in, d_first.as<int32_t>(), n_vtx, d_cnt.as<int32_t>(), d_bad.as<unsigned long long>());
+    PHICHK(phi_scan_counts_wide(c, d_cnt.as<int32_t>(), n_in, d_off.as<int64_t>()));
+    HIPCHK(hipEventRecord(ev[1], c->stream));
+    unsigned long long bad = 0;
+    int64_t n_out = 0;
+    HIPCHK(hipMemcpyAsync(&bad, d_bad.p, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&n_out, d_off.as<int64_t>() + n_in, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipGetLastError());
+    if (bad != ~0ull) {
+        int32_t v = 0;
+        HIPCHK(phi_copy_sync(c, &v, d_in + bad, 4, hipMemcpyDeviceToHost));
+        const int32_t h = (int32_t)(std::upper_bound(walk_off, walk_off + n_walks + 1, (int64_t)bad) - walk_off) - 1;
+        return phi_fail(c, PHI_ERR_WALK, "walk %d holds vertex %d out of range", h, v);
+    }
+    // (decided from the counts: nothing has been allocated for the chopped entries yet, and walks resolved on the device are as they were)
+    if (n_out > PHI_MAX_ENTRIES)
+        return phi_fail(c, PHI_ERR_UNSUPPORTED, "chopped to %d bases the walks have %lld entries: more than 2^32 - 64", max_len, (long long)n_out);
+    PHICHK(phi_dev_ensure(c, d_out, (size_t)n_out * 4));
+    HIPCHK(hipEventRecord(ev[2], c->stream));
+    phi_launch_chop_expand(c->stream, d_in, d_off.as<int64_t>(), n_in, d_first.as<int32_t>(), d_out.as<int32_t>(), n_out);
+    phi_launch_chop_walks(c->stream, d_in, d_off.as<int64_t>(), d_woff_in.as<int64_t>(), n_walks, d_first.as<int32_t>(), d_woff_out.as<int64_t>(),
+                          d_ends.as<int32_t>());
+    HIPCHK(hipEventRecord(ev[3], c->stream));
+    std::vector<int64_t> walk_off2((size_t)n_walks + 1);
+    std::vector<int32_t> ends((size_t)n_walks * 2);
+    HIPCHK(hipMemcpyAsync(walk_off2.data(), d_woff_out.p, walk_off2.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(ends.data(), d_ends.p, ends.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipGetLastError());
+    float ms_a = 0.f, ms_b = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms_a, ev[0], ev[1]));
+    HIPCHK(hipEventElapsedTime(&ms_b, ev[2], ev[3]));
+    info.n_entries_out = n_out;
+    info.expand_gpu_ms = (double)ms_a + (double)ms_b;
+    tm.lap("chop: walk entries on the device");
+    // the chopped entries become the context's walks, as if phi_walk_text_resolve had left them
+    std::swap(c->d_walk_vtx, d_out);                           // (the guard lets the unchopped ones go)
+    c->wtext.ends.swap(ends);
+    c->walks_on_device = true;
+    c->walks_on_device_n = n_out;
+    for (DevBuf *x : guard.b) dev_free(*x);
+    const int rc = set_graph_impl(c, (int32_t)nv2, seq_concat, seq_off2.data(), adj_off2.data(), adj2.data(), n_walks, walk_off2.data(), nullptr, topo2.data());
+    c->walks_on_device = false;
+    if (rc) return rc;
+    if (walk_off_out) memcpy(walk_off_out, walk_off2.data(), walk_off2.size() * 8);
+    c->chop.info = info; c->chop.on = true;
+    return PHI_OK;
+}
+
+int phi_chop_origin(phi_ctx *c, const int32_t *vtx, int64_t n, int32_t *orig_vtx, int32_t *orig_off)
+{
+    if (!c || n < 0 || (n > 0 && !vtx)) return PHI_ERR_INVALID;
+    if (!c->have_graph || !c->chop.on) return phi_fail(c, PHI_ERR_STATE, "phi_chop_origin: the graph was not set with phi_set_graph_chopped");
+    const auto &first = c->chop.first;
+    for (int64_t i = 0; i < n; i++) {
+        const int32_t id = vtx[i];                            // (read first: the outputs may be the input array)
+        if (id < 0 || id >= first.back()) return phi_fail(c, PHI_ERR_INVALID, "phi_chop_origin: vertex %d is not in the chopped graph", id);
+        const int32_t v = (int32_t)(std::upper_bound(first.begin(), first.end(), id) - first.begin()) - 1;
+        if (orig_vtx) orig_vtx[i] = v;
+        if (orig_off) orig_off[i] = (id - first[(size_t)v]) * c->chop.info.max_len;
+    }
+    return PHI_OK;
+}
+
+int phi_chop_stats(phi_ctx *c, phi_chop_info *out)
+{
+    if (!c || !out) return PHI_ERR_INVALID;
+    if (!c->have_graph || !c->chop.on) return phi_fail(c, PHI_ERR_STATE, "phi_chop_stats: the graph was not set with phi_set_graph_chopped");
+    *out = c->chop.info;
     return PHI_OK;
 }
 

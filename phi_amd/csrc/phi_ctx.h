@@ -102,6 +102,12 @@ struct phi_ctx {
     } wtext;
     bool walks_on_device = false;
     int64_t walks_on_device_n = 0;
+    // ---- the graph was set chopped (phi_set_graph_chopped): the vertices the solve names are pieces of the caller's
+    struct PhiChop {
+        bool on = false;
+        std::vector<int32_t> first;                   // [vertices as passed in + 1] first piece of every vertex
+        phi_chop_info info{};
+    } chop;
 
     // ---- graph, device side
     DevBuf d_seq, d_seq_off, d_walk_vtx, d_walk_off, d_topo, d_in_off, d_in_src;

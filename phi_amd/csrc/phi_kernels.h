@@ -398,6 +398,14 @@ uint32_t phi_text_num_tiles(uint32_t start, uint32_t end);
 uint32_t phi_text_scan_blocks(uint32_t line_cap);
 void phi_launch_reads_text(hipStream_t st, const PhiTextArgs &A);
 
+// chop.hip: the walk entries of a graph whose vertices are cut into pieces (phi_set_graph_chopped); first[v] = first piece of v
+void phi_launch_chop_count(hipStream_t st, const int32_t *walk_vtx, int64_t n_entries, const int32_t *first, int32_t n_vtx, int32_t *cnt,
+                           unsigned long long *bad_entry);
+void phi_launch_chop_expand(hipStream_t st, const int32_t *walk_vtx, const int64_t *ent_off, int64_t n_entries, const int32_t *first,
+                            int32_t *out, int64_t n_out);
+void phi_launch_chop_walks(hipStream_t st, const int32_t *walk_vtx, const int64_t *ent_off, const int64_t *walk_off, int32_t n_walks,
+                           const int32_t *first, int64_t *walk_off_out, int32_t *ends);
+
 // code-object warm-up, one per translation unit (phi_ctx_create)
 void phi_warm_sketch(hipStream_t st);
 void phi_warm_table(hipStream_t st);

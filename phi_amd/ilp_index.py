@@ -345,8 +345,8 @@ class DeferredGraph:
         self.walk_off = _view(self._L.phi_graph_walk_off(self._h), self.num_walks + 1, C.c_int64, np.int64).copy()
         self.walk_vtx = _view(self._L.phi_graph_walk_vtx(self._h), int(self.walk_off[-1]) if self.num_walks else 0, C.c_int32, np.int32).copy()
 
-    def set_graph(self, ctx):
-        ctx.set_graph(self.seq_concat, self.seq_off, self.adj_off, self.adj, self.walk_off, self.walk_vtx, self.top_order_map)
+    def set_graph(self, ctx, chop=None):
+        return ctx.set_graph(self.seq_concat, self.seq_off, self.adj_off, self.adj, self.walk_off, self.walk_vtx, self.top_order_map, chop=chop)
 
 
 def read_reads(path):
@@ -393,6 +393,7 @@ class ILP_index:
         self.threshold = 1.0
         self.is_mixed = True
         self.max_occ = 5000
+        self.chop = None                # N: segments are cut into pieces of at most N bases first (data/chop_graph.sh:3 `hal2vg --chop 30`)
         self.graph = None
         self.result = None
         self._t0 = time.time()
@@ -428,9 +429,15 @@ class ILP_index:
         try:
             flags = (_capi.PHI_FLAG_QCLP if self.is_qclp else 0) | (_capi.PHI_FLAG_MIXED if self.is_mixed else 0)
             ctx.set_params(k=self.k_mer, w=self.window, threshold=self.threshold, recombination=self.recombination, flags=flags)
-            ctx.set_graph(G.seq_concat, G.seq_off, G.adj_off, G.adj, G.walk_off, G.walk_vtx, G.top_order_map)
+            ctx.set_graph(G.seq_concat, G.seq_off, G.adj_off, G.adj, G.walk_off, G.walk_vtx, G.top_order_map, chop=self.chop)
+            if self.chop is not None:
+                cs = ctx.chop_stats()
+                self._stamp(f"Graph chopped to {self.chop} bases: {cs['n_vtx_in']} -> {cs['n_vtx_out']} vertices, "
+                            f"{cs['n_entries_in']} -> {cs['n_entries_out']} walk entries")
             ctx.add_reads(seqs)
             res = ctx.solve()
+            if self.chop is not None:                          # the path in the caller's vertices: (segment, offset of the piece)
+                res["path_orig_vtx"], res["path_orig_off"] = ctx.chop_origin(res["path_vtx"])
             hap = ctx.path_sequence(res["hap_len"])
             sharing = ctx.walk_sharing(G.num_walks) if self.debug else None
         finally:
@@ -476,8 +483,13 @@ class ILP_index:
         if len(vt) == 0:
             return ""
         prev_hap = int(hp[0])
+        if "path_orig_vtx" in res:                             # chopped: the pieces' lengths
+            ov, oo = res["path_orig_vtx"], res["path_orig_off"]
+            lens = np.maximum(0, np.minimum(self.chop, (G.seq_off[ov + 1] - G.seq_off[ov]) - oo))
+        else:
+            lens = G.seq_off[vt + 1] - G.seq_off[vt]
         for i in range(len(vt)):
-            str_id += int(G.seq_off[vt[i] + 1] - G.seq_off[vt[i]])
+            str_id += int(lens[i])
             if i > 0 and int(hp[i]) != prev_hap:
                 out.append(f">({G.hap_id2name[prev_hap]},[{prev},{str_id - 1}])")
                 prev_hap, prev = int(hp[i]), str_id
@@ -500,6 +512,7 @@ def main(argv=None):
     ap.add_argument("-T", type=float, default=1.0)
     ap.add_argument("-t", type=int, default=4)
     ap.add_argument("-d", type=int, default=0)
+    ap.add_argument("--chop", type=int, default=None)
     a = ap.parse_args(argv)
     idx = ILP_index(a.g)
     idx.read_gfa()
@@ -507,6 +520,7 @@ def main(argv=None):
     idx.hap_name = get_hap_name(a.g, a.r)
     idx.k_mer, idx.window, idx.recombination = a.k, a.w, a.R
     idx.is_qclp, idx.threshold, idx.is_mixed = a.q, a.T, bool(a.m)
+    idx.chop = a.chop
     reads = []
     idx.read_ip_reads(reads, a.r)
     idx.ILP_function(reads)
