@@ -21,7 +21,10 @@
  * contexts, anchors in the model and walk entries on vertices with recombination edges, at most
  * 254 out-edges and 255 recombination in-edges per vertex, no walk through a segment without
  * sequence, no graph whose walks both start and end at interior vertices.  phi_set_graph_chopped: the same limits hold
- * for the CHOPPED graph (at most 2^31 - 1 pieces, at most 2^32 - 64 chopped walk entries).
+ * for the CHOPPED graph (at most 2^31 - 1 pieces, at most 2^32 - 64 chopped walk entries).  phi_vcf_genotypes / phi_vcf_walks:
+ * one contig, fewer than 2^31 kept records, genotype text + matrix (4 bytes per record and sample) within device memory, fewer
+ * than 65 535 ALT alleles per record, at most 1022 kept haplotypes (reference
+ * included) and 2^32 - 64 walk entries, as for any graph.
  */
 #ifndef PHI_AMD_H
 #define PHI_AMD_H
@@ -120,6 +123,44 @@ typedef struct {
     double expand_gpu_ms;
 } phi_chop_info;
 int phi_chop_stats(phi_ctx *ctx, phi_chop_info *out);
+
+/*
+ * "Set graph" from a phased multi-sample VCF + reference FASTA (the reference's second input route, vcf2gfa.py:27-64: `vg construct
+ * | vg gbwt | gfa2gbwt -m 30`, here the rule of phi_amd/vcf2gfa.py) without a GFA in between.  The host reads the small parts
+ * and builds the per-vertex arrays (include/phi_host.h phi_vcf_read, phi_vcf_build); the device parses the genotype text, the
+ * bulk of a VCF's bytes, and writes the walk entries, which at panel scale exist only in device memory:
+ *   phi_vcf_genotypes   vcf2gfa.py:27-64, the GT columns.  text[n_text]: the sample columns of the kept records back to back,
+ *                       record r's slice at [text_off[r], text_off[r + 1] - 1) with ONE line feed behind it (phi_vcf_text of
+ *                       phi_host.h); gt_index[r] = index of GT in FORMAT.  Sample s's field stands behind the slice's s-th tab; its
+ *                       GT part is the gt_index-th ':'-separated part; '/' reads as '|'; the first two '|'-separated parts give
+ *                       gt[(r * n_samples + s) * 2 + {0, 1}] (uint16: a non-empty run of ASCII digits is its value, anything
+ *                       else 0); ploidy[s] = max over records of min(2, parts other than ".").  flagged[r] != 0: the kernel did
+ *                       not decide record r (a value of more than four digits, fewer fields than samples, fewer ':' parts than
+ *                       gt_index + 1, a GT part of kilobytes) and nothing of its row is to be trusted: phi_vcf_parse_gt
+ *                       (phi_host.h) over that row fills it and raises ploidy, or reports the error.  Nothing is guessed.
+ *   phi_vcf_walks       vcf2gfa.py:27-64, the W-lines.  From phi_vcf_build's tables -- unit_first[n_units + 1], per site its
+ *                       backbone unit and first allele unit, choice[site * n_haps + haplotype] -- every haplotype's walk over
+ *                       units (2 * n_sites + 1 entries: backbone, allele, ..., last backbone = unit n_units - 1), expanded to
+ *                       segment ids by the count / scan / expand of phi_set_graph_chopped (chop.hip).  The entries and
+ *                       walk_off_out[n_haps + 1] are left where phi_walk_text_resolve leaves them: phi_set_graph(..., walk_vtx =
+ *                       NULL, ...) and phi_walk_entries follow unchanged.  More than 1022 haplotypes or 2^32 - 64 entries:
+ *                       PHI_ERR_UNSUPPORTED, decided before the entries are allocated; the context stays usable and walks
+ *                       an earlier call left on the device are as they were.
+ *   phi_vcf_stats       what the last two calls did; the GPU milliseconds by HIP events on the context's stream.
+ */
+typedef struct {
+    int64_t text_bytes;               /* genotype text uploaded */
+    int64_t n_records;
+    int32_t n_samples;
+    int64_t n_flagged;                /* records left to the host's scalar parser */
+    int64_t n_units, n_entries;       /* phi_vcf_walks: units of the graph, walk entries written */
+    double genotype_gpu_ms, walks_gpu_ms;
+} phi_vcf_info;
+int phi_vcf_genotypes(phi_ctx *ctx, const char *text, int64_t n_text, const int64_t *text_off, const int32_t *gt_index, int64_t n_records,
+                      int32_t n_samples, uint16_t *gt, int32_t *ploidy, uint8_t *flagged);
+int phi_vcf_walks(phi_ctx *ctx, const int32_t *unit_first, int64_t n_units, const int32_t *site_backbone, const int32_t *site_allele0,
+                  int64_t n_sites, const int32_t *choice, int32_t n_haps, int64_t *walk_off_out);
+int phi_vcf_stats(phi_ctx *ctx, phi_vcf_info *out);
 
 /*
  * Stage 1b/2a of ILP_function (:617-655) for one batch of reads: sketch, spectrum insert,

@@ -8,6 +8,7 @@
  *                       in memory + blocks a callback hands over (the rest of a stream whose beginning the device has taken)
  *   phi_text_stream_*   the (inflated) text of a reads file as it is, for phi_add_reads_text (phi_amd.h): the records are
  *                       found on the device, no host core parses a regular FASTA / FASTQ file
+ *   phi_vcf_*        vcf2gfa.py (VCF + FASTA -> graph)              vcf2gfa.py:27-64, without vg / gfa2gbwt
  *   phi_hap_name     get_hap_name()                       src/misc.cpp:58-87
  *   phi_write_fasta  the FASTA writer                     src/ILP_index.cpp:1590-1598
  * The arrays phi_gfa_read returns are exactly the arguments of phi_set_graph (phi_amd.h).
@@ -79,6 +80,60 @@ const int32_t *phi_graph_walk_vtx(const phi_graph *g);
 const int32_t *phi_graph_topo_rank(const phi_graph *g);    /* top_order_map */
 const char *phi_graph_hap_name(const phi_graph *g, int32_t walk);   /* sample + "." + hap (:98) */
 const char *phi_graph_seg_name(const phi_graph *g, int32_t vtx);
+
+/* A phased multi-sample VCF + a reference FASTA as the graph (the reference's second input route, vcf2gfa.py:27-64), without a
+ * GFA in between.  The graph is exactly the one phi_amd/vcf2gfa.py writes (read_fasta_single, read_vcf, build, write_gfa, its
+ * CHOP a parameter) and phi_gfa_read reads back: vertices, adjacency (out-edges ascending), walks, hap names, Kahn ranks.
+ *   phi_vcf_read      the FASTA record (upper-cased; more than one record: PHI_HOST_ERR_INVALID) and the VCF (plain, gzip, BGZF):
+ *                     the record rules on the FIXED columns -- first contig seen (others counted: phi_vcf_n_other_contig), REF
+ *                     against the FASTA (phi_vcf_n_ref_mismatch), GT in FORMAT, sequence ALTs only, inside the contig --, the
+ *                     stable sort by (start, end), the sites (phi_vcf_site_off[n_sites + 1]: records of every maximal run that
+ *                     overlaps or touches).  The SAMPLE columns of the kept records are not parsed: phi_vcf_text holds them back
+ *                     to back, record r's slice (from the byte after the line's 9th tab to its end, CR / LF stripped) at
+ *                     [text_off[r], text_off[r + 1] - 1) with ONE LINE FEED behind it, ready for one upload (phi_vcf_genotypes
+ *                     of phi_amd.h).  ALT a of record r: alt_bytes[alt_pos[alt_off[r] + a], alt_pos[alt_off[r] + a + 1]).
+ *   phi_vcf_parse_gt  the exact scalar genotype parser over those slices, rows [rec_lo, rec_hi): what the device kernel computes
+ *                     and its fallback.  gt[(r * n_samples + s) * 2 + column] (65 535 = that index or more; a record holds fewer
+ *                     ALTs), ploidy[s] raised to min(2, GT parts other than ".").  PHI_HOST_ERR_INVALID where the Python raises.
+ *   phi_vcf_build     genotype matrix -> graph with the walks left out (as phi_gfa_read_deferred leaves them; free it with
+ *                     phi_graph_free) + the tables phi_vcf_walks (phi_amd.h) makes the walk entries from: unit_first[n_units + 1]
+ *                     (units are backbone, alleles, backbone, ... and hold consecutive segment ids), per real site its backbone
+ *                     unit and first allele unit, choice[site * n_kept_haps + kept haplotype] = allele index.  The two refusals
+ *                     ("first base of the contig", "last base of the contig") are PHI_HOST_ERR_INVALID.  At most 16 threads.
+ * Errors occur wherever the Python raises, and in two places where it does not: a #CHROM line that names samples behind kept data
+ * lines (the script starts a new sample list there and then indexes the earlier records with it), and a POS that is not an
+ * optionally signed run of decimal digits (Python's int() also takes forms such as "1_0"). */
+typedef struct phi_vcf phi_vcf;
+int phi_vcf_read(const char *vcf_path, const char *fasta_path, phi_vcf **out, char *err, int err_cap);
+void phi_vcf_free(phi_vcf *v);
+int32_t phi_vcf_n_samples(const phi_vcf *v);
+const char *phi_vcf_sample_name(const phi_vcf *v, int32_t s);
+const char *phi_vcf_contig(const phi_vcf *v);
+int64_t phi_vcf_n_records(const phi_vcf *v);
+int64_t phi_vcf_n_sites(const phi_vcf *v);
+int64_t phi_vcf_n_other_contig(const phi_vcf *v);
+int64_t phi_vcf_n_ref_mismatch(const phi_vcf *v);
+int64_t phi_vcf_ref_len(const phi_vcf *v);
+const char *phi_vcf_ref_seq(const phi_vcf *v);
+const int64_t *phi_vcf_rec_start(const phi_vcf *v);        /* [n_records], 0-based */
+const int64_t *phi_vcf_rec_end(const phi_vcf *v);
+const int32_t *phi_vcf_rec_gt_index(const phi_vcf *v);     /* index of GT in FORMAT */
+const int64_t *phi_vcf_rec_alt_off(const phi_vcf *v);      /* [n_records + 1] */
+const int64_t *phi_vcf_alt_pos(const phi_vcf *v);
+const char *phi_vcf_alt_bytes(const phi_vcf *v);
+const int64_t *phi_vcf_site_off(const phi_vcf *v);
+const char *phi_vcf_text(const phi_vcf *v);
+const int64_t *phi_vcf_text_off(const phi_vcf *v);         /* [n_records + 1] */
+int phi_vcf_parse_gt(const char *text, const int64_t *text_off, const int32_t *gt_index, int64_t rec_lo, int64_t rec_hi, int32_t n_samples,
+                     uint16_t *gt, int32_t *ploidy, char *err, int err_cap);
+int phi_vcf_build(phi_vcf *v, const uint16_t *gt, const int32_t *ploidy, int32_t max_len, phi_graph **out, char *err, int err_cap);
+int64_t phi_vcf_n_units(const phi_vcf *v);                 /* these after phi_vcf_build */
+const int32_t *phi_vcf_unit_first(const phi_vcf *v);
+int64_t phi_vcf_n_real_sites(const phi_vcf *v);
+const int32_t *phi_vcf_site_backbone(const phi_vcf *v);
+const int32_t *phi_vcf_site_allele0(const phi_vcf *v);
+int32_t phi_vcf_n_kept_haps(const phi_vcf *v);
+const int32_t *phi_vcf_choice(const phi_vcf *v);
 
 /* FASTA/FASTQ reader with kseq's record rules (multi-line FASTA, '+' quality blocks). */
 int phi_reads_read(const char *path, phi_reads **out, char *err, int err_cap);

@@ -33,6 +33,7 @@ SYMBOLS = [
     "phi_text_park_gzip_begin", "phi_text_park_gzip_add", "phi_text_park_gzip_end",
     "phi_gfa_gzip_split", "phi_gfa_gzip_free",
     "phi_set_graph_chopped", "phi_chop_origin", "phi_chop_stats",
+    "phi_vcf_genotypes", "phi_vcf_walks", "phi_vcf_stats",
 ]
 PHI_INFLATE_NO_FINDER = 1
 PHI_INFLATE_CHUNK_DEFAULT = 64 << 10          # include/phi_amd.h
@@ -51,6 +52,11 @@ class PhiSolveInfo(C.Structure):
 class PhiChopInfo(C.Structure):
     _fields_ = [("n_vtx_in", C.c_int64), ("n_vtx_out", C.c_int64), ("n_entries_in", C.c_int64), ("n_entries_out", C.c_int64),
                 ("max_len", C.c_int32), ("expand_gpu_ms", C.c_double)]
+
+
+class PhiVcfInfo(C.Structure):
+    _fields_ = [("text_bytes", C.c_int64), ("n_records", C.c_int64), ("n_samples", C.c_int32), ("n_flagged", C.c_int64),
+                ("n_units", C.c_int64), ("n_entries", C.c_int64), ("genotype_gpu_ms", C.c_double), ("walks_gpu_ms", C.c_double)]
 
 
 class PhiResult(C.Structure):
@@ -100,6 +106,9 @@ def load():
     L.phi_set_graph_chopped.argtypes = [vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, vp]
     L.phi_chop_origin.argtypes = [vp, vp, i64, vp, vp]
     L.phi_chop_stats.argtypes = [vp, C.POINTER(PhiChopInfo)]
+    L.phi_vcf_genotypes.argtypes = [vp, vp, i64, vp, vp, i64, i32, vp, vp, vp]
+    L.phi_vcf_walks.argtypes = [vp, vp, i64, vp, vp, i64, vp, i32, vp]
+    L.phi_vcf_stats.argtypes = [vp, C.POINTER(PhiVcfInfo)]
     L.phi_add_reads.argtypes = [vp, vp, vp, i64]
     L.phi_add_reads_device.argtypes = [vp, vp, vp, i64, i64]
     L.phi_reset_reads.argtypes = [vp]

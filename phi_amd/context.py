@@ -87,6 +87,55 @@ class Context:
                                         self.n_walks, _ptr(walk_off), _ptr(walk_vtx), _ptr(top_rank)))
         return None
 
+    def set_graph_vcf(self, vcf_path, fasta_path, max_len=30):
+        """ "Set graph" from a phased VCF + reference FASTA (the graph of phi_amd.vcf2gfa, no GFA in between): vcf_graph(), then
+        phi_set_graph takes the walk entries from where the device left them.  Returns the host graph description (VcfGraph:
+        hap_id2name, the arrays, walk_off, n_other_contig / n_ref_mismatch / warnings()) with .stats = vcf_stats() plus host
+        seconds per stage.  What phi_set_graph refuses of any graph it refuses here (the context stays usable)."""
+        import time
+        v = self.vcf_graph(vcf_path, fasta_path, max_len)
+        t4 = time.perf_counter()
+        self.set_graph(v.seq_concat, v.seq_off, v.adj_off, v.adj, v.walk_off, None, v.top_order_map)
+        v.stats["set_graph_s"] = time.perf_counter() - t4
+        return v
+
+    def vcf_graph(self, vcf_path, fasta_path, max_len=30):
+        """The VCF route up to "set graph": the host reads the fixed columns and builds the per-vertex arrays
+        (ilp_index.VcfGraph), the device parses the genotype text (phi_vcf_genotypes; records it flags go through the host's
+        scalar parser) and writes the walk entries (phi_vcf_walks): walk_entries() returns them, set_graph(..., walk_vtx=None)
+        takes them."""
+        import time
+        from .ilp_index import VcfGraph
+        t0 = time.perf_counter()
+        v = VcfGraph(vcf_path, fasta_path)
+        t1 = time.perf_counter()
+        n_s, n_r = len(v.samples), v.n_records
+        gt = np.zeros((n_r, n_s, 2), np.uint16)
+        ploidy = np.zeros(n_s, np.int32)
+        flagged = np.zeros(max(n_r, 1), np.uint8)
+        self._chk(self._L.phi_vcf_genotypes(self._h, _ptr(v.text), len(v.text), _ptr(v.text_off), _ptr(v.gt_index), n_r, n_s,
+                                            _ptr(gt), _ptr(ploidy), _ptr(flagged)))
+        for r in np.flatnonzero(flagged[:n_r]).tolist():          # what the kernel left undecided: the exact scalar parser
+            v.parse_gt(r, r + 1, gt, ploidy)
+        t2 = time.perf_counter()
+        v.build(gt, ploidy, max_len)
+        t3 = time.perf_counter()
+        walk_off = np.zeros(v.num_walks + 1, np.int64)
+        choice = np.ascontiguousarray(v.choice, np.int32)
+        self._chk(self._L.phi_vcf_walks(self._h, _ptr(v.unit_first), v.n_units, _ptr(v.site_backbone), _ptr(v.site_allele0), v.n_real_sites,
+                                        _ptr(choice), v.num_walks, _ptr(walk_off)))
+        t4 = time.perf_counter()
+        v.walk_off = walk_off
+        v.stats = dict(self.vcf_stats(), read_s=t1 - t0, genotypes_s=t2 - t1, build_s=t3 - t2, walks_s=t4 - t3, set_graph_s=0.0)
+        return v
+
+    def vcf_stats(self):
+        """What phi_vcf_genotypes / phi_vcf_walks did: bytes of genotype text, records, samples, flagged records, units, entries,
+        GPU milliseconds of the two stages."""
+        r = _capi.PhiVcfInfo()
+        self._chk(self._L.phi_vcf_stats(self._h, C.byref(r)))
+        return {n: getattr(r, n) for n, _ in _capi.PhiVcfInfo._fields_}
+
     def chop_origin(self, vtx):
         """Chopped vertex ids -> (vertex as passed to set_graph(chop=N), base offset of the piece inside it)."""
         vtx = np.ascontiguousarray(vtx, np.int32)

@@ -136,6 +136,9 @@ struct Options {
     long long shard_min_bases = 50000000;                     // --shard-min-bases: text bytes of reads a further GPU must be worth
     float threshold = 1.0f;
     std::string gfa_file, reads_file, hap_file;               // (reads_file / hap_file: the first job's, for the usage text)
+    std::string vcf_ref;                                      // --vcf FILE --ref FILE: the graph from a phased VCF (gfa_file holds the VCF's name then)
+    bool from_vcf = false;
+    int vcf_max_len = 30;                                     // its segments' length (--chop N; gfa2gbwt -m 30, vcf2gfa.py:53)
     std::vector<std::string> reads_files, hap_files;          // one entry per job: -r a -o a.fa -r b -o b.fa ...
     int argc = 0;
     char **argv = nullptr;
@@ -447,6 +450,7 @@ struct Driver {
     phi_ctx *ctx = nullptr;                                   // the context that solves and reports
     ReadsFeed feed;
     phi_graph *g = nullptr;
+    phi_vcf *vcf = nullptr;                                   // --vcf: the reader's handle (the unit tables build_index writes the walks from)
     char err[512] = "";
     std::string reads_file, hap_file;                         // the job at hand, and the name in its FASTA
     char hap_name[4096];
@@ -537,6 +541,41 @@ struct Driver {
         d.wt.rc = phi_walk_text_upload(d.ctxs[0], reinterpret_cast<const phi_walk_text *>(walks), n);
         d.wt.sent = d.wt.rc == 0;
     }
+    // ---- graph from a phased VCF + reference FASTA (vcf2gfa.py:27-64): the host reads the fixed columns, the
+    //      device parses the genotype text, the host builds the per-vertex arrays; the walk entries are written on every GPU
+    //      by build_index.  No GFA is written or read.
+    int load_graph_vcf()
+    {
+        int r;
+        {
+            Stage st("VCF + FASTA read");
+            r = phi_vcf_read(o.gfa_file.c_str(), o.vcf_ref.c_str(), &vcf, err, sizeof err);
+        }
+        if (r != PHI_HOST_OK) return fail("[E::vcf2gfa] %s\n", err);
+        if (const long long n = phi_vcf_n_other_contig(vcf))
+            fprintf(stderr, "[W::vcf2gfa] %lld record(s) of other contigs than %s skipped (vcf2gfa handles one contig)\n", n, phi_vcf_contig(vcf));
+        if (const long long n = phi_vcf_n_ref_mismatch(vcf))
+            fprintf(stderr, "[W::vcf2gfa] %lld record(s) skipped: their REF column is not what the FASTA holds at POS (another assembly?)\n", n);
+        const int64_t n_rec = phi_vcf_n_records(vcf);
+        const int32_t n_s = phi_vcf_n_samples(vcf);
+        std::vector<uint16_t> gt((size_t)n_rec * (size_t)n_s * 2 + 1, 0);
+        std::vector<int32_t> ploidy((size_t)n_s + 1, 0);
+        std::vector<uint8_t> flagged((size_t)n_rec + 1, 0);
+        {
+            Stage st("VCF genotypes on the device");
+            if ((r = f_ctx.get())) return fail("[E::main] no usable MI355X (HIP) device %d: %s\n", devices[0], phi_strerror(r));
+            r = phi_vcf_genotypes(ctxs[0], phi_vcf_text(vcf), phi_vcf_text_off(vcf)[n_rec], phi_vcf_text_off(vcf), phi_vcf_rec_gt_index(vcf), n_rec, n_s,
+                                  gt.data(), ploidy.data(), flagged.data());
+            if (r) return fail_on(ctxs[0], "VCF genotypes", r);
+            for (int64_t i = 0; i < n_rec; i++)                // what the kernel left undecided: the exact scalar parser
+                if (flagged[(size_t)i] && phi_vcf_parse_gt(phi_vcf_text(vcf), phi_vcf_text_off(vcf), phi_vcf_rec_gt_index(vcf), i, i + 1, n_s, gt.data(), ploidy.data(), err, sizeof err))
+                    return fail("[E::vcf2gfa] %s\n", err);
+        }
+        Stage st("VCF graph build");
+        if (phi_vcf_build(vcf, gt.data(), ploidy.data(), o.vcf_max_len, &g, err, sizeof err) != PHI_HOST_OK) return fail("[E::vcf2gfa] %s\n", err);
+        feed.mark(feed.gfa_parsed);
+        return 0;
+    }
     // ---- graph (main.cpp:101-115)
     // One GPU: the walks stay TEXT in the reader (include/phi_host.h phi_gfa_read_deferred) and go to HBM as soon as the reader
     // knows where they are -- while it still enters the segment names --, and the device resolves them (phi_walk_text_*): at
@@ -547,6 +586,7 @@ struct Driver {
     // path has to wait for that start before its first byte moves: measured at C2, 32 MB as the threshold cost every process 40 ms)
     int load_graph()
     {
+        if (o.from_vcf) return load_graph_vcf();
         const bool defer_walks = n_dev == 1 && !kn.walks_host;
         const bool on_device = defer_walks && kn.gfa_inflate && gfa_on_device();
         if (!on_device) {
@@ -580,7 +620,15 @@ struct Driver {
             int r = phi_set_params(cx, o.k, o.w, o.threshold, o.recombination, flags);
             // the reference's model.optimize() has no limit (ILP_index.cpp:1412-1418): none here unless --dp-budget asks for one
             if (!r) r = phi_set_solve_budget(cx, o.dp_budget >= 0 ? o.dp_budget : 0);
-            if (!r && o.chop)
+            std::vector<int64_t> vcf_walk_off;
+            if (!r && vcf) {
+                vcf_walk_off.resize((size_t)phi_graph_n_walks(g) + 1);
+                r = phi_vcf_walks(cx, phi_vcf_unit_first(vcf), phi_vcf_n_units(vcf), phi_vcf_site_backbone(vcf), phi_vcf_site_allele0(vcf),
+                                  phi_vcf_n_real_sites(vcf), phi_vcf_choice(vcf), phi_vcf_n_kept_haps(vcf), vcf_walk_off.data());
+                if (!r)
+                    r = phi_set_graph(cx, phi_graph_n_vtx(g), phi_graph_seq_concat(g), phi_graph_seq_off(g), phi_graph_adj_off(g),
+                                      phi_graph_adj(g), phi_graph_n_walks(g), vcf_walk_off.data(), nullptr, phi_graph_topo_rank(g));
+            } else if (!r && o.chop)
                 r = phi_set_graph_chopped(cx, phi_graph_n_vtx(g), phi_graph_seq_concat(g), phi_graph_seq_off(g), phi_graph_adj_off(g), phi_graph_adj(g),
                                           phi_graph_n_walks(g), phi_graph_walk_off(g), phi_graph_walk_vtx(g), phi_graph_topo_rank(g), o.chop, nullptr);
             else if (!r)
@@ -815,7 +863,7 @@ struct Driver {
         return 3;
     }
     // PHI_FULL_TEARDOWN (leak checks): everything given back in order
-    void teardown() { feed.stop_reader(); feed.teardown(ctx); phi_graph_free(g); for (phi_ctx *cx : ctxs) phi_ctx_destroy(cx); }
+    void teardown() { feed.stop_reader(); feed.teardown(ctx); phi_graph_free(g); if (vcf) phi_vcf_free(vcf); for (phi_ctx *cx : ctxs) phi_ctx_destroy(cx); }
 };
 
 // Every stage keeps its overlap: the device contexts are made while the GFA is parsed, the reads file is read while the graph
@@ -886,15 +934,18 @@ int main(int argc, char *argv[])
     Options o;
     int help = 0;
     static struct option long_options[] = {{"version", no_argument, 0, 300}, {"device", required_argument, 0, 301}, {"dp-budget", required_argument, 0, 302},
-                                           {"devices", required_argument, 0, 303}, {"shard-min-bases", required_argument, 0, 304}, {"chop", required_argument, 0, 305}, {0, 0, 0, 0}};
+                                           {"devices", required_argument, 0, 303}, {"shard-min-bases", required_argument, 0, 304}, {"chop", required_argument, 0, 305}, {"vcf", required_argument, 0, 306}, {"ref", required_argument, 0, 307}, {0, 0, 0, 0}};
     int c;
+    std::string gfa_arg, vcf_arg;
     // main.cpp:38 declares -h with an argument; a bare -h falls into the usage branch either way
     while ((c = getopt_long(argc, argv, "x:d:c:l:s:m:R:q:T:N:h:k:w:t:g:r:o:DS", long_options, nullptr)) >= 0) {
         if (c == 'w') o.w = atoi(optarg);
         else if (c == 'k') o.k = atoi(optarg);
         else if (c == 't') o.n_threads = atoi(optarg);
         else if (c == 'm') o.is_mixed = atoi(optarg);
-        else if (c == 'g') o.gfa_file = optarg;
+        else if (c == 'g') { gfa_arg = optarg; }
+        else if (c == 306) { vcf_arg = optarg; }
+        else if (c == 307) o.vcf_ref = optarg;
         else if (c == 'R') o.recombination = atoi(optarg);
         else if (c == 'q') o.is_qclp = atoi(optarg);
         else if (c == 'N') o.is_naive = atoi(optarg);
@@ -921,6 +972,10 @@ int main(int argc, char *argv[])
             }
         }
     }
+    if (!vcf_arg.empty() && !gfa_arg.empty()) { fprintf(stderr, "[E::main] --vcf and -g exclude each other: the graph comes from a GFA or from a VCF + FASTA\n"); return 1; }
+    if (vcf_arg.empty() != o.vcf_ref.empty()) { fprintf(stderr, "[E::main] --vcf FILE and --ref FILE go together (a phased VCF and its reference FASTA)\n"); return 1; }
+    o.gfa_file = vcf_arg.empty() ? gfa_arg : vcf_arg;
+    if (!vcf_arg.empty()) { o.from_vcf = true; o.vcf_max_len = o.chop ? o.chop : 30; o.chop = 0; }      // (--chop N: the segments are built at that length)
     if (argc < 2 || o.gfa_file.empty() || o.reads_file.empty() || o.hap_file.empty() || help) {
         usage(stderr, o.k, o.w, o.recombination, o.is_qclp, o.is_mixed, o.threshold, o.n_threads, o.gfa_file.c_str(), o.reads_file.c_str(), o.hap_file.c_str(), o.debug);
         return 1;

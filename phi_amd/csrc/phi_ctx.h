@@ -108,6 +108,11 @@ struct phi_ctx {
         std::vector<int32_t> first;                   // [vertices as passed in + 1] first piece of every vertex
         phi_chop_info info{};
     } chop;
+    // ---- "set graph" from a phased VCF (phi_vcf_genotypes, phi_vcf_walks): what the last calls did
+    struct PhiVcf {
+        bool have = false;
+        phi_vcf_info info{};
+    } vcf;
 
     // ---- graph, device side
     DevBuf d_seq, d_seq_off, d_walk_vtx, d_walk_off, d_topo, d_in_off, d_in_src;

@@ -406,6 +406,13 @@ void phi_launch_chop_expand(hipStream_t st, const int32_t *walk_vtx, const int64
 void phi_launch_chop_walks(hipStream_t st, const int32_t *walk_vtx, const int64_t *ent_off, const int64_t *walk_off, int32_t n_walks,
                            const int32_t *first, int64_t *walk_off_out, int32_t *ends);
 
+// vcf.hip: the sample columns of a VCF parsed on the device; the walks over units of a graph built from one (phi_vcf_genotypes, phi_vcf_walks)
+int64_t phi_vcf_num_tiles(int64_t n_bytes);
+void phi_launch_vcf_genotypes(hipStream_t st, const uint8_t *text, int64_t n, void *tile_seg, const int32_t *gt_index, int64_t n_rec, int32_t n_samples,
+                              uint16_t *gt, int32_t *ploidy, uint8_t *flag, uint32_t *err);
+void phi_launch_vcf_unit_walks(hipStream_t st, const int32_t *site_backbone, const int32_t *site_allele0, const int32_t *choice, int64_t n_sites,
+                               int32_t n_haps, int32_t last_unit, int32_t *out);
+
 // code-object warm-up, one per translation unit (phi_ctx_create)
 void phi_warm_sketch(hipStream_t st);
 void phi_warm_table(hipStream_t st);

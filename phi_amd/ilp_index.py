@@ -30,6 +30,11 @@ HOST_SYMBOLS = [
     "phi_text_stream_open", "phi_text_stream_read", "phi_text_stream_close",
     "phi_gfa_read_deferred", "phi_graph_walks_deferred", "phi_graph_walk_texts", "phi_graph_name_index", "phi_graph_resolve_walks",
     "phi_graph_set_walk_off", "phi_gfa_read_deferred_text",
+    "phi_vcf_read", "phi_vcf_free", "phi_vcf_n_samples", "phi_vcf_sample_name", "phi_vcf_contig", "phi_vcf_n_records", "phi_vcf_n_sites",
+    "phi_vcf_n_other_contig", "phi_vcf_n_ref_mismatch", "phi_vcf_ref_len", "phi_vcf_ref_seq", "phi_vcf_rec_start", "phi_vcf_rec_end",
+    "phi_vcf_rec_gt_index", "phi_vcf_rec_alt_off", "phi_vcf_alt_pos", "phi_vcf_alt_bytes", "phi_vcf_site_off", "phi_vcf_text", "phi_vcf_text_off",
+    "phi_vcf_parse_gt", "phi_vcf_build", "phi_vcf_n_units", "phi_vcf_unit_first", "phi_vcf_n_real_sites", "phi_vcf_site_backbone",
+    "phi_vcf_site_allele0", "phi_vcf_n_kept_haps", "phi_vcf_choice",
 ]
 
 WALK_TEXT_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_int32)
@@ -97,6 +102,23 @@ def host_lib():
     L.phi_graph_set_walk_off.argtypes = [vp, vp]
     L.phi_gfa_read_deferred_text.argtypes = [vp, C.c_int64, C.c_char_p, C.POINTER(vp), C.c_char_p, C.c_int]
     L.phi_hap_name.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int]
+    L.phi_vcf_read.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(vp), C.c_char_p, C.c_int]
+    L.phi_vcf_free.restype = None
+    L.phi_vcf_free.argtypes = [vp]
+    for n, rt in (("n_samples", C.c_int32), ("n_kept_haps", C.c_int32), ("contig", C.c_char_p), ("n_records", C.c_int64), ("n_sites", C.c_int64),
+                  ("n_other_contig", C.c_int64), ("n_ref_mismatch", C.c_int64), ("ref_len", C.c_int64), ("n_units", C.c_int64), ("n_real_sites", C.c_int64)):
+        f = getattr(L, "phi_vcf_" + n)
+        f.restype = rt
+        f.argtypes = [vp]
+    for n in ("ref_seq", "rec_start", "rec_end", "rec_gt_index", "rec_alt_off", "alt_pos", "alt_bytes", "site_off", "text", "text_off",
+              "unit_first", "site_backbone", "site_allele0", "choice"):
+        f = getattr(L, "phi_vcf_" + n)
+        f.restype = vp
+        f.argtypes = [vp]
+    L.phi_vcf_sample_name.restype = C.c_char_p
+    L.phi_vcf_sample_name.argtypes = [vp, C.c_int32]
+    L.phi_vcf_parse_gt.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, C.c_int32, vp, vp, C.c_char_p, C.c_int]
+    L.phi_vcf_build.argtypes = [vp, vp, vp, C.c_int32, C.POINTER(vp), C.c_char_p, C.c_int]
     L.phi_write_fasta.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int64]
     for n in HOST_SYMBOLS:
         getattr(L, n)
@@ -236,6 +258,125 @@ class Graph:
             self.seg_names = [L.phi_graph_seg_name(h, v).decode() for v in range(self.n_vtx)]
         finally:
             L.phi_graph_free(h)
+
+
+def parse_gt(text, text_off, gt_index, n_samples, rec_lo=0, rec_hi=None, gt=None, ploidy=None):
+    """phi_vcf_parse_gt: the exact scalar genotype parser over sample-column slices (every slice followed by a line feed).
+    -> (gt uint16 [records, n_samples, 2], ploidy int32 [n_samples]); rows outside [rec_lo, rec_hi) are left as passed in."""
+    text = np.ascontiguousarray(np.frombuffer(bytes(text), np.uint8) if not isinstance(text, np.ndarray) else text)
+    text_off = np.ascontiguousarray(text_off, np.int64)
+    gt_index = np.ascontiguousarray(gt_index, np.int32)
+    n_rec = len(text_off) - 1
+    gt = np.zeros((n_rec, n_samples, 2), np.uint16) if gt is None else gt
+    ploidy = np.zeros(n_samples, np.int32) if ploidy is None else ploidy
+    err = C.create_string_buffer(512)
+    rc = host_lib().phi_vcf_parse_gt(text.ctypes.data, text_off.ctypes.data, gt_index.ctypes.data, rec_lo, n_rec if rec_hi is None else rec_hi,
+                                     n_samples, gt.ctypes.data, ploidy.ctypes.data, err, 512)
+    if rc:
+        raise HostError(rc, err.value.decode())
+    return gt, ploidy
+
+
+class VcfGraph:
+    """A phased VCF + reference FASTA read by phi_vcf_read: the kept records (fixed columns), the sites and the sample-column
+    text; build(gt, ploidy, max_len) makes the graph of phi_amd.vcf2gfa -- the attributes of Graph, with walk_off / walk_vtx
+    None: Context.set_graph_vcf writes the walk entries on the device -- and the unit tables the device needs."""
+
+    def __init__(self, vcf_path, fasta_path):
+        L = host_lib()
+        self._L = L
+        self._h = C.c_void_p()
+        err = C.create_string_buffer(1024)
+        rc = L.phi_vcf_read(os.fsencode(vcf_path), os.fsencode(fasta_path), C.byref(self._h), err, 1024)
+        if rc:
+            raise HostError(rc, err.value.decode())
+        h = self._h
+        self.samples = [L.phi_vcf_sample_name(h, s).decode() for s in range(L.phi_vcf_n_samples(h))]
+        self.contig = L.phi_vcf_contig(h).decode()
+        self.n_records, self.n_sites = L.phi_vcf_n_records(h), L.phi_vcf_n_sites(h)
+        self.n_other_contig, self.n_ref_mismatch = L.phi_vcf_n_other_contig(h), L.phi_vcf_n_ref_mismatch(h)
+        n = self.n_records
+        self.ref_seq = _view(L.phi_vcf_ref_seq(h), L.phi_vcf_ref_len(h), C.c_uint8, np.uint8)
+        self.rec_start = _view(L.phi_vcf_rec_start(h), n, C.c_int64, np.int64)
+        self.rec_end = _view(L.phi_vcf_rec_end(h), n, C.c_int64, np.int64)
+        self.gt_index = _view(L.phi_vcf_rec_gt_index(h), n, C.c_int32, np.int32)
+        self.alt_off = _view(L.phi_vcf_rec_alt_off(h), n + 1, C.c_int64, np.int64)
+        self.alt_pos = _view(L.phi_vcf_alt_pos(h), int(self.alt_off[-1]) + 1, C.c_int64, np.int64)
+        self.alt_bytes = _view(L.phi_vcf_alt_bytes(h), int(self.alt_pos[-1]), C.c_uint8, np.uint8)
+        self.site_off = _view(L.phi_vcf_site_off(h), self.n_sites + 1, C.c_int64, np.int64)
+        self.text_off = _view(L.phi_vcf_text_off(h), n + 1, C.c_int64, np.int64)
+        self.text = _view(L.phi_vcf_text(h), int(self.text_off[-1]), C.c_uint8, np.uint8)
+
+    def warnings(self):
+        """The two warnings of vcf2gfa.read_vcf, in its words."""
+        out = []
+        if self.n_other_contig:
+            out.append(f"{self.n_other_contig} record(s) of other contigs than {self.contig} skipped (vcf2gfa handles one contig)")
+        if self.n_ref_mismatch:
+            out.append(f"{self.n_ref_mismatch} record(s) skipped: their REF column is not what the FASTA holds at POS (another assembly?)")
+        return out
+
+    def alts(self, r):
+        raw = self.alt_bytes.tobytes()
+        return [raw[self.alt_pos[a]:self.alt_pos[a + 1]] for a in range(int(self.alt_off[r]), int(self.alt_off[r + 1]))]
+
+    def parse_gt(self, rec_lo=0, rec_hi=None, gt=None, ploidy=None):
+        return parse_gt(self.text, self.text_off, self.gt_index, len(self.samples), rec_lo, rec_hi, gt, ploidy)
+
+    def build(self, gt, ploidy, max_len=30):
+        L, h = self._L, self._h
+        gt = np.ascontiguousarray(gt, np.uint16)
+        ploidy = np.ascontiguousarray(ploidy, np.int32)
+        assert gt.size == self.n_records * len(self.samples) * 2 and len(ploidy) == len(self.samples)
+        g = C.c_void_p()
+        err = C.create_string_buffer(1024)
+        rc = L.phi_vcf_build(h, gt.ctypes.data if gt.size else None, ploidy.ctypes.data if ploidy.size else None, max_len, C.byref(g), err, 1024)
+        if rc:
+            raise HostError(rc, err.value.decode())
+        try:
+            self.n_vtx = L.phi_graph_n_vtx(g)
+            self.num_walks = L.phi_graph_n_walks(g)
+            ne = L.phi_graph_n_edges(g)
+            self.seq_off = _view(L.phi_graph_seq_off(g), self.n_vtx + 1, C.c_int64, np.int64).copy()
+            self.seq_concat = _view(L.phi_graph_seq_concat(g), int(self.seq_off[-1]), C.c_uint8, np.uint8).copy()
+            self.adj_off = _view(L.phi_graph_adj_off(g), self.n_vtx + 1, C.c_int64, np.int64).copy()
+            self.adj = _view(L.phi_graph_adj(g), ne, C.c_int32, np.int32).copy()
+            self.top_order_map = _view(L.phi_graph_topo_rank(g), self.n_vtx, C.c_int32, np.int32).copy()
+            self.hap_id2name = [L.phi_graph_hap_name(g, w).decode() for w in range(self.num_walks)]
+        finally:
+            L.phi_graph_free(g)
+        self.walk_off = self.walk_vtx = None
+        self.n_units, self.n_real_sites = L.phi_vcf_n_units(h), L.phi_vcf_n_real_sites(h)
+        assert L.phi_vcf_n_kept_haps(h) == self.num_walks
+        self.unit_first = _view(L.phi_vcf_unit_first(h), self.n_units + 1, C.c_int32, np.int32).copy()
+        self.site_backbone = _view(L.phi_vcf_site_backbone(h), self.n_real_sites, C.c_int32, np.int32).copy()
+        self.site_allele0 = _view(L.phi_vcf_site_allele0(h), self.n_real_sites, C.c_int32, np.int32).copy()
+        self.choice = _view(L.phi_vcf_choice(h), self.n_real_sites * self.num_walks, C.c_int32, np.int32).copy().reshape(self.n_real_sites, self.num_walks)
+        return self
+
+    def host_walks(self):
+        """The walks the device writes, made here from the same tables (tests, and callers without a GPU): (walk_off, walk_vtx)."""
+        uw = np.empty((self.num_walks, 2 * self.n_real_sites + 1), np.int64)
+        uw[:, 0:-1:2] = self.site_backbone[None, :]
+        uw[:, 1::2] = (self.site_allele0[:, None] + self.choice).T
+        uw[:, -1] = self.n_units - 1
+        cnt = np.diff(self.unit_first.astype(np.int64))[uw]
+        walk_off = np.concatenate([[0], np.cumsum(cnt.sum(axis=1))]).astype(np.int64)
+        flat_u, flat_c = uw.ravel(), cnt.ravel()
+        start = np.repeat(self.unit_first[flat_u].astype(np.int64), flat_c)
+        within = np.arange(int(flat_c.sum()), dtype=np.int64) - np.repeat(np.cumsum(flat_c) - flat_c, flat_c)
+        return walk_off, (start + within).astype(np.int32)
+
+    def close(self):
+        if self._h:
+            self._L.phi_vcf_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class DeferredGraph:
