@@ -544,6 +544,53 @@ int phi_gfa_gzip_split(phi_ctx *ctx, const void *gz, int64_t n, int64_t chunk_by
                        phi_gfa_gzip_info *info);
 void phi_gfa_gzip_free(char *host_text);
 
+/*
+ * A ladder of coverages from ONE read set, sampled on the device.  Replaces data/preprocess.py:83-107 (seven
+ * `seqkit sample` files per sample) and data/run_batch_4.py:38-58 (one PHI process per (sample, coverage) pair): the read
+ * set is uploaded once, partitioned into nested bands by a per-read draw, and every base is scored once.
+ *
+ * The rule.  Read i (its 0-based ordinal in the order the reads reach the context) draws u_i = the upper 32 bits of output
+ * i + 1 of SplitMix64 seeded with `seed`.  Level j of fraction f_j has the threshold t_j = min(2^32, floor(f_j * 2^32)); the
+ * band of read i is the smallest j with u_i < t_j (none: the read is dropped); level j = bands 0..j.  A per-read Bernoulli
+ * draw, as `seqkit sample -p`: level sizes are not exact counts.
+ *
+ *   phi_reads_collect_begin    (data/preprocess.py:83-107, data/run_batch_4.py:38-58) from now on every reads route -- phi_add_reads,
+ *                              phi_add_reads_device, the text and the parked route -- appends its batches to a store on the device
+ *                              instead of scoring them: no read counter moves.  first_ordinal: the ordinal of the first read
+ *                              collected (shards of one read set; tests).  PHI_ERR_STATE while collecting or before phi_set_graph.
+ *   phi_reads_collect_end      (data/preprocess.py:83-107, data/run_batch_4.py:38-58) stops collecting; reads and bases in the store.
+ *                              PHI_ERR_STATE when not collecting.
+ *   phi_reads_collect_release  (data/preprocess.py:83-107, data/run_batch_4.py:38-58) frees the store and the plan.
+ *   phi_ladder_plan            (data/preprocess.py:83-107, data/run_batch_4.py:38-58) partitions the store, stably, into band order:
+ *                              band-major, inside a band by ordinal.  1 <= n_levels <= PHI_LADDER_MAX_LEVELS, fractions ascending and
+ *                              not negative (PHI_ERR_INVALID otherwise); PHI_ERR_STATE while collecting or without a store.
+ *   phi_ladder_advance         (data/preprocess.py:83-107, data/run_batch_4.py:38-58) scores the bands up to `level` that have not been
+ *                              scored since the last phi_reset_reads: the read state is then that of a context handed exactly
+ *                              level `level`'s reads.  PHI_ERR_STATE without a plan or for a level below one already scored.
+ *                              phi_reset_reads rewinds to "no band scored" and keeps the plan; phi_set_graph* drops store and plan.
+ *   phi_ladder_band            (data/preprocess.py:83-107, data/run_batch_4.py:38-58; tests) the ordinals of a band's reads in stored
+ *                              order into ordinals_out[0, cap) and, when not NULL, the band's bases and its reads + 1 offsets
+ *                              (from 0).  *n = the band's reads, *n_bases its bases, whatever cap is (nothing is copied to a
+ *                              buffer that is too small).
+ */
+#define PHI_LADDER_MAX_LEVELS 16
+typedef struct {
+    int32_t n_levels;
+    int32_t one_length;                              /* the store is of one read length (> 0: that length; 0: it is not) */
+    int64_t n_reads, n_bases;                        /* the store */
+    int64_t n_kept_reads, n_kept_bases;              /* all bands */
+    int64_t band_reads[PHI_LADDER_MAX_LEVELS], band_bases[PHI_LADDER_MAX_LEVELS];
+    uint64_t threshold[PHI_LADDER_MAX_LEVELS];
+    double count_gpu_ms, scan_gpu_ms, scatter_gpu_ms, copy_gpu_ms;   /* by events */
+} phi_ladder_info;
+int phi_reads_collect_begin(phi_ctx *ctx, int64_t first_ordinal);
+int phi_reads_collect_end(phi_ctx *ctx, int64_t *n_reads, int64_t *n_bases);
+int phi_reads_collect_release(phi_ctx *ctx);
+int phi_ladder_plan(phi_ctx *ctx, uint64_t seed, const double *fractions, int32_t n_levels, phi_ladder_info *info);
+int phi_ladder_advance(phi_ctx *ctx, int32_t level);
+int phi_ladder_band(phi_ctx *ctx, int32_t band, int64_t *ordinals_out, int64_t cap, int64_t *n,
+                    char *bases_out, int64_t bases_cap, int64_t *offsets_out, int64_t *n_bases);
+
 #ifdef __cplusplus
 }
 #endif

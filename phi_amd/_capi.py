@@ -34,7 +34,9 @@ SYMBOLS = [
     "phi_gfa_gzip_split", "phi_gfa_gzip_free",
     "phi_set_graph_chopped", "phi_chop_origin", "phi_chop_stats",
     "phi_vcf_genotypes", "phi_vcf_walks", "phi_vcf_stats",
+    "phi_reads_collect_begin", "phi_reads_collect_end", "phi_reads_collect_release", "phi_ladder_plan", "phi_ladder_advance", "phi_ladder_band",
 ]
+PHI_LADDER_MAX_LEVELS = 16
 PHI_INFLATE_NO_FINDER = 1
 PHI_INFLATE_CHUNK_DEFAULT = 64 << 10          # include/phi_amd.h
 
@@ -57,6 +59,14 @@ class PhiChopInfo(C.Structure):
 class PhiVcfInfo(C.Structure):
     _fields_ = [("text_bytes", C.c_int64), ("n_records", C.c_int64), ("n_samples", C.c_int32), ("n_flagged", C.c_int64),
                 ("n_units", C.c_int64), ("n_entries", C.c_int64), ("genotype_gpu_ms", C.c_double), ("walks_gpu_ms", C.c_double)]
+
+
+class PhiLadderInfo(C.Structure):
+    _fields_ = [("n_levels", C.c_int32), ("one_length", C.c_int32), ("n_reads", C.c_int64), ("n_bases", C.c_int64),
+                ("n_kept_reads", C.c_int64), ("n_kept_bases", C.c_int64),
+                ("band_reads", C.c_int64 * PHI_LADDER_MAX_LEVELS), ("band_bases", C.c_int64 * PHI_LADDER_MAX_LEVELS),
+                ("threshold", C.c_uint64 * PHI_LADDER_MAX_LEVELS),
+                ("count_gpu_ms", C.c_double), ("scan_gpu_ms", C.c_double), ("scatter_gpu_ms", C.c_double), ("copy_gpu_ms", C.c_double)]
 
 
 class PhiResult(C.Structure):
@@ -109,6 +119,12 @@ def load():
     L.phi_vcf_genotypes.argtypes = [vp, vp, i64, vp, vp, i64, i32, vp, vp, vp]
     L.phi_vcf_walks.argtypes = [vp, vp, i64, vp, vp, i64, vp, i32, vp]
     L.phi_vcf_stats.argtypes = [vp, C.POINTER(PhiVcfInfo)]
+    L.phi_reads_collect_begin.argtypes = [vp, i64]
+    L.phi_reads_collect_end.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
+    L.phi_reads_collect_release.argtypes = [vp]
+    L.phi_ladder_plan.argtypes = [vp, C.c_uint64, C.POINTER(C.c_double), i32, C.POINTER(PhiLadderInfo)]
+    L.phi_ladder_advance.argtypes = [vp, i32]
+    L.phi_ladder_band.argtypes = [vp, i32, vp, i64, C.POINTER(i64), vp, i64, vp, C.POINTER(i64)]
     L.phi_add_reads.argtypes = [vp, vp, vp, i64]
     L.phi_add_reads_device.argtypes = [vp, vp, vp, i64, i64]
     L.phi_reset_reads.argtypes = [vp]

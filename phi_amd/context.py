@@ -218,6 +218,81 @@ class Context:
     def reset_reads(self):
         self._chk(self._L.phi_reset_reads(self._h))
 
+    # ------------------------------------------------------------------ a ladder of coverages from one read set
+    def collect_begin(self, first_ordinal=0):
+        """From now on every reads route appends its batches to a store on the device instead of scoring them
+        (phi_reads_collect_begin); first_ordinal: the ordinal of the first read collected."""
+        self._chk(self._L.phi_reads_collect_begin(self._h, int(first_ordinal)))
+
+    def collect_end(self):
+        """Stops collecting: (reads, bases) in the store."""
+        nr, nb = C.c_int64(), C.c_int64()
+        self._chk(self._L.phi_reads_collect_end(self._h, C.byref(nr), C.byref(nb)))
+        return nr.value, nb.value
+
+    def collect_release(self):
+        self._chk(self._L.phi_reads_collect_release(self._h))
+
+    def ladder_plan(self, seed, fractions):
+        """Partitions the collected store into the bands of phi_amd.ladder's rule (phi_ladder_plan); returns phi_ladder_info
+        as a dict (band_reads, band_bases, threshold as lists of one entry per level)."""
+        f = (C.c_double * len(fractions))(*[float(x) for x in fractions])
+        info = _capi.PhiLadderInfo()
+        self._chk(self._L.phi_ladder_plan(self._h, C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), f, len(fractions), C.byref(info)))
+        d = {n: getattr(info, n) for n, _ in _capi.PhiLadderInfo._fields_}
+        for key in ("band_reads", "band_bases", "threshold"):
+            d[key] = list(d[key])[:info.n_levels]
+        return d
+
+    def ladder_advance(self, level):
+        """Scores the bands up to `level` not scored since the last reset_reads: the read state is then that of a context
+        handed exactly that level's reads."""
+        self._chk(self._L.phi_ladder_advance(self._h, int(level)))
+
+    def ladder_band(self, band, data=False):
+        """The ordinals (int64) of a band's reads in stored order; data=True: (ordinals, uint8 bases, int64 offsets)."""
+        n, nb = C.c_int64(), C.c_int64()
+        self._chk(self._L.phi_ladder_band(self._h, band, None, 0, C.byref(n), None, 0, None, C.byref(nb)))
+        ords = np.zeros(n.value, np.int64)
+        bases, off = np.zeros(nb.value, np.uint8), np.zeros(n.value + 1, np.int64)
+        self._chk(self._L.phi_ladder_band(self._h, band, _ptr(ords), n.value, C.byref(n), _ptr(bases) if data else None, nb.value,
+                                          off.ctypes.data if data else None, C.byref(nb)))
+        return (ords, bases, off) if data else ords
+
+    def coverage_ladder(self, reads, coverages, genome_size, seed=0, text=False):
+        """One read set inferred at a ladder of coverages (ascending; the reference: data/preprocess.py:83-107 +
+        data/run_batch_4.py:38-58): the set is uploaded once, sampled on the device and every base scored once.  reads: a
+        list of sequences (or (concat, offsets)) for add_reads, or with text=True an iterable of pieces of FASTA / FASTQ text
+        for the text route (which must take all of it).  Yields one dict per level: solve()'s result plus coverage, fraction,
+        n_reads and n_bases of the level; the context holds that level's state while the caller looks at it."""
+        from . import ladder as _ladder
+        self.reset_reads()
+        self.collect_begin(0)
+        try:
+            if text:
+                self.reads_text_begin()
+                for piece in reads:
+                    if self.add_reads_text(piece):
+                        raise ValueError("coverage_ladder: the reads text is irregular (parse it on the host and pass sequences)")
+                pending, _ = self.reads_text_end()
+                tail = _parse_reads_tail(pending)                 # (the device leaves the last record: nothing told it that it had ended)
+                if tail:
+                    self.add_reads(tail)
+            else:
+                self.add_reads(reads)
+        finally:
+            _, total_bases = self.collect_end()
+        fr = _ladder.fractions_from_coverage(coverages, genome_size, total_bases)
+        info = self.ladder_plan(seed, fr)
+        nr = nb = 0
+        for j, cv in enumerate(coverages):
+            self.ladder_advance(j)
+            nr += info["band_reads"][j]
+            nb += info["band_bases"][j]
+            res = self.solve()
+            res.update(coverage=cv, fraction=fr[j], n_reads=nr, n_bases=nb)
+            yield res
+
     def reads_stats(self):
         a, b, e, d = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
         self._chk(self._L.phi_reads_stats(self._h, C.byref(a), C.byref(b), C.byref(e), C.byref(d)))
@@ -486,6 +561,28 @@ class Context:
         n, ms, b = C.c_int64(), C.c_double(), C.c_int64()
         self._chk(self._L.phi_prof_read(self._h, C.byref(n), C.byref(ms), C.byref(b)))
         return n.value, ms.value, b.value
+
+
+def _parse_reads_tail(text):
+    """The sequences of the few whole records a reads text ends with (FASTA, or FASTQ with four lines per record)."""
+    lines = [ln.rstrip(b"\r") for ln in text.split(b"\n")]
+    while lines and not lines[-1]:
+        lines.pop()
+    if not lines:
+        return []
+    if lines[0][:1] == b"@":
+        if len(lines) % 4:
+            raise ValueError("the reads text ends inside a FASTQ record")
+        return lines[1::4]
+    if lines[0][:1] != b">":
+        raise ValueError("the reads text is neither FASTA nor FASTQ")
+    seqs = []
+    for ln in lines:
+        if ln[:1] == b">":
+            seqs.append([])
+        else:
+            seqs[-1].append(ln)
+    return [b"".join(s) for s in seqs]
 
 
 def _info(info):

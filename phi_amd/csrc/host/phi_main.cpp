@@ -4,6 +4,7 @@
 //
 //   ./PHI -g <target.gfa> -r <reads.fa> -o <haplotype.fasta> [-k -w -R -q -m -T -t -d -N -c]
 //         [--device N | --devices 0,1,..] [--dp-budget RUNS]
+//         [--coverage C0,C1,.. --genome-size N [--seed S]]   (-o 'out.{cov}x.fa': one FASTA per coverage)
 //   ./PHI -g <target.gfa> -r a.fq -o a.fa -r b.fq -o b.fa ...      several read sets against ONE graph: the graph is parsed and
 //         indexed once (the reference's harness runs PHI once per sample x coverage on the same graph,
 //         data/run_batch_4_miqp.py:31-46), every job prints the log of a run of its own and writes its own FASTA
@@ -140,6 +141,12 @@ struct Options {
     bool from_vcf = false;
     int vcf_max_len = 30;                                     // its segments' length (--chop N; gfa2gbwt -m 30, vcf2gfa.py:53)
     std::vector<std::string> reads_files, hap_files;          // one entry per job: -r a -o a.fa -r b -o b.fa ...
+    // --coverage C0,C1,.. --genome-size N [--seed S]: every read set is inferred at a ladder of coverages (data/preprocess.py:83-107,
+    // data/run_batch_4.py:38-58): collected once, sampled on the device, one FASTA per level (-o names them through {cov})
+    std::vector<std::string> cov_names;                       // as written on the command line
+    std::vector<double> cov;
+    double genome_size = 0.0;
+    unsigned long long seed = 0;
     int argc = 0;
     char **argv = nullptr;
     bool detached = false;
@@ -838,12 +845,46 @@ struct Driver {
             if (run_on_all("reset", [&](int, phi_ctx *cx) -> int { return phi_reset_reads(cx); })) return 1;
             loaded();
         }
+        const bool ladder = !o.cov.empty();                  // (one GPU: main refuses --coverage with --devices of several)
+        int rc;
+        if (ladder && (rc = phi_reads_collect_begin(ctx, 0))) return fail_on(ctx, "collect", rc);
         if (Stage st("reads: text -> device, records, sketch"); run_on_all("reads", [&](int, phi_ctx *cx) -> int { return feed_reads(cx); })) return 1;
         if (feed.reader.get() != PHI_HOST_OK) return fail("[E::main] %s\n", feed.err);
+        if (ladder) return run_ladder();
         if (n_dev > 1) {
             Stage st(use_peers ? "exchange (peer-mapped)" : "exchange (RCCL)");
             if (run_on_all("exchange", [&](int, phi_ctx *cx) -> int { return use_peers ? phi_peers_exchange(cx) : phi_comm_exchange(cx); })) return 1;
         }
+        return solve_and_report();
+    }
+    // ---- the read set as collected: plan, then per level advance, solve, FASTA (what a plain run logs, behind one line per level)
+    int run_ladder()
+    {
+        int rc, status = 0;
+        int64_t n_reads = 0, n_bases = 0;
+        if ((rc = phi_reads_collect_end(ctx, &n_reads, &n_bases))) return fail_on(ctx, "collect", rc);
+        std::vector<double> fr;
+        for (double cv : o.cov) fr.push_back(n_bases > 0 ? std::min(1.0, cv * o.genome_size / (double)n_bases) : 1.0);
+        phi_ladder_info li;
+        if (Stage st("ladder plan (count, scan, scatter, copy)"); (rc = phi_ladder_plan(ctx, o.seed, fr.data(), (int32_t)fr.size(), &li))) return fail_on(ctx, "ladder plan", rc);
+        const std::string pattern = hap_file;
+        int64_t lr = 0, lb = 0;
+        for (size_t j = 0; j < fr.size(); j++) {
+            if (Stage st("ladder advance"); (rc = phi_ladder_advance(ctx, (int32_t)j))) return fail_on(ctx, "ladder advance", rc);
+            lr += li.band_reads[j]; lb += li.band_bases[j];
+            hap_file = pattern;
+            for (size_t at; (at = hap_file.find("{cov}")) != std::string::npos;) hap_file.replace(at, 5, o.cov_names[j]);
+            fprintf(stderr, "Coverage %sx: fraction %.6f, %lld reads, %lld bases\n", o.cov_names[j].c_str(), fr[j], (long long)lr, (long long)lb);
+            const int r = solve_and_report();
+            if (r == 1) return 1;
+            if (r) status = r;
+        }
+        hap_file = pattern;
+        if ((rc = phi_reads_collect_release(ctx))) return fail_on(ctx, "collect release", rc);
+        return status;
+    }
+    int solve_and_report()
+    {
         int64_t total_reads = 0;
         int rc;
         for (phi_ctx *cx : ctxs) {
@@ -934,7 +975,8 @@ int main(int argc, char *argv[])
     Options o;
     int help = 0;
     static struct option long_options[] = {{"version", no_argument, 0, 300}, {"device", required_argument, 0, 301}, {"dp-budget", required_argument, 0, 302},
-                                           {"devices", required_argument, 0, 303}, {"shard-min-bases", required_argument, 0, 304}, {"chop", required_argument, 0, 305}, {"vcf", required_argument, 0, 306}, {"ref", required_argument, 0, 307}, {0, 0, 0, 0}};
+                                           {"devices", required_argument, 0, 303}, {"shard-min-bases", required_argument, 0, 304}, {"chop", required_argument, 0, 305}, {"vcf", required_argument, 0, 306}, {"ref", required_argument, 0, 307},
+                                           {"coverage", required_argument, 0, 308}, {"genome-size", required_argument, 0, 309}, {"seed", required_argument, 0, 310}, {0, 0, 0, 0}};
     int c;
     std::string gfa_arg, vcf_arg;
     // main.cpp:38 declares -h with an argument; a bare -h falls into the usage branch either way
@@ -959,6 +1001,20 @@ int main(int argc, char *argv[])
         else if (c == 301) o.device = atoi(optarg);
         else if (c == 302) o.dp_budget = atoll(optarg);
         else if (c == 305) { o.chop = atoi(optarg); if (o.chop < 1) { fprintf(stderr, "[E::main] --chop takes a segment length of at least 1\n"); return 1; } }
+        else if (c == 308) {                                   // --coverage 0.1,0.5,1,...: ascending
+            o.cov.clear(); o.cov_names.clear();
+            for (const char *p = optarg; *p;) {
+                char *end = nullptr;
+                const double v = strtod(p, &end);
+                if (end == p || !(v >= 0.0) || (*end && *end != ',')) { fprintf(stderr, "[E::main] --coverage takes a comma-separated list of coverages, e.g. 0.1,0.5,1,2,5,10,15\n"); return 1; }
+                if (!o.cov.empty() && v < o.cov.back()) { fprintf(stderr, "[E::main] --coverage: the coverages must ascend (%s follows %s)\n", std::string(p, (const char *)end).c_str(), o.cov_names.back().c_str()); return 1; }
+                o.cov.push_back(v); o.cov_names.emplace_back(p, (const char *)end);
+                p = *end == ',' ? end + 1 : end;
+            }
+            if (o.cov.empty() || o.cov.size() > 16) { fprintf(stderr, "[E::main] --coverage takes 1 to 16 coverages\n"); return 1; }
+        }
+        else if (c == 309) o.genome_size = atof(optarg);
+        else if (c == 310) o.seed = strtoull(optarg, nullptr, 10);
         else if (c == 304) o.shard_min_bases = std::max<long long>(1, atoll(optarg));
         else if (c == 303) {                                   // --devices 0,1,2,...: shard the reads over these GPUs
             o.devices.clear();
@@ -981,6 +1037,13 @@ int main(int argc, char *argv[])
         return 1;
     }
     if (o.reads_files.size() != o.hap_files.size()) { fprintf(stderr, "[E::main] %zu -r but %zu -o: several read sets against one graph are given as -r a.fq -o a.fa -r b.fq -o b.fa ...\n", o.reads_files.size(), o.hap_files.size()); return 1; }
+    if (!o.cov.empty()) {
+        if (!(o.genome_size > 0.0)) { fprintf(stderr, "[E::main] --coverage needs --genome-size N (the bases of the region the coverages refer to)\n"); return 1; }
+        if (o.devices.size() > 1) { fprintf(stderr, "[E::main] --coverage runs on one GPU: not together with --devices of several (sharded ladders are not supported)\n"); return 1; }
+        if (o.cov.size() > 1)
+            for (const std::string &h : o.hap_files)
+                if (h.find("{cov}") == std::string::npos) { fprintf(stderr, "[E::main] --coverage with several coverages: -o must contain {cov} (got %s), e.g. -o 'out.{cov}x.fa'\n", h.c_str()); return 1; }
+    } else if (o.genome_size != 0.0) { fprintf(stderr, "[E::main] --genome-size goes with --coverage\n"); return 1; }
     o.argc = argc; o.argv = argv;
     t0_real = realtime();
 

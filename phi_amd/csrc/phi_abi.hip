@@ -251,6 +251,8 @@ int phi_read_counts(phi_ctx *c, uint64_t *n_logged, uint64_t *n_emitted)
     return PHI_OK;
 }
 
+void phi_dev_free(DevBuf &b) { dev_free(b); }
+
 static uint64_t pow2_at_least(uint64_t x) { uint64_t p = 1; while (p < x) p <<= 1; return p; }
 
 // a device buffer that grows and KEEPS its first `keep` bytes
@@ -271,6 +273,7 @@ static int dev_grow_keep(phi_ctx *c, DevBuf &b, size_t bytes, size_t keep)
     b = nb;
     return PHI_OK;
 }
+int phi_dev_grow_keep(phi_ctx *c, DevBuf &b, size_t bytes, size_t keep) { return dev_grow_keep(c, b, bytes, keep); }
 
 static int sp_set_size(phi_ctx *c, uint64_t *n)
 {
@@ -493,6 +496,7 @@ void phi_ctx_destroy(phi_ctx *c)
     (void)phi_ipc_destroy(c);
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
+    phi_ladder_drop(c);
     DevBuf *all[] = {&c->d_anchors, &c->d_cov_all, &c->d_cov_w, &c->d_slots, &c->d_slots2, &c->d_segs, &c->d_ctr, &c->d_vmax, &c->d_lane_walk, &c->d_walk_lane, &c->d_coff, &c->d_blk_ncls, &c->d_rownew, &c->d_blk_bad, &c->d_seg_lo, &c->d_seg_row, &c->d_seg_S, &c->wtext.d_text, &c->d_sel_off, &c->d_sel_tri, &c->d_blk_lo, &c->d_blk_ev, &c->d_blk_S, &c->d_row_out, &c->d_rowend, &c->d_blk_keys, &c->d_blk_carry, &c->d_cov, &c->d_cov2, &c->d_stepdiff, &c->alt.hit, &c->hit_extra[0], &c->hit_extra[1], &c->alt.stripes, &c->d_sp_cnt, &c->d_novlog, &c->d_novcnt, &c->d_ovlist, &c->d_vlen, &c->d_ent_cls, &c->d_cls_rep, &c->d_cls_left, &c->d_cls_mult, &c->d_cls_base, &c->d_cls_rec_off, &c->d_rec_cls, &c->d_rec_rel, &c->d_u_replist, &c->d_adj_off, &c->d_adj, &c->d_topo_rank, &c->d_cnt_edge, &c->d_walk_err, &c->d_sa_cnt, &c->d_sa_cur, &c->d_sa_off, &c->d_sa_idx, &c->d_seq, &c->d_seq_off, &c->d_walk_vtx, &c->d_walk_off, &c->d_topo, &c->d_in_off,
                      &c->d_in_src, &c->d_e_out, &c->d_st_rec, &c->d_st_mask, &c->d_in_packed, &c->d_word, &c->d_wwords, &c->d_wbad,
                      &c->d_wascii, &c->d_wstarts, &c->d_rec_hash, &c->d_rec_pos, &c->d_rec_slot,
@@ -792,6 +796,7 @@ static int set_graph_check_args(phi_ctx *c, int32_t n_vtx, const char *seq_conca
     c->have_graph = false;
     c->chop.on = false;
     c->solved = false;
+    phi_ladder_drop(c);                                        // (a collected read set and its bands belong to the graph they were collected under)
     return PHI_OK;
 }
 static int set_graph_check_offsets(phi_ctx *c, int32_t n_vtx, const int64_t *seq_off, const int64_t *adj_off, int32_t n_walks, const int64_t *walk_off)
@@ -1658,6 +1663,7 @@ int phi_add_reads_device_impl(phi_ctx *c, const void *d_bases, const void *d_rea
     if (!c) return PHI_ERR_INVALID;
     if (!c->have_graph) return phi_fail(c, PHI_ERR_STATE, "phi_add_reads before phi_set_graph");
     if (n_reads < 0 || n_bases < 0 || (n_bases > 0 && !d_bases)) return phi_fail(c, PHI_ERR_INVALID, "phi_add_reads: bad arguments");
+    if (__builtin_expect(c->ladder.collecting, 0)) return phi_ladder_collect(c, d_bases, d_read_off, n_reads, n_bases);   // phi_reads_collect_begin: kept, not scored
     // no offsets: reads of one length, n_bases / n_reads each
     int64_t uniform_len = 0;
     if (!d_read_off && n_reads > 0 && n_bases > 0) {
@@ -1789,6 +1795,17 @@ static int replay_if_full(phi_ctx *c, uint32_t err, const void *d_bases, const v
         PHICHK(phi_add_reads_device_impl(c, d_bases, d_off, n_reads, n_bases, true));
         HIPCHK(phi_copy_sync(c, &err, scalar(c, S_ERR), 4, hipMemcpyDeviceToHost));
     }
+    return PHI_OK;
+}
+
+int phi_score_resident_batch(phi_ctx *c, const void *d_bases, const void *d_read_off, int64_t n_reads, int64_t n_bases)
+{
+    if (c->async_batches) { PHICHK(phi_sync_check(c)); c->async_batches = false; }   // (a replay below must only ever concern THIS batch)
+    if (!c->h_err) HIPCHK(hipHostMalloc((void **)&c->h_err, 64, hipHostMallocDefault));
+    PHICHK(phi_add_reads_device_impl(c, d_bases, d_read_off, n_reads, n_bases, false));
+    HIPCHK(hipMemcpyAsync(c->h_err, scalar(c, S_ERR), 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (*c->h_err & PHI_KERR_TABLE_FULL) PHICHK(replay_if_full(c, *c->h_err, d_bases, d_read_off, n_reads, n_bases));
     return PHI_OK;
 }
 
@@ -2296,6 +2313,7 @@ int phi_reset_reads(phi_ctx *c)
     c->log_chunks = c->log_done = 0; c->logged_done = 0; c->ov_done = 0; c->ov_bound = 0; c->last_log_chunks = 0;
     c->reads_bases = 0; c->reads_count = 0; c->spectrum_override = -1;
     c->solved = false;
+    c->ladder.scored = 0;                                      // (phi_ladder_advance starts over; the plan stays)
     return PHI_OK;
 }
 

@@ -202,6 +202,21 @@ struct phi_ctx {
         uint32_t why = 0, first_bad = 0;
     } text;
 
+    // ---- a ladder of coverages from one read set (ladder.hip): the collected store, and its partition into bands
+    struct PhiLadder {
+        bool collecting = false, have_store = false, have_plan = false;
+        int64_t first_ordinal = 0;
+        int64_t n_reads = 0, n_bases = 0;             // the store
+        int64_t one_len = -1;                         // -1 nothing collected yet, -2 reads of several lengths, else the one length
+        DevBuf d_bases, d_off;                        // the store: bases in arrival order, n_reads + 1 offsets (64-bit)
+        // the plan: bases band-major (every band starts on a 256-byte border), per band reads + 1 offsets from 0, and per
+        // kept read its index in the store and where its bases lie there
+        DevBuf d_pbases, d_poff, d_pidx, d_psrc, d_wg, d_tab;
+        int64_t band_read0[PHI_LADDER_MAX_LEVELS + 1] = {0}, band_pos[PHI_LADDER_MAX_LEVELS + 1] = {0};
+        int32_t scored = 0;                           // bands scored since the last phi_reset_reads
+        phi_ladder_info info{};
+    } ladder;
+
     // ---- scratch for sketch passes and compaction
     DevBuf d_blk_cnt, d_blk_off, d_flags, d_flags2, d_list, d_list2, d_list3, d_walk_last;
     DevBuf d_sel_off, d_sel_tri;                       // the filter's selected class records, packed per class (phi_solve: the anchors are expanded from these)
@@ -358,6 +373,13 @@ int phi_add_reads_device_impl(phi_ctx *c, const void *d_bases, const void *d_rea
 // helpers shared between phi_abi.hip and phi_solve.hip
 int phi_fail(phi_ctx *c, int code, const char *fmt, ...);
 int phi_dev_ensure(phi_ctx *c, DevBuf &b, size_t bytes);
+int phi_dev_grow_keep(phi_ctx *c, DevBuf &b, size_t bytes, size_t keep);   // grows and KEEPS the first `keep` bytes
+void phi_dev_free(DevBuf &b);
+// ladder.hip
+int phi_ladder_collect(phi_ctx *c, const void *d_bases, const void *d_read_off, int64_t n_reads, int64_t n_bases);   // the hook of phi_add_reads_device_impl
+void phi_ladder_drop(phi_ctx *c);                      // store and plan let go (a new graph, the context's end)
+// a batch whose data stays where it is: scored, waited for, and replayed if the overflow list of novel hashes ran full
+int phi_score_resident_batch(phi_ctx *c, const void *d_bases, const void *d_read_off, int64_t n_reads, int64_t n_bases);
 void phi_pool_flush(int device);                    // the pool of large device buffers let go (phi_abi.hip) back to the driver
 int phi_hip_check(phi_ctx *c, hipError_t e, const char *what);
 int phi_sync_check(phi_ctx *c);
