@@ -31,6 +31,7 @@
 #include <algorithm>
 #include <vector>
 #include "../../include/phi_amd.h"
+#include "phi_ctx.h"
 
 #define INF_TB 10               // first-level table bits of the literal/length and distance codes
 #define INF_SEG 4096            // CRC segment
@@ -619,6 +620,7 @@ struct Dev {
         void *p = nullptr;
         if (hipMalloc(&p, std::max<size_t>(bytes, 16)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
         bufs.push_back(p);
+        if (phi_dev_poison(p, std::max<size_t>(bytes, 16))) return nullptr;
         return (T *)p;
     }
 };

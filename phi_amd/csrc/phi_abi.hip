@@ -51,7 +51,10 @@ int phi_hip_check(phi_ctx *c, hipError_t e, const char *what)
 namespace {
 struct DevPool { std::mutex mu; std::vector<DevBuf> bufs; };
 DevPool g_pool[64];
-// (PHI_DEVICE_POOL_MIN=bytes: tests pool everything, so that every buffer comes back with an earlier owner's contents)
+// (PHI_DEVICE_POOL_MIN=bytes: tests pool everything, so that every buffer comes back with an earlier owner's contents;
+//  PHI_DEVICE_POISON=0..255: tests fill every buffer with that byte when it gets a new owner -- phi_dev_poison of phi_ctx.h,
+//  tests/test_gpu_dirty_memory.py runs the small shapes of every kernel family under both.  Not for groups of processes:
+//  the mailbox of phi_ipc.hip is left alone)
 const size_t POOL_MIN = getenv("PHI_DEVICE_POOL_MIN") ? (size_t)atoll(getenv("PHI_DEVICE_POOL_MIN")) : ((size_t)16 << 20);
 thread_local bool t_pool_bypass = false;
 bool pool_on()
@@ -73,7 +76,23 @@ bool pool_take(int dev, size_t want, DevBuf &b)
     P.bufs.erase(P.bufs.begin() + best);
     return true;
 }
+int poison_from_env()
+{
+    const char *e = getenv("PHI_DEVICE_POISON");
+    if (!e || !*e) return -1;
+    char *end = nullptr;
+    const long v = strtol(e, &end, 0);
+    return (*end || v < 0 || v > 255) ? -1 : (int)v;
+}
 }  // namespace
+const int phi_device_poison = poison_from_env();
+// (the null stream, and a wait for it: the mode is for tests, and the buffer has no other user yet)
+int phi_dev_poison_fill(void *p, size_t bytes)
+{
+    if (!p || !bytes) return 0;
+    if (hipMemset(p, phi_device_poison, bytes) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) { (void)hipGetLastError(); return 1; }
+    return 0;
+}
 void phi_pool_flush(int dev)
 {
     if (dev < 0 || dev >= 64) return;
@@ -104,9 +123,14 @@ static void dev_free(DevBuf &b)
 int phi_dev_ensure(phi_ctx *c, DevBuf &b, size_t bytes)
 {
     if (bytes <= b.cap && b.p) return PHI_OK;
+    const uint32_t gen = b.gen + 1;                        // (the memory behind b changes hands below, whatever address it gets)
     dev_free(b);
     size_t want = bytes < 256 ? 256 : bytes;
-    if (want >= POOL_MIN && pool_on() && pool_take(c->device, want, b)) return PHI_OK;
+    if (want >= POOL_MIN && pool_on() && pool_take(c->device, want, b)) {
+        b.gen = gen;
+        if (phi_dev_poison(b.p, b.cap)) return phi_fail(c, PHI_ERR_DEVICE, "PHI_DEVICE_POISON: the fill of %zu bytes failed", b.cap);
+        return PHI_OK;
+    }
     static const bool timing = getenv("PHI_TIMING_ALLOC") != nullptr;
     const auto t0 = std::chrono::steady_clock::now();
     hipError_t e = hipMalloc(&b.p, want);
@@ -123,6 +147,8 @@ int phi_dev_ensure(phi_ctx *c, DevBuf &b, size_t bytes)
     }
     if (e != hipSuccess) { b.p = nullptr; return phi_fail(c, PHI_ERR_NOMEM, "hipMalloc(%zu bytes) failed: %s", want, hipGetErrorString(e)); }
     b.cap = want;
+    b.gen = gen;
+    if (phi_dev_poison(b.p, b.cap)) return phi_fail(c, PHI_ERR_DEVICE, "PHI_DEVICE_POISON: the fill of %zu bytes failed", b.cap);
     return PHI_OK;
 }
 
@@ -260,6 +286,7 @@ static int dev_grow_keep(phi_ctx *c, DevBuf &b, size_t bytes, size_t keep)
 {
     if (bytes <= b.cap && b.p) return PHI_OK;
     DevBuf nb;
+    nb.gen = b.gen;                                        // (b's generation goes on counting through the exchange below)
     int rc = phi_dev_ensure(c, nb, bytes);
     if (rc) return rc;
     if (b.p && keep) {
@@ -435,6 +462,7 @@ int phi_ctx_create(int device_id, phi_ctx **out)
         void *d = nullptr;
         std::vector<char> h((size_t)1 << 20, 0);
         if (hipMalloc(&d, h.size()) == hipSuccess) {
+            (void)phi_dev_poison(d, h.size());
             (void)hipMemcpyAsync(d, h.data(), h.size(), hipMemcpyHostToDevice, c->aux_stream);
             (void)hipMemcpyAsync(h.data(), d, h.size(), hipMemcpyDeviceToHost, c->aux_stream);
             (void)hipMemcpyAsync(d, h.data(), 64, hipMemcpyHostToDevice, c->aux_stream);
@@ -2075,6 +2103,7 @@ int phi_text_park_add_async(phi_text_park *p, const char *text, int64_t n, int32
         if (hipMalloc(&pc.d.p, want) != hipSuccess) { (void)hipGetLastError(); return PHI_ERR_NOMEM; }
         pc.d.cap = want;
     }
+    if (phi_dev_poison(pc.d.p, pc.d.cap)) { (void)hipFree(pc.d.p); return PHI_ERR_DEVICE; }
     pc.n = n; pc.first = text[0];
     if (hipEventCreateWithFlags(&pc.ev, hipEventDisableTiming) != hipSuccess ||
         hipMemcpyAsync(pc.d.p, text, (size_t)n, hipMemcpyHostToDevice, p->stream) != hipSuccess || hipEventRecord(pc.ev, p->stream) != hipSuccess) {
@@ -2197,6 +2226,7 @@ int phi_text_park_gzip_end(phi_text_park *p, int32_t *first, int32_t *count, phi
             if (hipMalloc(&pc.d.p, want) != hipSuccess) { (void)hipGetLastError(); rc = PHI_ERR_NOMEM; break; }
             pc.d.cap = want;
         }
+        if (phi_dev_poison(pc.d.p, pc.d.cap)) { (void)hipFree(pc.d.p); rc = PHI_ERR_DEVICE; break; }
         pc.n = n;
         if (hipMemcpy(&pc.first, (char *)d + at, 1, hipMemcpyDeviceToHost) != hipSuccess ||
             hipEventCreateWithFlags(&pc.ev, hipEventDisableTiming) != hipSuccess ||

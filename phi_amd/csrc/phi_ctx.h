@@ -20,6 +20,7 @@
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
+    uint32_t gen = 0;        // bumped by phi_dev_ensure whenever the memory behind p changes hands (a new allocation, a buffer from the pool)
     template <class T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
@@ -375,6 +376,13 @@ int phi_fail(phi_ctx *c, int code, const char *fmt, ...);
 int phi_dev_ensure(phi_ctx *c, DevBuf &b, size_t bytes);
 int phi_dev_grow_keep(phi_ctx *c, DevBuf &b, size_t bytes, size_t keep);   // grows and KEEPS the first `keep` bytes
 void phi_dev_free(DevBuf &b);
+// PHI_DEVICE_POISON=<0..255> (tests; read once at load, -1 = unset): every device buffer is filled with that byte over its whole
+// capacity when it gets a new owner, and the fill is complete on the device before the buffer is handed on.  Called wherever
+// device memory changes hands: phi_dev_ensure, the text park's pieces, the inflater's buffers.  Not meant for groups of
+// processes (phi_ipc.hip): their mailbox is not poisoned.
+extern const int phi_device_poison;
+int phi_dev_poison_fill(void *p, size_t bytes);         // 0 = filled
+static inline int phi_dev_poison(void *p, size_t bytes) { return phi_device_poison < 0 ? 0 : phi_dev_poison_fill(p, bytes); }
 // ladder.hip
 int phi_ladder_collect(phi_ctx *c, const void *d_bases, const void *d_read_off, int64_t n_reads, int64_t n_bases);   // the hook of phi_add_reads_device_impl
 void phi_ladder_drop(phi_ctx *c);                      // store and plan let go (a new graph, the context's end)

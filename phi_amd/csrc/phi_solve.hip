@@ -192,10 +192,11 @@ static int dp_prepare_blocks(phi_ctx *c, int64_t n_dp)
         // use, without looking: that must be a value NEGK can be added to -- not what an earlier owner of the memory left there
         // (found when a freed buffer of segment rows, holding sums of two NEGK, came back as this table: NEGK + INT32_MIN wraps
         // into a valid key).  A table allocated anew is filled with 0xC0C0C0C0 (below NEGK / 2, and NEGK plus it stays inside
-        // int32); afterwards only keys and NEGK are written into it.
-        const void *before = c->d_row_out.p;
+        // int32); afterwards only keys and NEGK are written into it.  "Anew" is the buffer's generation, not its address: a
+        // table below the pool's threshold goes back to the driver, and the larger one may come back at the same address.
+        const uint32_t before = c->d_row_out.gen;
         PHICHK(phi_dev_ensure(c, c->d_row_out, nbk * nrow * 64 * 4));
-        if (c->d_row_out.p != before) HIPCHK(hipMemsetAsync(c->d_row_out.p, 0xC0, c->d_row_out.cap, c->stream));
+        if (c->d_row_out.gen != before) HIPCHK(hipMemsetAsync(c->d_row_out.p, 0xC0, c->d_row_out.cap, c->stream));
     }
     PHICHK(phi_dev_ensure(c, c->d_rowend, nbk * nrow * 4));
     if (cls) {
