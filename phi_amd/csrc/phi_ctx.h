@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include "../../include/phi_amd.h"
 #include "phi_kernels.h"
+#include "phi_host_par.h"          // phi_host_threads, phi_parallel_chunks, PhiHostError (no HIP: shared with dp_steps.h)
 
 // growable device buffer
 struct DevBuf {
@@ -313,69 +314,48 @@ static inline int32_t phi_entry_walk(const phi_ctx *c, int64_t e)
     return (int32_t)(std::upper_bound(c->h_walk_off.begin(), c->h_walk_off.end(), e) - c->h_walk_off.begin()) - 1;
 }
 
-// ---- host threads for the O(walk entries) preparation of phi_set_graph
-static inline int phi_host_threads()
-{
-    const char *e = getenv("PHI_HOST_THREADS");
-    int n = e ? atoi(e) : (int)std::thread::hardware_concurrency();
-    if (n < 1) n = 1;
-    return n > 16 ? 16 : n;
-}
-
-// fn(lo, hi, worker) over [0, n) in chunks handed out dynamically; worker < phi_host_threads()
-template <class F> static void phi_parallel_chunks(int64_t n, int64_t chunk, F fn)
-{
-    const int64_t n_chunks = (n + chunk - 1) / chunk;
-    int nt = phi_host_threads();
-    if (nt > n_chunks) nt = (int)n_chunks;
-    if (nt <= 1) {
-        for (int64_t i = 0; i < n_chunks; i++) fn(i * chunk, std::min(n, (i + 1) * chunk), 0);
-        return;
-    }
-    std::atomic<int64_t> next{0};
-    auto work = [&](int worker) {
-        for (;;) {
-            const int64_t i = next.fetch_add(1, std::memory_order_relaxed);
-            if (i >= n_chunks) break;
-            fn(i * chunk, std::min(n, (i + 1) * chunk), worker);
-        }
-    };
-    std::vector<std::thread> th;
-    for (int t = 1; t < nt; t++) th.emplace_back(work, t);
-    work(0);
-    for (auto &t : th) t.join();
-}
-
-// first error raised by any worker
-struct PhiHostError {
-    std::atomic<int> flag{0};
-    std::mutex m;
-    int code = 0;
-    std::string msg;
-    bool failed() const { return flag.load(std::memory_order_relaxed) != 0; }
-    void set(int code_, const char *fmt, ...)
-    {
-        std::lock_guard<std::mutex> g(m);
-        if (flag.load()) return;
-        char buf[512];
-        va_list ap;
-        va_start(ap, fmt);
-        vsnprintf(buf, sizeof buf, fmt, ap);
-        va_end(ap);
-        code = code_; msg = buf;
-        flag.store(1);
-    }
-};
-
 // phi_solve.cpp: host orchestration of the exact solve on top of the DP kernel
 int phi_solve_impl(phi_ctx *c);
 // one batch of reads the device can address; replay: the same batch again after the spectrum set was regrown
 int phi_add_reads_device_impl(phi_ctx *c, const void *d_bases, const void *d_read_off, int64_t n_reads, int64_t n_bases, bool replay);
-// helpers shared between phi_abi.hip and phi_solve.hip
+// helpers of phi_abi.hip shared with the files that keep a feature's host glue beside its kernels (set_graph.hip, chop.hip,
+// vcf.hip, ladder.hip) and with phi_solve.hip
 int phi_fail(phi_ctx *c, int code, const char *fmt, ...);
 int phi_dev_ensure(phi_ctx *c, DevBuf &b, size_t bytes);
 int phi_dev_grow_keep(phi_ctx *c, DevBuf &b, size_t bytes, size_t keep);   // grows and KEEPS the first `keep` bytes
-void phi_dev_free(DevBuf &b);
+void phi_dev_free(DevBuf &b);                          // to the pool of large buffers or back to the driver (waits for the device)
+// temporaries of one call: let go, through phi_dev_free, when the scope ends
+struct PhiDevGuard {
+    std::vector<DevBuf *> b;
+    ~PhiDevGuard() { for (DevBuf *x : b) phi_dev_free(*x); }
+};
+// scalar slots in d_scalars (8 bytes each)
+enum { S_ERR = 0, S_NBAD = 1, S_BATCHBAD = 2, S_NEMIT = 3, S_FILTERED = 4, S_INMODEL = 5, S_EXPORT = 6, S_BATCHBAD2 = 7,
+       S_OVCNT = 8 /* .. 10: three rotating counters of the overflow list, generation g uses g % 3 */, S_N = 11 };
+static inline uint64_t *scalar(phi_ctx *c, int i) { return c->d_scalars.as<uint64_t>() + i; }
+#define STRIPE_BYTES ((size_t)PHI_STRIPES * 8 * 8)
+static inline uint64_t pow2_at_least(uint64_t x) { uint64_t p = 1; while (p < x) p <<= 1; return p; }
+// n bytes from host memory into b (grown to hold them) on `st`, the context's stream if null; not waited for.  256 MB and more
+// from pageable memory go through the context's pinned staging buffers, given back by stage_release.
+int phi_upload_bytes(phi_ctx *c, DevBuf &b, const void *src, size_t bytes, hipStream_t st);
+template <class T> static inline int upload(phi_ctx *c, DevBuf &b, const T *src, size_t n, hipStream_t st = nullptr)
+{
+    return phi_upload_bytes(c, b, src, n * sizeof(T), st);
+}
+void stage_release(phi_ctx *c);                        // the pinned staging buffers given back
+// count pass -> scan -> ordered write of the minimiser records of one packed flat sequence (phi_abi.hip)
+int sketch_records(phi_ctx *c, const uint64_t *words, const unsigned long long *starts, int64_t n_bases, int32_t k, int32_t w,
+                   const uint8_t *ascii_if_bad, DevBuf &out_hash, DevBuf &out_pos, int64_t *n_out);
+// set_graph.hip: the body of phi_set_graph, and of phi_set_graph_chopped once the graph is chopped; what both check first
+int set_graph_check_args(phi_ctx *c, int32_t n_vtx, const char *seq_concat, const int64_t *seq_off, const int64_t *adj_off,
+                         const int32_t *adj, int32_t n_walks, const int64_t *walk_off, const int32_t *walk_vtx, const int32_t *topo_rank);
+int set_graph_check_offsets(phi_ctx *c, int32_t n_vtx, const int64_t *seq_off, const int64_t *adj_off, int32_t n_walks, const int64_t *walk_off);
+int set_graph_impl(phi_ctx *c, int32_t n_vtx, const char *seq_concat, const int64_t *seq_off, const int64_t *adj_off,
+                   const int32_t *adj, int32_t n_walks, const int64_t *walk_off, const int32_t *walk_vtx, const int32_t *topo_rank);
+// chop.hip: count / 64-bit scan / tiled expand of walk entries on the device (phi_set_graph_chopped, phi_vcf_walks)
+int chop_expand_entries(phi_ctx *c, const int32_t *d_in, int64_t n_in, const int32_t *first, int32_t n_vtx, const int64_t *walk_off,
+                        int32_t n_walks, int32_t max_len, DevBuf &d_out, std::vector<int64_t> &walk_off2, std::vector<int32_t> &ends,
+                        int64_t *n_out_p, double *gpu_ms);
 // PHI_DEVICE_POISON=<0..255> (tests; read once at load, -1 = unset): every device buffer is filled with that byte over its whole
 // capacity when it gets a new owner, and the fill is complete on the device before the buffer is handed on.  Called wherever
 // device memory changes hands: phi_dev_ensure, the text park's pieces, the inflater's buffers.  Not meant for groups of

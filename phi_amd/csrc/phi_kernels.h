@@ -1,7 +1,9 @@
-// phi_kernels.h -- launch interface between the C-ABI layer (phi_abi.hip) and the kernels.
+// phi_kernels.h -- launch interface between the C-ABI layer (phi_abi.hip, set_graph.hip, phi_solve.hip and the host glue kept
+// beside the kernels of chop.hip, vcf.hip, ladder.hip) and the kernels.
 #pragma once
 #include <stdint.h>
 #include <hip/hip_runtime.h>
+#include "phi_dp_flags.h"        // PHI_DP_NEED_ENTRY, _NEED_TOPS, _LANE_ONLY, _PAIR: shared with the host code of dp_steps.h
 
 #ifndef PHI_TPB
 #define PHI_TPB 256            // lanes per workgroup of the sketch kernel (4 waves)
@@ -249,8 +251,6 @@ void phi_launch_entry_csr(hipStream_t st, const phi_ent_t *a_e1, int64_t n_a, in
 // dp.hip
 #define PHI_DP_CHUNK 128        // steps staged through LDS at a time
 #define PHI_DP_RING 2048        // steps whose leaving states are kept in LDS
-#define PHI_DP_NEED_ENTRY 1     // step flag: a recombination can enter this vertex
-#define PHI_DP_NEED_TOPS 2      // step flag: a recombination can leave this vertex
 #define PHI_DP_MAX_WALKS 1022       // one walk per lane of sixteen waves; a walk id + 1 has 10 bits in the packed tops
 
 struct PhiDpArgs {
@@ -275,9 +275,6 @@ void phi_launch_dp(hipStream_t st, const PhiDpArgs &A);
 // event-driven DP (dp_events.hip): up to PHI_DP_EVENT_MAX_WALKS walks
 #define PHI_DP_EVENT_MAX_WALKS 256
 #define PHI_DP_EVENT_SAFE_WALKS 128  // beyond: per-lane queues of 16 runs; a deeper one makes the caller fall back to dp.hip
-#define PHI_DP_LANE_ONLY 4      // compact-step flag: a walk starts or ends on the vertex (no ENTRY / TOPS work)
-#define PHI_DP_PAIR 8           // compact-step flag: this step and the next have no TOPS and no walk in common
-                                // (two alleles of one site): the consumer may take them in one iteration
 struct PhiDpEventArgs {
     int32_t n_k, n_walks;                // compact steps (vertices with ENTRY / TOPS / a walk start or end)
     int64_t n_ev;                        // events = walk entries on those vertices

@@ -26,10 +26,6 @@
 #define HIPCHK(call) do { int rc_ = phi_hip_check(c, (call), #call); if (rc_) return rc_; } while (0)
 #define PHICHK(call) do { int rc_ = (call); if (rc_) return rc_; } while (0)
 
-enum { S_ERR = 0, S_NBAD = 1, S_BATCHBAD = 2, S_NEMIT = 3, S_FILTERED = 4, S_INMODEL = 5, S_EXPORT = 6, S_BATCHBAD2 = 7,
-       S_OVCNT = 8 /* .. 10: three rotating overflow counters (phi_ctx.h) */, S_N = 11 };
-static uint64_t *scalar(phi_ctx *c, int i) { return c->d_scalars.as<uint64_t>() + i; }
-
 // The walk entries as the solve's host code reads them: from the context's host copy, or -- a chromosome-scale graph keeps none
 // (phi_set_graph) -- from the device copy: single entries for the backtrack, whole stretches for the decoded path.
 static bool have_host_walks(const phi_ctx *c) { return (int64_t)c->h_walk_vtx.size() == c->n_entries; }
@@ -50,7 +46,6 @@ static int ensure_host_walks(phi_ctx *c)
     if (!c->h_walk_vtx.resize((size_t)c->n_entries)) return phi_fail(c, PHI_ERR_NOMEM, "host allocation failed");
     return phi_hip_check(c, phi_copy_sync(c, c->h_walk_vtx.data(), c->d_walk_vtx.p, (size_t)c->n_entries * 4, hipMemcpyDeviceToHost), "walk entries D2H");
 }
-static uint64_t pow2_at_least(uint64_t x) { uint64_t p = 1; while (p < x) p <<= 1; return p; }
 
 struct Seg { int32_t h; int64_t es, ee; };     // path segment: walk h, entries es..ee (inclusive)
 

@@ -17,8 +17,12 @@
 //
 // WALKS.  Every kept haplotype's walk over UNITS (backbone, its allele, backbone, ...: 2 * sites + 1 entries) from the choice
 // matrix; chop.hip's count / scan / expand then turns units into segment ids with unit_first in the place of first.
+#include <string.h>
 #include <algorithm>
-#include "phi_kernels.h"
+#include "phi_ctx.h"
+
+#define HIPCHK(call) do { int rc_ = phi_hip_check(c, (call), #call); if (rc_) return rc_; } while (0)
+#define PHICHK(call) do { int rc_ = (call); if (rc_) return rc_; } while (0)
 
 #define VCF_TPB 256
 #define VCF_TILE (VCF_TPB * 16)
@@ -234,3 +238,137 @@ void phi_launch_vcf_unit_walks(hipStream_t st, const int32_t *site_backbone, con
     const unsigned nb = (unsigned)std::min<int64_t>((n + 255) / 256, 256 * 64);
     hipLaunchKernelGGL(vcf_unit_walks_kernel, dim3(nb), dim3(256), 0, st, site_backbone, site_allele0, choice, n_sites, n_haps, last_unit, out);
 }
+
+// ---- host side (C ABI of include/phi_amd.h)
+
+extern "C" {
+
+// vcf2gfa.py:27-64, the sample columns: the text of the kept records' slices to the device, the genotype kernel (vcf.hip) over it,
+// matrix, ploidy and the per-record flags back.
+int phi_vcf_genotypes(phi_ctx *c, const char *text, int64_t n_text, const int64_t *text_off, const int32_t *gt_index, int64_t n_records,
+                      int32_t n_samples, uint16_t *gt, int32_t *ploidy, uint8_t *flagged)
+{
+    if (!c) return PHI_ERR_INVALID;
+    if (n_text < 0 || n_records < 0 || n_samples < 0 || !text_off || (n_records > 0 && (!text || !gt_index || !flagged)) ||
+        (n_samples > 0 && !ploidy) || (n_records > 0 && n_samples > 0 && !gt))
+        return phi_fail(c, PHI_ERR_INVALID, "phi_vcf_genotypes: null pointer or negative size");
+    // the layout the kernel relies on: slices back to back, one line feed behind each and nowhere else
+    if (text_off[0] != 0 || text_off[n_records] != n_text) return phi_fail(c, PHI_ERR_INVALID, "phi_vcf_genotypes: the offsets do not cover the text");
+    for (int64_t r = 0; r < n_records; r++)
+        if (text_off[r + 1] <= text_off[r] || text[text_off[r + 1] - 1] != '\n')
+            return phi_fail(c, PHI_ERR_INVALID, "phi_vcf_genotypes: the slice of record %lld is not followed by a line feed", (long long)r);
+    // (the text, the matrix and the flags have to fit device memory side by side: phi_dev_ensure says so where they do not;
+    //  this only keeps the record index in 32 bits and the grid within what a launch takes)
+    if (n_records >= ((int64_t)1 << 31) || phi_vcf_num_tiles(n_text) >= ((int64_t)1 << 31))
+        return phi_fail(c, PHI_ERR_UNSUPPORTED, "phi_vcf_genotypes: 2^31 kept records and more");
+    HIPCHK(hipSetDevice(c->device));
+    PhiStageTimer tm("vcf genotypes");
+    c->vcf.have = false;
+    phi_vcf_info info{};
+    info.text_bytes = n_text; info.n_records = n_records; info.n_samples = n_samples;
+    for (int32_t s = 0; s < n_samples; s++) ploidy[s] = 0;
+    if (n_records > 0) memset(flagged, 0, (size_t)n_records);
+    if (n_records == 0 || n_samples == 0) { c->vcf.info = info; c->vcf.have = true; return PHI_OK; }
+    const size_t n_cells = (size_t)n_records * (size_t)n_samples;
+    const int64_t n_tiles = phi_vcf_num_tiles(n_text);
+    DevBuf d_text, d_seg, d_gi, d_gt, d_ploidy, d_flag, d_err;
+    PhiDevGuard guard{{&d_text, &d_seg, &d_gi, &d_gt, &d_ploidy, &d_flag, &d_err}};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int i = 0; i < 2; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } evg{ev};
+    for (int i = 0; i < 2; i++) HIPCHK(hipEventCreate(&ev[i]));
+    PHICHK(upload(c, d_text, text, (size_t)n_text));
+    PHICHK(upload(c, d_gi, gt_index, (size_t)n_records));
+    PHICHK(phi_dev_ensure(c, d_seg, ((size_t)n_tiles + 1) * 8));
+    PHICHK(phi_dev_ensure(c, d_gt, n_cells * 4));
+    PHICHK(phi_dev_ensure(c, d_ploidy, (size_t)n_samples * 4));
+    PHICHK(phi_dev_ensure(c, d_flag, (size_t)n_records));
+    PHICHK(phi_dev_ensure(c, d_err, 4));
+    HIPCHK(hipMemsetAsync(d_gt.p, 0, n_cells * 4, c->stream));
+    HIPCHK(hipMemsetAsync(d_ploidy.p, 0, (size_t)n_samples * 4, c->stream));
+    HIPCHK(hipMemsetAsync(d_flag.p, 0, (size_t)n_records, c->stream));
+    HIPCHK(hipMemsetAsync(d_err.p, 0, 4, c->stream));
+    tm.lap("text to the device");
+    HIPCHK(hipEventRecord(ev[0], c->stream));
+    phi_launch_vcf_genotypes(c->stream, d_text.as<uint8_t>(), n_text, d_seg.p, d_gi.as<int32_t>(), n_records, n_samples, d_gt.as<uint16_t>(),
+                             d_ploidy.as<int32_t>(), d_flag.as<uint8_t>(), d_err.as<uint32_t>());
+    HIPCHK(hipEventRecord(ev[1], c->stream));
+    uint32_t kerr = 0;
+    HIPCHK(hipMemcpyAsync(gt, d_gt.p, n_cells * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(ploidy, d_ploidy.p, (size_t)n_samples * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(flagged, d_flag.p, (size_t)n_records, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&kerr, d_err.p, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipGetLastError());
+    if (kerr) return phi_fail(c, PHI_ERR_INVALID, "phi_vcf_genotypes: a line feed inside a slice (the text is not laid out as phi_vcf_read lays it out)");
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    info.genotype_gpu_ms = ms;
+    for (int64_t r = 0; r < n_records; r++) info.n_flagged += flagged[r] != 0;
+    tm.lap("genotype kernel, matrix back");
+    c->vcf.info = info; c->vcf.have = true;
+    return PHI_OK;
+}
+
+// vcf2gfa.py:27-64, the W-lines that are never written: every kept haplotype's walk over units from the choice matrix
+// (vcf.hip), then chop.hip's count / scan / expand with unit_first in the place of first; the entries and their offsets
+// are left where phi_walk_text_resolve leaves them.
+int phi_vcf_walks(phi_ctx *c, const int32_t *unit_first, int64_t n_units, const int32_t *site_backbone, const int32_t *site_allele0,
+                  int64_t n_sites, const int32_t *choice, int32_t n_haps, int64_t *walk_off_out)
+{
+    if (!c) return PHI_ERR_INVALID;
+    if (!unit_first || !walk_off_out || n_units < 1 || n_sites < 0 || n_haps < 1 || (n_sites > 0 && (!site_backbone || !site_allele0 || !choice)))
+        return phi_fail(c, PHI_ERR_INVALID, "phi_vcf_walks: null pointer or empty table");
+    if (n_units > INT32_MAX - 1 || n_units < 2 * n_sites + 1) return phi_fail(c, PHI_ERR_INVALID, "phi_vcf_walks: %lld units for %lld sites", (long long)n_units, (long long)n_sites);
+    if (n_haps > PHI_DP_MAX_WALKS) return phi_fail(c, PHI_ERR_UNSUPPORTED, "more than %d walks", PHI_DP_MAX_WALKS);
+    if (unit_first[0] != 0) return phi_fail(c, PHI_ERR_INVALID, "phi_vcf_walks: unit_first must start at 0");
+    for (int64_t u = 0; u < n_units; u++)
+        if (unit_first[u + 1] <= unit_first[u]) return phi_fail(c, PHI_ERR_INVALID, "phi_vcf_walks: unit %lld holds no segment", (long long)u);
+    const int64_t per = 2 * n_sites + 1, n_in = per * n_haps;
+    if (n_in > PHI_MAX_ENTRIES) return phi_fail(c, PHI_ERR_UNSUPPORTED, "more than 2^32 - 64 walk entries");
+    HIPCHK(hipSetDevice(c->device));
+    PhiStageTimer tm("vcf walks");
+    DevBuf d_sb, d_sa, d_choice, d_units, d_out;
+    PhiDevGuard guard{{&d_sb, &d_sa, &d_choice, &d_units, &d_out}};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int i = 0; i < 2; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } evg{ev};
+    for (int i = 0; i < 2; i++) HIPCHK(hipEventCreate(&ev[i]));
+    PHICHK(upload(c, d_sb, site_backbone, (size_t)n_sites));
+    PHICHK(upload(c, d_sa, site_allele0, (size_t)n_sites));
+    PHICHK(upload(c, d_choice, choice, (size_t)n_sites * (size_t)n_haps));
+    PHICHK(phi_dev_ensure(c, d_units, (size_t)n_in * 4));
+    HIPCHK(hipEventRecord(ev[0], c->stream));
+    phi_launch_vcf_unit_walks(c->stream, d_sb.as<int32_t>(), d_sa.as<int32_t>(), d_choice.as<int32_t>(), n_sites, n_haps, (int32_t)n_units - 1,
+                              d_units.as<int32_t>());
+    HIPCHK(hipEventRecord(ev[1], c->stream));
+    std::vector<int64_t> woff_in((size_t)n_haps + 1), walk_off2;
+    for (int32_t h = 0; h <= n_haps; h++) woff_in[(size_t)h] = per * h;
+    std::vector<int32_t> ends;
+    int64_t n_out = 0;
+    double expand_ms = 0.0;
+    // (a choice beyond its site's alleles names a unit of the next site or none at all: the count reports the latter as a vertex out of range)
+    PHICHK(chop_expand_entries(c, d_units.as<int32_t>(), n_in, unit_first, (int32_t)n_units, woff_in.data(), n_haps, 0, d_out, walk_off2, ends, &n_out, &expand_ms));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    // (only now: after a refusal above, walks an earlier phi_walk_text_resolve / phi_vcf_walks left on the device are as they were)
+    std::swap(c->d_walk_vtx, d_out);                           // (the guard lets the entries the context held go)
+    c->wtext.ends.swap(ends);
+    c->walks_on_device = true;
+    c->walks_on_device_n = n_out;
+    memcpy(walk_off_out, walk_off2.data(), walk_off2.size() * 8);
+    c->vcf.info.n_units = n_units;
+    c->vcf.info.n_entries = n_out;
+    c->vcf.info.walks_gpu_ms = (double)ms + expand_ms;
+    c->vcf.have = true;
+    tm.lap("unit walks, count, scan, expand");
+    return PHI_OK;
+}
+
+int phi_vcf_stats(phi_ctx *c, phi_vcf_info *out)
+{
+    if (!c || !out) return PHI_ERR_INVALID;
+    if (!c->vcf.have) return phi_fail(c, PHI_ERR_STATE, "phi_vcf_stats: no phi_vcf_genotypes / phi_vcf_walks on this context");
+    *out = c->vcf.info;
+    return PHI_OK;
+}
+
+}  // extern "C"
