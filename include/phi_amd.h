@@ -125,6 +125,68 @@ typedef struct {
 int phi_chop_stats(phi_ctx *ctx, phi_chop_info *out);
 
 /*
+ * "Set graph" against a PANEL: a chosen subset of the graph's haplotypes.  The reference builds one graph from the full VCF
+ * (data/chop_graph.sh:46-50), removes samples from the haplotype index (data/chop_graph.sh:51-61 `vg gbwt ... -R SAMPLE`, the
+ * sample lists drawn nested by data/get_ids.py and data/get_ids_2.py), writes one GFA per panel (data/chop_graph.sh:62-66) and
+ * runs PHI once per panel (data/run_batch_9.py to run_batch_13.py); leave-one-out evaluation is the same operation.
+ *
+ * THE RULE.  Given a graph and a flag per walk (keep[h] != 0), the panel graph is the subgraph induced by the kept walks:
+ *   vertices   those on at least one kept walk, in their old order; the new id is the number of kept vertices before it;
+ *   edges      the edges (u, v) that at least one kept walk steps along, in their old order within u's list; an edge whose
+ *              two ends are kept but which no kept walk uses is dropped (what a graph induced by a haplotype index holds);
+ *   walks      the kept walks in their old order, renumbered from 0, their entries renamed;
+ *   ranks      the topological ranks the host reader gives the panel graph -- Kahn's algorithm with a FIFO queue, sources in
+ *              id order (ILP_index.cpp:115-154) --, NOT the old ranks compressed: the two can differ, and ranks break ties.
+ * The rule is applied uniformly: with every walk kept, vertices and edges on no walk still go.  With these ranks the result
+ * is what phi_set_graph gives for the GFA minus the W-lines of the dropped walks and the S- and L-lines nothing uses any
+ * more.  Believed to be what `gfa2gbwt -d` writes after `vg gbwt -R`; not compared with `vg`.
+ *
+ *   phi_set_graph_panel  (data/chop_graph.sh:46-66) the arrays of phi_set_graph without topo_rank (the panel's ranks are made
+ *                        here).  walk_vtx: host entries, or NULL for entries on the device -- freshly resolved there
+ *                        (phi_walk_text_resolve, phi_vcf_walks) or retained by an earlier call.  The kept entries are marked
+ *                        and renamed on the device (panel.hip), the per-vertex arrays reduced on the host.  max_len > 0 then
+ *                        chops the PANEL graph (phi_set_graph_chopped: phi_chop_origin names (panel vertex, offset));
+ *                        max_len <= 0: no chop.  walk_off_out[kept walks + 1] (may be NULL): the panel's (chopped) walk
+ *                        offsets.  flags: PHI_PANEL_RETAIN keeps the FULL entries on the device after the call, so that a
+ *                        later call with walk_vtx = NULL and the same walk_off starts from them (a ladder of panels from
+ *                        one upload or one device-side resolve); they stay until phi_panel_release, a retaining call that
+ *                        replaces them, or a call without the flag that starts from them.  walk_vtx = NULL with neither:
+ *                        PHI_ERR_STATE.  No walk kept: PHI_ERR_INVALID; more than 1022 KEPT walks: PHI_ERR_UNSUPPORTED (the
+ *                        input's walk count is not limited); both decided before anything is allocated, the context and
+ *                        walks resolved on the device as they were.  A kept walk holding a vertex out of range:
+ *                        PHI_ERR_WALK, naming the walk and the vertex as passed in (a dropped walk's entries are not looked
+ *                        at).  A cycle: PHI_ERR_INVALID in the host reader's words.  Whatever phi_set_graph refuses of the
+ *                        panel graph is refused the same way, ids in such a message being the panel graph's; on failure the
+ *                        context holds no graph.  Everything downstream (phi_solve's path_vtx and path_hap,
+ *                        phi_kept_anchors, phi_walk_minimizers, ...) speaks of panel vertices and panel walks.
+ *   phi_panel_origin     (data/chop_graph.sh:51-66 undone for reporting) panel vertex vtx[i] -> the vertex as passed in.
+ *   phi_panel_walks      (data/chop_graph.sh:51-61 undone for reporting) orig_walk[0, *n_kept): panel walk -> the walk as passed
+ *                        in; nothing is copied when cap is too small.
+ *   phi_panel_stats      (data/chop_graph.sh:46-66) walks, vertices, edges and walk entries before and after; the GPU
+ *                        milliseconds of mark, scan and remap by HIP events on the context's stream; the host seconds of the
+ *                        array reduction and of Kahn.
+ *   phi_panel_release    (data/run_batch_9.py to run_batch_13.py: the ladder is over) lets retained entries go.
+ * The three accessors give PHI_ERR_STATE when the context's graph was not set as a panel.
+ */
+#define PHI_PANEL_RETAIN 1u
+typedef struct {
+    int32_t n_walks_in, n_walks_out;
+    int64_t n_vtx_in, n_vtx_out;
+    int64_t n_edges_in, n_edges_out;
+    int64_t n_entries_in, n_entries_out;
+    double mark_gpu_ms, scan_gpu_ms, remap_gpu_ms;
+    double reduce_host_s, kahn_host_s;
+} phi_panel_info;
+int phi_set_graph_panel(phi_ctx *ctx, int32_t n_vtx, const char *seq_concat, const int64_t *seq_off,
+                        const int64_t *adj_off, const int32_t *adj, int32_t n_walks,
+                        const int64_t *walk_off, const int32_t *walk_vtx, const uint8_t *keep,
+                        int32_t max_len, uint32_t flags, int64_t *walk_off_out);
+int phi_panel_origin(phi_ctx *ctx, const int32_t *vtx, int64_t n, int32_t *orig_vtx);
+int phi_panel_walks(phi_ctx *ctx, int32_t *orig_walk, int32_t cap, int32_t *n_kept);
+int phi_panel_stats(phi_ctx *ctx, phi_panel_info *out);
+int phi_panel_release(phi_ctx *ctx);
+
+/*
  * "Set graph" from a phased multi-sample VCF + reference FASTA (the reference's second input route, vcf2gfa.py:27-64: `vg construct
  * | vg gbwt | gfa2gbwt -m 30`, here the rule of phi_amd/vcf2gfa.py) without a GFA in between.  The host reads the small parts
  * and builds the per-vertex arrays (include/phi_host.h phi_vcf_read, phi_vcf_build); the device parses the genotype text, the

@@ -35,7 +35,9 @@ SYMBOLS = [
     "phi_set_graph_chopped", "phi_chop_origin", "phi_chop_stats",
     "phi_vcf_genotypes", "phi_vcf_walks", "phi_vcf_stats",
     "phi_reads_collect_begin", "phi_reads_collect_end", "phi_reads_collect_release", "phi_ladder_plan", "phi_ladder_advance", "phi_ladder_band",
+    "phi_set_graph_panel", "phi_panel_origin", "phi_panel_walks", "phi_panel_stats", "phi_panel_release",
 ]
+PHI_PANEL_RETAIN = 1
 PHI_LADDER_MAX_LEVELS = 16
 PHI_INFLATE_NO_FINDER = 1
 PHI_INFLATE_CHUNK_DEFAULT = 64 << 10          # include/phi_amd.h
@@ -54,6 +56,13 @@ class PhiSolveInfo(C.Structure):
 class PhiChopInfo(C.Structure):
     _fields_ = [("n_vtx_in", C.c_int64), ("n_vtx_out", C.c_int64), ("n_entries_in", C.c_int64), ("n_entries_out", C.c_int64),
                 ("max_len", C.c_int32), ("expand_gpu_ms", C.c_double)]
+
+
+class PhiPanelInfo(C.Structure):
+    _fields_ = [("n_walks_in", C.c_int32), ("n_walks_out", C.c_int32), ("n_vtx_in", C.c_int64), ("n_vtx_out", C.c_int64),
+                ("n_edges_in", C.c_int64), ("n_edges_out", C.c_int64), ("n_entries_in", C.c_int64), ("n_entries_out", C.c_int64),
+                ("mark_gpu_ms", C.c_double), ("scan_gpu_ms", C.c_double), ("remap_gpu_ms", C.c_double),
+                ("reduce_host_s", C.c_double), ("kahn_host_s", C.c_double)]
 
 
 class PhiVcfInfo(C.Structure):
@@ -116,6 +125,11 @@ def load():
     L.phi_set_graph_chopped.argtypes = [vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, vp]
     L.phi_chop_origin.argtypes = [vp, vp, i64, vp, vp]
     L.phi_chop_stats.argtypes = [vp, C.POINTER(PhiChopInfo)]
+    L.phi_set_graph_panel.argtypes = [vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, C.c_uint32, vp]
+    L.phi_panel_origin.argtypes = [vp, vp, i64, vp]
+    L.phi_panel_walks.argtypes = [vp, vp, i32, C.POINTER(i32)]
+    L.phi_panel_stats.argtypes = [vp, C.POINTER(PhiPanelInfo)]
+    L.phi_panel_release.argtypes = [vp]
     L.phi_vcf_genotypes.argtypes = [vp, vp, i64, vp, vp, i64, i32, vp, vp, vp]
     L.phi_vcf_walks.argtypes = [vp, vp, i64, vp, vp, i64, vp, i32, vp]
     L.phi_vcf_stats.argtypes = [vp, C.POINTER(PhiVcfInfo)]

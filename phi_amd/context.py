@@ -65,18 +65,36 @@ class Context:
         self._chk(self._L.phi_set_params(self._h, k, w, C.c_float(threshold), recombination, flags))
         self.k, self.w = k, w
 
-    def set_graph(self, seq_concat, seq_off, adj_off, adj, walk_off, walk_vtx, top_rank, chop=None):
+    def set_graph(self, seq_concat, seq_off, adj_off, adj, walk_off, walk_vtx, top_rank, chop=None, keep=None, retain=False):
         """Arrays of phi_set_graph: bytes + int64/int32 numpy arrays.  chop=N: every vertex is first cut into pieces of at
         most N bases (phi_set_graph_chopped: what `hal2vg --chop N` does in the reference's pipeline); returns the chopped
-        walks' offsets, and path_vtx, kept_anchors ... then speak of the chopped graph (chop_origin maps back)."""
+        walks' offsets, and path_vtx, kept_anchors ... then speak of the chopped graph (chop_origin maps back).
+        keep=mask (one flag per walk): the graph is first reduced to the subgraph induced by the kept walks
+        (phi_set_graph_panel, the rule of phi_amd.panel; top_rank is not used: the panel's ranks are made by the library),
+        then chopped when chop is given; returns the panel's (chopped) walk offsets, and path_vtx, path_hap ... speak of the
+        panel (panel_origin, panel_walks map back).  retain=True keeps the full walk entries on the device: a later call
+        with walk_vtx=None and the same walk_off starts from them (panel_release lets them go)."""
         seq_off = np.ascontiguousarray(seq_off, np.int64)
         adj_off = np.ascontiguousarray(adj_off, np.int64)
         adj = np.ascontiguousarray(adj, np.int32)
         walk_off = np.ascontiguousarray(walk_off, np.int64)
         walk_vtx = np.ascontiguousarray(walk_vtx, np.int32) if walk_vtx is not None else None     # (None: resolved on the device, phi_walk_text_resolve)
-        top_rank = np.ascontiguousarray(top_rank, np.int32)
+        top_rank = np.ascontiguousarray(top_rank, np.int32) if top_rank is not None else None     # (not used with keep=mask)
         buf = np.frombuffer(seq_concat, np.uint8) if not isinstance(seq_concat, np.ndarray) else seq_concat
         self.n_vtx, self.n_walks = len(seq_off) - 1, len(walk_off) - 1
+        if keep is not None:
+            keep = np.ascontiguousarray(np.asarray(keep) != 0, np.uint8)
+            if keep.shape != (self.n_walks,):
+                raise ValueError(f"keep must hold one flag per walk ({self.n_walks}), not {keep.shape}")
+            walk_off_out = np.zeros(int(keep.sum()) + 1, np.int64)
+            self._chk(self._L.phi_set_graph_panel(self._h, self.n_vtx, _ptr(buf), _ptr(seq_off), _ptr(adj_off), _ptr(adj),
+                                                  self.n_walks, _ptr(walk_off), _ptr(walk_vtx), keep.ctypes.data,
+                                                  int(chop) if chop is not None else 0,
+                                                  _capi.PHI_PANEL_RETAIN if retain else 0, walk_off_out.ctypes.data))
+            self.n_walks = len(walk_off_out) - 1
+            return walk_off_out
+        if retain:
+            raise ValueError("retain=True goes with keep=mask")
         if chop is not None:
             walk_off_out = np.zeros(self.n_walks + 1, np.int64)
             self._chk(self._L.phi_set_graph_chopped(self._h, self.n_vtx, _ptr(buf), _ptr(seq_off), _ptr(adj_off), _ptr(adj),
@@ -87,19 +105,27 @@ class Context:
                                         self.n_walks, _ptr(walk_off), _ptr(walk_vtx), _ptr(top_rank)))
         return None
 
-    def set_graph_vcf(self, vcf_path, fasta_path, max_len=30):
+    def set_graph_vcf(self, vcf_path, fasta_path, max_len=30, keep_samples=None):
         """ "Set graph" from a phased VCF + reference FASTA (the graph of phi_amd.vcf2gfa, no GFA in between): vcf_graph(), then
         phi_set_graph takes the walk entries from where the device left them.  Returns the host graph description (VcfGraph:
         hap_id2name, the arrays, walk_off, n_other_contig / n_ref_mismatch / warnings()) with .stats = vcf_stats() plus host
-        seconds per stage.  What phi_set_graph refuses of any graph it refuses here (the context stays usable)."""
+        seconds per stage.  What phi_set_graph refuses of any graph it refuses here (the context stays usable).
+        keep_samples=[names]: a panel, with the reference's semantics (data/chop_graph.sh:46-66) -- the graph is built from
+        ALL samples' records, only the kept samples' haplotypes are written as walks (the reference is the sample "REF"), and
+        the panel step then removes what no kept walk uses.  v.hap_id2name, v.num_walks and v.walk_off then speak of the kept
+        walks, v.kept_haps names them among all haplotypes; path_vtx speaks of the panel graph (panel_origin maps back to
+        v's vertices).  The limit of 1022 haplotypes applies to the kept ones."""
         import time
-        v = self.vcf_graph(vcf_path, fasta_path, max_len)
+        v = self.vcf_graph(vcf_path, fasta_path, max_len, keep_samples=keep_samples)
         t4 = time.perf_counter()
-        self.set_graph(v.seq_concat, v.seq_off, v.adj_off, v.adj, v.walk_off, None, v.top_order_map)
+        if keep_samples is None:
+            self.set_graph(v.seq_concat, v.seq_off, v.adj_off, v.adj, v.walk_off, None, v.top_order_map)
+        else:
+            v.walk_off = self.set_graph(v.seq_concat, v.seq_off, v.adj_off, v.adj, v.walk_off, None, None, keep=np.ones(v.num_walks, np.uint8))
         v.stats["set_graph_s"] = time.perf_counter() - t4
         return v
 
-    def vcf_graph(self, vcf_path, fasta_path, max_len=30):
+    def vcf_graph(self, vcf_path, fasta_path, max_len=30, keep_samples=None):
         """The VCF route up to "set graph": the host reads the fixed columns and builds the per-vertex arrays
         (ilp_index.VcfGraph), the device parses the genotype text (phi_vcf_genotypes; records it flags go through the host's
         scalar parser) and writes the walk entries (phi_vcf_walks): walk_entries() returns them, set_graph(..., walk_vtx=None)
@@ -120,6 +146,14 @@ class Context:
         t2 = time.perf_counter()
         v.build(gt, ploidy, max_len)
         t3 = time.perf_counter()
+        if keep_samples is not None:                              # the choice columns of the kept haplotypes only
+            from .panel import keep_mask
+            v.kept_haps = np.flatnonzero(keep_mask(v.hap_id2name, keep_samples=keep_samples)).astype(np.int32)
+            if len(v.kept_haps) == 0:
+                raise ValueError("keep_samples keeps no haplotype")
+            v.choice = np.ascontiguousarray(v.choice[:, v.kept_haps])
+            v.hap_id2name = [v.hap_id2name[h] for h in v.kept_haps.tolist()]
+            v.num_walks = len(v.kept_haps)
         walk_off = np.zeros(v.num_walks + 1, np.int64)
         choice = np.ascontiguousarray(v.choice, np.int32)
         self._chk(self._L.phi_vcf_walks(self._h, _ptr(v.unit_first), v.n_units, _ptr(v.site_backbone), _ptr(v.site_allele0), v.n_real_sites,
@@ -142,6 +176,32 @@ class Context:
         ov, oo = np.zeros(len(vtx), np.int32), np.zeros(len(vtx), np.int32)
         self._chk(self._L.phi_chop_origin(self._h, _ptr(vtx), len(vtx), _ptr(ov), _ptr(oo)))
         return ov, oo
+
+    def panel_origin(self, vtx):
+        """Panel vertex ids -> the vertices as passed to set_graph(keep=mask) (after chop_origin when the panel was chopped)."""
+        vtx = np.ascontiguousarray(vtx, np.int32)
+        ov = np.zeros(len(vtx), np.int32)
+        self._chk(self._L.phi_panel_origin(self._h, _ptr(vtx), len(vtx), _ptr(ov)))
+        return ov
+
+    def panel_walks(self):
+        """Panel walk ids (path_hap, kept_anchors' walks) -> the walks as passed to set_graph(keep=mask)."""
+        n = C.c_int32()
+        self._chk(self._L.phi_panel_walks(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, np.int32)
+        self._chk(self._L.phi_panel_walks(self._h, _ptr(out), n.value, C.byref(n)))
+        return out
+
+    def panel_stats(self):
+        """What set_graph(keep=mask) did: walks, vertices, edges and walk entries before and after, GPU milliseconds of mark,
+        scan and remap, host seconds of the array reduction and of Kahn."""
+        r = _capi.PhiPanelInfo()
+        self._chk(self._L.phi_panel_stats(self._h, C.byref(r)))
+        return {n: getattr(r, n) for n, _ in _capi.PhiPanelInfo._fields_}
+
+    def panel_release(self):
+        """Lets the full walk entries a set_graph(keep=mask, retain=True) kept on the device go."""
+        self._chk(self._L.phi_panel_release(self._h))
 
     def chop_stats(self):
         """What set_graph(chop=N) did: vertices and walk entries before and after, N, GPU time of the expansion."""

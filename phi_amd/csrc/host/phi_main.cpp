@@ -5,6 +5,9 @@
 //   ./PHI -g <target.gfa> -r <reads.fa> -o <haplotype.fasta> [-k -w -R -q -m -T -t -d -N -c]
 //         [--device N | --devices 0,1,..] [--dp-budget RUNS]
 //         [--coverage C0,C1,.. --genome-size N [--seed S]]   (-o 'out.{cov}x.fa': one FASTA per coverage)
+//         [--keep-samples A,B,.. | --drop-samples A,B,.. | --panels N0,N1,.. [--panel-seed S] [--panel-always NAME,..]]
+//                                                             a panel of the graph's haplotypes, subset inside "set graph"
+//                                                             (data/chop_graph.sh:46-66); -o 'out.{panel}.fa': one FASTA per panel
 //   ./PHI -g <target.gfa> -r a.fq -o a.fa -r b.fq -o b.fa ...      several read sets against ONE graph: the graph is parsed and
 //         indexed once (the reference's harness runs PHI once per sample x coverage on the same graph,
 //         data/run_batch_4_miqp.py:31-46), every job prints the log of a run of its own and writes its own FASTA
@@ -147,10 +150,50 @@ struct Options {
     std::vector<double> cov;
     double genome_size = 0.0;
     unsigned long long seed = 0;
+    // a panel of the graph's haplotypes (data/chop_graph.sh:46-66; the sample lists of data/get_ids.py, data/get_ids_2.py):
+    // --keep-samples / --drop-samples A,B,.. or @FILE; --panels N0,N1,..: nested panels by sample (data/run_batch_9.py to run_batch_13.py)
+    std::vector<std::string> keep_samples, drop_samples, panel_always;
+    bool have_keep = false, have_drop = false;
+    std::vector<std::string> panel_names;                     // the sizes as written on the command line
+    std::vector<int> panel_sizes;
+    unsigned long long panel_seed = 0;
+    bool panel() const { return have_keep || have_drop || !panel_sizes.empty(); }
     int argc = 0;
     char **argv = nullptr;
     bool detached = false;
 };
+
+// A,B,.. or @FILE (one name per line): the names of --keep-samples, --drop-samples, --panel-always
+static bool read_names(const char *arg, std::vector<std::string> &out)
+{
+    out.clear();
+    if (arg[0] == '@') {
+        FILE *fp = fopen(arg + 1, "r");
+        if (!fp) return false;
+        char line[4096];
+        while (fgets(line, sizeof line, fp)) {
+            std::string t(line);
+            while (!t.empty() && (t.back() == '\n' || t.back() == '\r' || t.back() == ' ' || t.back() == '\t')) t.pop_back();
+            if (!t.empty()) out.push_back(t);
+        }
+        fclose(fp);
+        return true;
+    }
+    std::string t;
+    for (const char *p = arg;; p++) {
+        if (*p == ',' || !*p) { if (!t.empty()) out.push_back(t); t.clear(); if (!*p) break; }
+        else t.push_back(*p);
+    }
+    return true;
+}
+// output number ordinal + 1 of SplitMix64(seed): the key of phi_amd/panel.py nested_panels (phi_amd.ladder.splitmix64)
+static uint64_t splitmix64(uint64_t seed, uint64_t ordinal)
+{
+    uint64_t x = seed + (ordinal + 1) * 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
 
 // ---- the PHI_* knobs of a run, read once
 struct Knobs {
@@ -466,6 +509,15 @@ struct Driver {
     void *peer_group = nullptr;
     unsigned char comm_id[PHI_COMM_ID_BYTES];
     struct { int64_t bytes = 0; int rc = 0; bool sent = false; } wt;      // the walk text the deferred GFA reader sent to the device
+    // ---- a panel of the graph's haplotypes (--keep-samples, --drop-samples, --panels): keep[h] per walk of g, and what the
+    //      context's walks and vertices are in g's terms once the panel is set
+    std::vector<uint8_t> keep;
+    std::vector<int32_t> kept_walks;                          // panel walk -> walk of g
+    std::vector<std::vector<std::string>> panels;             // --panels: the samples of every panel
+    std::string hap_pattern;                                  // --panels: the job's -o with {panel} replaced
+    bool walks_retained = false;                              // --panels: the full entries are on the device (PHI_PANEL_RETAIN)
+    phi_panel_info panel_info{};
+    long long full_entries = 0;                               // walk entries handed to the panel step
     explicit Driver(const Options &opt) : o(opt), devices(opt.devices), reads_file(opt.reads_files[0]), hap_file(opt.hap_files[0]) {}
 
     // the one error exit: the message, the reader thread stopped, status 1
@@ -618,17 +670,120 @@ struct Driver {
         if (!walks_on_device && phi_graph_resolve_walks(g, err, sizeof err) != PHI_HOST_OK) return gfa_failed();
         return 0;
     }
+    // ---- the panel: samples are the W-lines' sample fields (the VCF's sample names, REF for the reference walk)
+    static std::string sample_of(const char *hap_name)
+    {
+        const char *dot = strrchr(hap_name, '.');
+        return dot ? std::string(hap_name, dot) : std::string(hap_name);
+    }
+    std::vector<std::string> samples_in_order() const
+    {
+        std::vector<std::string> out;
+        for (int32_t h = 0; h < phi_graph_n_walks(g); h++) {
+            const std::string sm = sample_of(phi_graph_hap_name(g, h));
+            if (std::find(out.begin(), out.end(), sm) == out.end()) out.push_back(sm);
+        }
+        return out;
+    }
+    int check_names(const char *option, const std::vector<std::string> &names, const std::vector<std::string> &have)
+    {
+        std::string missing;
+        for (const std::string &n : names)
+            if (std::find(have.begin(), have.end(), n) == have.end()) missing += (missing.empty() ? "" : ", ") + n;
+        return missing.empty() ? 0 : fail("[E::main] %s: the graph holds no sample named %s\n", option, missing.c_str());
+    }
+    // keep[] from a list of samples to keep, or to drop
+    void mask_of(const std::vector<std::string> &names, bool drop)
+    {
+        const int32_t n_walks = phi_graph_n_walks(g);
+        keep.assign((size_t)n_walks, 0);
+        for (int32_t h = 0; h < n_walks; h++) {
+            const bool in = std::find(names.begin(), names.end(), sample_of(phi_graph_hap_name(g, h))) != names.end();
+            keep[(size_t)h] = in != drop;
+        }
+    }
+    // the options checked against the graph's samples; --panels: the nested panels of phi_amd/panel.py nested_panels
+    int plan_panels()
+    {
+        if (!o.panel()) return 0;
+        const std::vector<std::string> have = samples_in_order();
+        if (o.have_keep) { if (check_names("--keep-samples", o.keep_samples, have)) return 1; mask_of(o.keep_samples, false); return 0; }
+        if (o.have_drop) { if (check_names("--drop-samples", o.drop_samples, have)) return 1; mask_of(o.drop_samples, true); return 0; }
+        if (check_names("--panel-always", o.panel_always, have)) return 1;
+        std::vector<std::string> rest;
+        for (const std::string &sm : have)
+            if (std::find(o.panel_always.begin(), o.panel_always.end(), sm) == o.panel_always.end()) rest.push_back(sm);
+        if (o.panel_sizes.back() > (int)rest.size())
+            return fail("[E::main] --panels: a panel of %d samples, but the graph holds %zu besides the always-kept ones\n", o.panel_sizes.back(), rest.size());
+        std::vector<size_t> order(rest.size());
+        for (size_t i = 0; i < order.size(); i++) order[i] = i;
+        std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return splitmix64(o.panel_seed, a) < splitmix64(o.panel_seed, b); });
+        for (int n : o.panel_sizes) {
+            std::vector<std::string> p(o.panel_always);
+            for (int i = 0; i < n; i++) p.push_back(rest[order[(size_t)i]]);
+            panels.push_back(p);
+        }
+        return 0;
+    }
+    const char *walk_name(int32_t h) const { return phi_graph_hap_name(g, o.panel() ? kept_walks[(size_t)h] : h); }
+    // "Panel: kept 13 of 49 walks (6 of 24 samples + REF): V -> V' vertices, E -> E' edges, X -> X' walk entries"
+    void log_panel()
+    {
+        std::vector<std::string> all, in;
+        bool ref_in = false;
+        for (int32_t h = 0; h < phi_graph_n_walks(g); h++) {
+            const std::string sm = sample_of(phi_graph_hap_name(g, h));
+            const bool is_ref = sm == "REF";
+            if (is_ref) { ref_in = ref_in || keep[(size_t)h]; continue; }
+            if (std::find(all.begin(), all.end(), sm) == all.end()) all.push_back(sm);
+            if (keep[(size_t)h] && std::find(in.begin(), in.end(), sm) == in.end()) in.push_back(sm);
+        }
+        const phi_panel_info &pi = panel_info;
+        stamp("main");
+        fprintf(stderr, "Panel: kept %d of %d walks (%zu of %zu samples%s): %lld -> %lld vertices, %lld -> %lld edges, %lld -> %lld walk entries\n",
+                (int)kept_walks.size(), phi_graph_n_walks(g), in.size(), all.size(), ref_in ? " + REF" : "", (long long)phi_graph_n_vtx(g), (long long)pi.n_vtx_out,
+                (long long)phi_graph_adj_off(g)[phi_graph_n_vtx(g)], (long long)pi.n_edges_out, (long long)full_entries, (long long)pi.n_entries_out);
+    }
     // ---- stage 1a: walks (ILP_index.cpp:556-611) on every GPU, while the reads are still being read
     int build_index()
     {
         const uint32_t flags = (o.is_qclp ? PHI_FLAG_QCLP : 0) | (o.is_mixed ? PHI_FLAG_MIXED : 0);
         Stage st("phi_set_graph (index build)");
+        if (o.panel()) {
+            kept_walks.clear();
+            for (int32_t h = 0; h < phi_graph_n_walks(g); h++) if (keep[(size_t)h]) kept_walks.push_back(h);
+            if (kept_walks.empty()) return fail("[E::main] the panel keeps no walk\n");
+        }
         const int rc = run_on_all("graph", [&](int, phi_ctx *cx) -> int {
-            int r = phi_set_params(cx, o.k, o.w, o.threshold, o.recombination, flags);
+            // (--panels: a context takes its parameters once, before its first graph)
+            int r = walks_retained ? 0 : phi_set_params(cx, o.k, o.w, o.threshold, o.recombination, flags);
             // the reference's model.optimize() has no limit (ILP_index.cpp:1412-1418): none here unless --dp-budget asks for one
             if (!r) r = phi_set_solve_budget(cx, o.dp_budget >= 0 ? o.dp_budget : 0);
             std::vector<int64_t> vcf_walk_off;
-            if (!r && vcf) {
+            if (!r && vcf && o.panel()) {
+                // the graph is built from ALL samples' records; only the kept haplotypes' choice columns become walks, and the
+                // panel step, with every walk kept, removes what nobody uses
+                const int64_t n_sites = phi_vcf_n_real_sites(vcf);
+                const int32_t n_haps = phi_vcf_n_kept_haps(vcf), n_kept = (int32_t)kept_walks.size();
+                std::vector<int32_t> choice((size_t)std::max<int64_t>(1, n_sites * n_kept));
+                for (int64_t si = 0; si < n_sites; si++)
+                    for (int32_t j = 0; j < n_kept; j++) choice[(size_t)(si * n_kept + j)] = phi_vcf_choice(vcf)[si * n_haps + kept_walks[(size_t)j]];
+                vcf_walk_off.resize((size_t)n_kept + 1);
+                r = phi_vcf_walks(cx, phi_vcf_unit_first(vcf), phi_vcf_n_units(vcf), phi_vcf_site_backbone(vcf), phi_vcf_site_allele0(vcf),
+                                  n_sites, choice.data(), n_kept, vcf_walk_off.data());
+                const std::vector<uint8_t> all((size_t)n_kept, 1);
+                if (!r)
+                    r = phi_set_graph_panel(cx, phi_graph_n_vtx(g), phi_graph_seq_concat(g), phi_graph_seq_off(g), phi_graph_adj_off(g), phi_graph_adj(g),
+                                            n_kept, vcf_walk_off.data(), nullptr, all.data(), 0, 0, nullptr);
+                if (!r && cx == ctx) full_entries = vcf_walk_off[(size_t)n_kept];
+            } else if (!r && o.panel()) {
+                // --panels: the full entries stay on the device behind the first panel, and every later one starts from them
+                const uint32_t pf = panels.empty() ? 0u : PHI_PANEL_RETAIN;
+                r = phi_set_graph_panel(cx, phi_graph_n_vtx(g), phi_graph_seq_concat(g), phi_graph_seq_off(g), phi_graph_adj_off(g), phi_graph_adj(g),
+                                        phi_graph_n_walks(g), phi_graph_walk_off(g), walks_retained ? nullptr : phi_graph_walk_vtx(g), keep.data(), o.chop, pf,
+                                        nullptr);
+                if (!r && cx == ctx) full_entries = phi_graph_walk_off(g)[phi_graph_n_walks(g)];
+            } else if (!r && vcf) {
                 vcf_walk_off.resize((size_t)phi_graph_n_walks(g) + 1);
                 r = phi_vcf_walks(cx, phi_vcf_unit_first(vcf), phi_vcf_n_units(vcf), phi_vcf_site_backbone(vcf), phi_vcf_site_allele0(vcf),
                                   phi_vcf_n_real_sites(vcf), phi_vcf_choice(vcf), phi_vcf_n_kept_haps(vcf), vcf_walk_off.data());
@@ -644,6 +799,12 @@ struct Driver {
             if (r == PHI_ERR_WALK && n_dev == 1) fprintf(stderr, "Error: %s\n", phi_last_error(cx));
             return r;
         });
+        if (!rc && o.panel()) {
+            if (!panels.empty()) walks_retained = true;
+            int prc = phi_panel_stats(ctx, &panel_info);
+            if (prc) return fail_on(ctx, "panel", prc);
+            log_panel();
+        }
         phi_chop_info ci;
         if (!rc && o.chop && !phi_chop_stats(ctx, &ci)) {
             stamp("main");
@@ -736,10 +897,10 @@ struct Driver {
     int report(const phi_result &res)
     {
         const double t_report = realtime();
-        const int32_t n_walks = phi_graph_n_walks(g);
+        const int32_t n_walks = o.panel() ? (int32_t)kept_walks.size() : phi_graph_n_walks(g);      // (the names printed are the kept walks' own)
         int rc;
         fprintf(stderr, "Number of Minimizers\n");
-        for (int32_t h = 0; h < n_walks; h++) fprintf(stderr, "%s : %d\n", phi_graph_hap_name(g, h), (int)res.n_minimizers[h]);
+        for (int32_t h = 0; h < n_walks; h++) fprintf(stderr, "%s : %d\n", walk_name(h), (int)res.n_minimizers[h]);
         if (o.debug) {                                        // ILP_index.cpp:591-604
             std::vector<int64_t> hist((size_t)n_walks + 1, 0);
             int64_t n_distinct = 0;
@@ -751,7 +912,7 @@ struct Driver {
         stamp("ILP_function"); fprintf(stderr, "Haplotypes sketched\n");
         stamp("ILP_function"); fprintf(stderr, "Indexed reads with spectrum size: %d\n", (int)res.spectrum_size);
         fprintf(stderr, "Number of Anchors\n");
-        for (int32_t h = 0; h < n_walks; h++) fprintf(stderr, "%s : %d\n", phi_graph_hap_name(g, h), (int)res.n_anchors[h]);
+        for (int32_t h = 0; h < n_walks; h++) fprintf(stderr, "%s : %d\n", walk_name(h), (int)res.n_anchors[h]);
         stamp("ILP_function");
         fprintf(stderr, "Filtered/Retained Minimizers: %.2f/%.2f%%\n", (float)res.filtered / (float)res.spectrum_size * 100, (float)res.retained / (float)res.spectrum_size * 100);
         stamp("ILP_function"); fprintf(stderr, "%s model started\n", o.is_qclp ? "QP" : "ILP");
@@ -802,16 +963,23 @@ struct Driver {
             const int rc = phi_chop_origin(ctx, res.path_vtx, res.n_path, seg.data(), at.data());
             if (rc) { fprintf(stderr, "\n[E::main] recombination report: %s: %s\n", phi_strerror(rc), phi_last_error(ctx)); return; }
         }
+        // a panel: the (unchopped) vertices are the panel graph's; g's own through phi_panel_origin
+        std::vector<int32_t> orig;
+        if (o.panel()) {
+            orig.resize((size_t)res.n_path);
+            const int rc = phi_panel_origin(ctx, o.chop ? seg.data() : res.path_vtx, res.n_path, orig.data());
+            if (rc) { fprintf(stderr, "\n[E::main] recombination report: %s: %s\n", phi_strerror(rc), phi_last_error(ctx)); return; }
+        }
         for (int64_t i = 0; i < res.n_path; i++) {
-            const int32_t v = o.chop ? seg[(size_t)i] : res.path_vtx[i];
+            const int32_t v = o.panel() ? orig[(size_t)i] : o.chop ? seg[(size_t)i] : res.path_vtx[i];
             const int64_t len = o.chop ? std::max<int64_t>(0, std::min<int64_t>(o.chop, so[v + 1] - so[v] - at[(size_t)i])) : so[v + 1] - so[v];
             str_id += len;                                    // (the reference adds the vertex length before testing the label: :1515-1523)
             if (i > 0 && res.path_hap[i] != prev_hap) {
-                fprintf(stderr, ">(%s,[%lld,%lld])", phi_graph_hap_name(g, prev_hap), (long long)prev_str_id, (long long)(str_id - 1));
+                fprintf(stderr, ">(%s,[%lld,%lld])", walk_name(prev_hap), (long long)prev_str_id, (long long)(str_id - 1));
                 prev_hap = res.path_hap[i]; prev_str_id = str_id;
             }
         }
-        if (res.n_path) fprintf(stderr, ">(%s,[%lld,%lld])", phi_graph_hap_name(g, prev_hap), (long long)prev_str_id, (long long)(str_id - 1));
+        if (res.n_path) fprintf(stderr, ">(%s,[%lld,%lld])", walk_name(prev_hap), (long long)prev_str_id, (long long)(str_id - 1));
         fprintf(stderr, "\n");
     }
     // what the peak is made of: the mapped GFA file's own pages count as resident (RssFile / RssShmem), anonymous memory is the rest
@@ -831,9 +999,9 @@ struct Driver {
         fprintf(stderr, "[phi timing] main: resident now: anonymous %.3f GB, mapped files %.3f GB (the GFA among them); peak %.3f GB\n", anon / 1048576.0, (file + shm) / 1048576.0, hwm / 1048576.0);
     }
     // ---- one read set against the graph and its index: 0, 3 (the path is not proven optimal) or 1 (an error)
-    int run_job(int job)
+    int run_job(int job, bool first_of_run = false)
     {
-        if (job > 0) {
+        if (job > 0 || !first_of_run) {
             // the next read set: clocks, names, the chunk queue and the reader thread start over; the contexts forget the reads
             fflush(nullptr);
             const double now = realtime();
@@ -845,6 +1013,7 @@ struct Driver {
             if (run_on_all("reset", [&](int, phi_ctx *cx) -> int { return phi_reset_reads(cx); })) return 1;
             loaded();
         }
+        if (!hap_pattern.empty()) hap_file = hap_pattern;
         const bool ladder = !o.cov.empty();                  // (one GPU: main refuses --coverage with --devices of several)
         int rc;
         if (ladder && (rc = phi_reads_collect_begin(ctx, 0))) return fail_on(ctx, "collect", rc);
@@ -892,7 +1061,8 @@ struct Driver {
             if ((rc = phi_reads_stats(cx, &nr, nullptr, nullptr, nullptr))) return fail_on(cx, "reads", rc);
             total_reads += nr;
         }
-        stamp("ILP_function"); fprintf(stderr, "Graph has %d vertices, %d walks and read has %d reads\n", phi_graph_n_vtx(g), phi_graph_n_walks(g), (int)total_reads);
+        stamp("ILP_function"); fprintf(stderr, "Graph has %d vertices, %d walks and read has %d reads\n", o.panel() ? (int)panel_info.n_vtx_out : phi_graph_n_vtx(g),
+                                      o.panel() ? (int)kept_walks.size() : phi_graph_n_walks(g), (int)total_reads);
         phi_result res;
         if (Stage st("phi_solve (filter, exact solve, decode)"); (rc = phi_solve(ctx, &res))) return fail_on(ctx, "solve", rc);
         if (report(res)) return 1;
@@ -955,17 +1125,28 @@ static int run(const Options &o)
     int rc;
     if (Stage st("wait for the device context"); (rc = d.f_ctx.get())) return d.fail("[E::main] no usable MI355X (HIP) device %d: %s\n", devices[0], phi_strerror(rc));
     d.ctx = d.ctxs[0];
-    if (d.build_index()) return 1;
-    d.feed.mark(d.feed.index_built);                         // (the reader thread stops parking chunks: they are taken as they come now)
-    if (d.setup_exchange()) return 1;
-
-    // ---- one job per read set (-r a -o a.fa -r b -o b.fa ...): the graph, its index and the communicator are made once
+    if (d.plan_panels()) return 1;
+    // --panels: the graph file is parsed once and its walks go to the device once; every panel is set, scored and solved in
+    // turn (the reads stage runs again per panel: phi_set_graph drops what a context has seen of the reads, on purpose)
+    const size_t n_panels = std::max<size_t>(1, d.panels.size());
     int status = 0;
-    for (int job = 0; job < (int)o.reads_files.size(); job++) {
-        const int r = d.run_job(job);
-        if (r == 1) return 1;
-        if (r) status = r;
+    for (size_t pj = 0; pj < n_panels; pj++) {
+        if (!d.panels.empty()) d.mask_of(d.panels[pj], false);
+        if (d.build_index()) return 1;
+        d.feed.mark(d.feed.index_built);                     // (the reader thread stops parking chunks: they are taken as they come now)
+        if (pj == 0 && d.setup_exchange()) return 1;
+        // ---- one job per read set (-r a -o a.fa -r b -o b.fa ...): the graph, its index and the communicator are made once
+        for (int job = 0; job < (int)o.reads_files.size(); job++) {
+            if (!d.panels.empty()) {
+                d.hap_pattern = o.hap_files[(size_t)job];
+                for (size_t at; (at = d.hap_pattern.find("{panel}")) != std::string::npos;) d.hap_pattern.replace(at, 7, o.panel_names[pj]);
+            }
+            const int r = d.run_job(job, pj == 0 && job == 0);
+            if (r == 1) return 1;
+            if (r) status = r;
+        }
     }
+    if (d.walks_retained) for (phi_ctx *cx : d.ctxs) (void)phi_panel_release(cx);
     if (kn.full_teardown) d.teardown();
     return status;
 }
@@ -976,7 +1157,9 @@ int main(int argc, char *argv[])
     int help = 0;
     static struct option long_options[] = {{"version", no_argument, 0, 300}, {"device", required_argument, 0, 301}, {"dp-budget", required_argument, 0, 302},
                                            {"devices", required_argument, 0, 303}, {"shard-min-bases", required_argument, 0, 304}, {"chop", required_argument, 0, 305}, {"vcf", required_argument, 0, 306}, {"ref", required_argument, 0, 307},
-                                           {"coverage", required_argument, 0, 308}, {"genome-size", required_argument, 0, 309}, {"seed", required_argument, 0, 310}, {0, 0, 0, 0}};
+                                           {"coverage", required_argument, 0, 308}, {"genome-size", required_argument, 0, 309}, {"seed", required_argument, 0, 310},
+                                           {"keep-samples", required_argument, 0, 311}, {"drop-samples", required_argument, 0, 312}, {"panels", required_argument, 0, 313},
+                                           {"panel-seed", required_argument, 0, 314}, {"panel-always", required_argument, 0, 315}, {0, 0, 0, 0}};
     int c;
     std::string gfa_arg, vcf_arg;
     // main.cpp:38 declares -h with an argument; a bare -h falls into the usage branch either way
@@ -1015,6 +1198,27 @@ int main(int argc, char *argv[])
         }
         else if (c == 309) o.genome_size = atof(optarg);
         else if (c == 310) o.seed = strtoull(optarg, nullptr, 10);
+        else if (c == 311 || c == 312 || c == 315) {
+            std::vector<std::string> &names = c == 311 ? o.keep_samples : c == 312 ? o.drop_samples : o.panel_always;
+            const char *opt = c == 311 ? "--keep-samples" : c == 312 ? "--drop-samples" : "--panel-always";
+            if (!read_names(optarg, names)) { fprintf(stderr, "[E::main] %s: cannot read %s\n", opt, optarg + 1); return 1; }
+            if (names.empty()) { fprintf(stderr, "[E::main] %s takes sample names: A,B,.. or @FILE with one name per line\n", opt); return 1; }
+            if (c == 311) o.have_keep = true;
+            if (c == 312) o.have_drop = true;
+        }
+        else if (c == 313) {                                   // --panels 3,6,12,24: ascending counts of samples besides the always-kept ones
+            o.panel_sizes.clear(); o.panel_names.clear();
+            for (const char *p = optarg; *p;) {
+                char *end = nullptr;
+                const long v = strtol(p, &end, 10);
+                if (end == p || v < 0 || v > 1000000 || (*end && *end != ',')) { fprintf(stderr, "[E::main] --panels takes a comma-separated list of sample counts, e.g. 3,6,12,24\n"); return 1; }
+                if (!o.panel_sizes.empty() && v < o.panel_sizes.back()) { fprintf(stderr, "[E::main] --panels: the sizes must ascend (%ld follows %d)\n", v, o.panel_sizes.back()); return 1; }
+                o.panel_sizes.push_back((int)v); o.panel_names.emplace_back(p, (const char *)end);
+                p = *end == ',' ? end + 1 : end;
+            }
+            if (o.panel_sizes.empty() || o.panel_sizes.size() > 16) { fprintf(stderr, "[E::main] --panels takes 1 to 16 sizes\n"); return 1; }
+        }
+        else if (c == 314) o.panel_seed = strtoull(optarg, nullptr, 10);
         else if (c == 304) o.shard_min_bases = std::max<long long>(1, atoll(optarg));
         else if (c == 303) {                                   // --devices 0,1,2,...: shard the reads over these GPUs
             o.devices.clear();
@@ -1044,6 +1248,15 @@ int main(int argc, char *argv[])
             for (const std::string &h : o.hap_files)
                 if (h.find("{cov}") == std::string::npos) { fprintf(stderr, "[E::main] --coverage with several coverages: -o must contain {cov} (got %s), e.g. -o 'out.{cov}x.fa'\n", h.c_str()); return 1; }
     } else if (o.genome_size != 0.0) { fprintf(stderr, "[E::main] --genome-size goes with --coverage\n"); return 1; }
+    if ((int)o.have_keep + (int)o.have_drop + (int)!o.panel_sizes.empty() > 1) { fprintf(stderr, "[E::main] --keep-samples, --drop-samples and --panels exclude each other\n"); return 1; }
+    if (o.panel_sizes.empty() && !o.panel_always.empty()) { fprintf(stderr, "[E::main] --panel-always goes with --panels\n"); return 1; }
+    if (!o.panel_sizes.empty()) {
+        if (!o.cov.empty()) { fprintf(stderr, "[E::main] --panels is not supported together with --coverage\n"); return 1; }
+        if (o.devices.size() > 1) { fprintf(stderr, "[E::main] --panels runs on one GPU: not together with --devices of several\n"); return 1; }
+        if (o.panel_sizes.size() > 1)
+            for (const std::string &h : o.hap_files)
+                if (h.find("{panel}") == std::string::npos) { fprintf(stderr, "[E::main] --panels with several sizes: -o must contain {panel} (got %s), e.g. -o 'out.{panel}.fa'\n", h.c_str()); return 1; }
+    }
     o.argc = argc; o.argv = argv;
     t0_real = realtime();
 

@@ -110,6 +110,15 @@ struct phi_ctx {
         std::vector<int32_t> first;                   // [vertices as passed in + 1] first piece of every vertex
         phi_chop_info info{};
     } chop;
+    // ---- the graph was set as a panel of its walks (phi_set_graph_panel): the vertices and walks the solve names are the panel's
+    struct PhiPanel {
+        bool on = false;
+        std::vector<int32_t> origin;                  // [panel vertices] the vertex as passed in
+        std::vector<int32_t> kept;                    // [panel walks] the walk as passed in
+        phi_panel_info info{};
+        DevBuf d_full;                                // PHI_PANEL_RETAIN: the full graph's walk entries, for the next panel
+        std::vector<int64_t> full_off;                // their walk offsets (empty: nothing retained)
+    } panel;
     // ---- "set graph" from a phased VCF (phi_vcf_genotypes, phi_vcf_walks): what the last calls did
     struct PhiVcf {
         bool have = false;

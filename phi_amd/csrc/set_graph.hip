@@ -224,6 +224,7 @@ int set_graph_check_args(phi_ctx *c, int32_t n_vtx, const char *seq_concat, cons
     if (c->ipc) return phi_fail(c, PHI_ERR_STATE, "phi_set_graph on a context in a group of processes: phi_ipc_destroy first (the peers have this context's hit vectors mapped)");
     c->have_graph = false;
     c->chop.on = false;
+    c->panel.on = false;
     c->solved = false;
     phi_ladder_drop(c);                                        // (a collected read set and its bands belong to the graph they were collected under)
     return PHI_OK;

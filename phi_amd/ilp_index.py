@@ -486,8 +486,9 @@ class DeferredGraph:
         self.walk_off = _view(self._L.phi_graph_walk_off(self._h), self.num_walks + 1, C.c_int64, np.int64).copy()
         self.walk_vtx = _view(self._L.phi_graph_walk_vtx(self._h), int(self.walk_off[-1]) if self.num_walks else 0, C.c_int32, np.int32).copy()
 
-    def set_graph(self, ctx, chop=None):
-        return ctx.set_graph(self.seq_concat, self.seq_off, self.adj_off, self.adj, self.walk_off, self.walk_vtx, self.top_order_map, chop=chop)
+    def set_graph(self, ctx, chop=None, keep=None, retain=False):
+        return ctx.set_graph(self.seq_concat, self.seq_off, self.adj_off, self.adj, self.walk_off, self.walk_vtx, self.top_order_map, chop=chop,
+                             keep=keep, retain=retain)
 
 
 def read_reads(path):
