@@ -522,6 +522,13 @@ int phi_walk_entries(phi_ctx *ctx, int32_t *out, int64_t cap, int64_t *n);
  * state: a fault raised by an earlier asynchronous launch surfaces here (diagnostics; no reference counterpart). */
 int phi_device_synchronize(phi_ctx *ctx);
 
+/* (tests; no reference counterpart) The prefix sums every count / scan / write pass of the library is built on, on device
+ * memory of the caller: d_out[0 .. n] = exclusive prefix sums of d_in[0 .. n), d_out[n] = the total.  kind 0: uint8 in,
+ * int32 out; 1: int32 in, int32 out, d_out may be d_in; 2: int32 in, int64 out.  d_out holds n + 1 items and nothing behind
+ * them is written.  n < 0, another kind, d_out = NULL or d_in = NULL with n > 0: PHI_ERR_INVALID, nothing launched.  Runs on
+ * the context's stream and returns when d_out is filled. */
+int phi_prefix_sums(phi_ctx *ctx, int32_t kind, const void *d_in, int64_t n, void *d_out);
+
 /* data/edlib_edits.py:24-27, data/postprocessing_2_MIQP.py:21-42, data/get_edit_stats.sh: edlib NW edit distance of
  * pair i = (a[a_off[i]..a_off[i+1]), b[b_off[i]..b_off[i+1])), one workgroup per pair.  out[i] = distance, or -1 when
  * max_distance >= 0 and the distance exceeds it.  Needs no phi_set_params / phi_set_graph and leaves graph, reads and

@@ -36,6 +36,7 @@ SYMBOLS = [
     "phi_vcf_genotypes", "phi_vcf_walks", "phi_vcf_stats",
     "phi_reads_collect_begin", "phi_reads_collect_end", "phi_reads_collect_release", "phi_ladder_plan", "phi_ladder_advance", "phi_ladder_band",
     "phi_set_graph_panel", "phi_panel_origin", "phi_panel_walks", "phi_panel_stats", "phi_panel_release",
+    "phi_prefix_sums",
 ]
 PHI_PANEL_RETAIN = 1
 PHI_LADDER_MAX_LEVELS = 16
@@ -198,6 +199,7 @@ def load():
     L.phi_host_unregister.argtypes = [vp, vp]
     L.phi_prof_read.argtypes = [vp, C.POINTER(i64), C.POINTER(C.c_double), C.POINTER(i64)]
     L.phi_device_synchronize.argtypes = [vp]
+    L.phi_prefix_sums.argtypes = [vp, i32, vp, i64, vp]
     L.phi_walk_text_upload.argtypes = [vp, vp, i32]
     L.phi_walk_text_resolve.argtypes = [vp, C.c_char_p, i32, vp, i64, i32, vp, C.POINTER(C.c_uint32)]
     L.phi_walk_entries.argtypes = [vp, vp, i64, C.POINTER(i64)]

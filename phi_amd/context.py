@@ -614,6 +614,11 @@ class Context:
     def device_synchronize(self):
         self._chk(self._L.phi_device_synchronize(self._h))
 
+    def prefix_sums(self, kind, d_in, n, d_out):
+        """(tests) d_out[0 .. n] = exclusive prefix sums of d_in[0 .. n) over device memory given as addresses (include/phi_amd.h
+        phi_prefix_sums): kind 0 uint8 -> int32, 1 int32 -> int32 (d_out may be d_in), 2 int32 -> int64."""
+        self._chk(self._L.phi_prefix_sums(self._h, kind, C.c_void_p(d_in), n, C.c_void_p(d_out)))
+
     def prof_enable(self, on=True):
         self._chk(self._L.phi_prof_enable(self._h, int(on)))
 

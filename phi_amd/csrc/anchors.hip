@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include "phi_dev.h"
 #include "phi_kernels.h"
+#include "phi_wave.h"
 
 static inline unsigned grid_for(int64_t n, int tpb)
 {
@@ -79,7 +80,7 @@ void phi_launch_walk_edges(hipStream_t st, const int32_t *walk_vtx, const int64_
 
 // ------------------------------------------------------------------------- minimiser -> anchors (CSR)
 // The certificate on the host walks the anchors of each minimiser; grouping 10^6-10^7 anchors by
-// minimiser id is a scatter the GPU does in microseconds: count per id, scan (phi_launch_scan_i32),
+// minimiser id is a scatter the GPU does in microseconds: count per id, scan (phi_scan of scan.hip),
 // scatter through atomic cursors, then put every short list in ascending anchor order (deterministic).
 __global__ void __launch_bounds__(256) phi_csr_count_kernel(const uint32_t *__restrict__ triples, int64_t n, int64_t n_ids,
                                                             int32_t *__restrict__ cnt, uint32_t *__restrict__ err)
@@ -125,67 +126,6 @@ void phi_launch_csr_scatter(hipStream_t st, const uint32_t *triples, int64_t n, 
 void phi_launch_csr_sort(hipStream_t st, const int32_t *off, int64_t n_ids, int32_t *idx)
 {
     if (n_ids > 0) hipLaunchKernelGGL(phi_csr_sort_kernel, dim3(grid_for(n_ids, 256)), dim3(256), 0, st, off, n_ids, idx);
-}
-
-// ------------------------------------------------------------------------- ordered compaction
-// flags[n] (0/1) -> ascending list of the flagged indices.  2048 items per workgroup.
-#define CMP_ITEMS 8
-__global__ void __launch_bounds__(256) phi_flag_count_kernel(const uint8_t *__restrict__ flags, int64_t n,
-                                                             int32_t *__restrict__ block_cnt)
-{
-    __shared__ int s_w[4];
-    const int64_t base = ((int64_t)blockIdx.x * 256 + threadIdx.x) * CMP_ITEMS;
-    int c = 0;
-#pragma unroll
-    for (int j = 0; j < CMP_ITEMS; j++)
-        if (base + j < n) c += flags[base + j] != 0;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d, 64);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) block_cnt[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-}
-
-__global__ void __launch_bounds__(256) phi_flag_write_kernel(const uint8_t *__restrict__ flags, int64_t n,
-                                                             const int64_t *__restrict__ block_off,
-                                                             int32_t *__restrict__ out)
-{
-    __shared__ int s_w[4];
-    const int64_t base = ((int64_t)blockIdx.x * 256 + threadIdx.x) * CMP_ITEMS;
-    uint32_t f = 0;
-#pragma unroll
-    for (int j = 0; j < CMP_ITEMS; j++)
-        if (base + j < n && flags[base + j]) f |= 1u << j;
-    const int c = __popc(f);
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    int v = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(v, d, 64);
-        if (lane >= d) v += t;
-    }
-    if (lane == 63) s_w[wid] = v;
-    __syncthreads();
-    int woff = 0;
-    for (int i = 0; i < wid; i++) woff += s_w[i];
-    int64_t o = block_off[blockIdx.x] + woff + v - c;
-#pragma unroll
-    for (int j = 0; j < CMP_ITEMS; j++)
-        if (f & (1u << j)) out[o++] = (int32_t)(base + j);
-}
-
-int64_t phi_compact_num_blocks(int64_t n) { return (n + 256 * CMP_ITEMS - 1) / (256 * CMP_ITEMS); }
-
-void phi_launch_flag_count(hipStream_t st, const uint8_t *flags, int64_t n, int32_t *block_cnt)
-{
-    const int64_t nb = phi_compact_num_blocks(n);
-    if (nb > 0) hipLaunchKernelGGL(phi_flag_count_kernel, dim3((unsigned)nb), dim3(256), 0, st, flags, n, block_cnt);
-}
-void phi_launch_flag_write(hipStream_t st, const uint8_t *flags, int64_t n, const int64_t *block_off, int32_t *out)
-{
-    const int64_t nb = phi_compact_num_blocks(n);
-    if (nb > 0)
-        hipLaunchKernelGGL(phi_flag_write_kernel, dim3((unsigned)nb), dim3(256), 0, st, flags, n, block_off, out);
 }
 
 // ------------------------------------------------------------------------- match
@@ -277,11 +217,8 @@ __global__ void __launch_bounds__(256) phi_slot_count_kernel(PhiFilterArgs A, in
         if ((float)c >= A.limit) n_filtered++;
         else if (A.slot_multi[s]) n_model++;
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        n_filtered += __shfl_xor(n_filtered, d, 64);
-        n_model += __shfl_xor(n_model, d, 64);
-    }
+    n_filtered = phi_wave_sum(n_filtered);
+    n_model = phi_wave_sum(n_model);
     if ((threadIdx.x & 63) == 0) {
         if (n_filtered) atomicAdd(&A.counters[0], (unsigned long long)n_filtered);
         if (n_model) atomicAdd(&A.counters[1], (unsigned long long)n_model);

@@ -7,7 +7,7 @@
 // the host; the walk entries multiply (a 1-kbp segment is 34 pieces at N = 30) and at chromosome scale exist only in HBM,
 // so they are expanded where they lie:
 //     count    pieces of every entry's vertex (first[v + 1] - first[v]); an entry outside [0, n_vtx) is reported
-//     scan     64-bit exclusive scan of the counts (phi_launch_scan_i64 of dp_events.hip) = where every entry's pieces go
+//     scan     64-bit exclusive scan of the counts (phi_scan of scan.hip) = where every entry's pieces go
 //     expand   a workgroup owns a tile of CHOP_TILE consecutive OUTPUT entries -- one input entry may become a million
 //              outputs and the next one a single one --, finds the input entries that cover the tile (one search of the
 //              scanned offsets per tile, all lanes probing), stages their starts and first pieces in LDS, and every lane
@@ -168,7 +168,7 @@ int chop_expand_entries(phi_ctx *c, const int32_t *d_in, int64_t n_in, const int
     HIPCHK(hipMemsetAsync(d_bad.p, 0xFF, 8, c->stream));
     HIPCHK(hipEventRecord(ev[0], c->stream));
     phi_launch_chop_count(c->stream, d_in, n_in, d_first.as<int32_t>(), n_vtx, d_cnt.as<int32_t>(), d_bad.as<unsigned long long>());
-    PHICHK(phi_scan_counts_wide(c, d_cnt.as<int32_t>(), n_in, d_off.as<int64_t>()));
+    PHICHK(phi_scan(c, d_cnt.as<int32_t>(), n_in, d_off.as<int64_t>()));
     HIPCHK(hipEventRecord(ev[1], c->stream));
     unsigned long long bad = 0;
     int64_t n_out = 0;

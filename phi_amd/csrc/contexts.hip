@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 #include "phi_dev.h"
 #include "phi_kernels.h"
+#include "phi_wave.h"
 
 static inline unsigned grid_for(int64_t n, int tpb)
 {
@@ -94,8 +95,7 @@ __global__ void __launch_bounds__(256) phi_walk_sum_kernel(const int32_t *__rest
                 const long long mine = (e >= row_lo && e < h_end) ? v : 0;
                 acc += mine;
                 if (h_end >= e0 + 64 || h_end >= hi) break;
-#pragma unroll
-                for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
+                acc = phi_wave_sum(acc);
                 if (lane == 0 && acc) atomicAdd(&out[h], (unsigned long long)acc);
                 acc = 0;
                 row_lo = h_end;
@@ -104,8 +104,7 @@ __global__ void __launch_bounds__(256) phi_walk_sum_kernel(const int32_t *__rest
             }
         }
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
+    acc = phi_wave_sum(acc);
     if (lane == 0 && acc) atomicAdd(&out[h], (unsigned long long)acc);
 }
 static inline unsigned walk_sum_grid(int64_t n_entries)
@@ -442,22 +441,13 @@ __global__ void __launch_bounds__(256) phi_expand_kernel(PhiExpandArgs A)
         if (A.sel_cnt) cnt += A.sel_cnt[c];
         else cnt += hi - lo;
     }
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    long long v = cnt;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const long long t = __shfl_up(v, d, 64);
-        if (lane >= d) v += t;
-    }
-    if (lane == 63) s_w[wid] = v;
-    __syncthreads();
+    long long total;
+    const long long before = phi_block_excl_scan<4>((long long)cnt, s_w, &total);
     if (!WRITE) {
-        if (threadIdx.x == 0) A.block_cnt[blockIdx.x] = (int32_t)(s_w[0] + s_w[1] + s_w[2] + s_w[3]);
+        if (threadIdx.x == 0) A.block_cnt[blockIdx.x] = (int32_t)total;
         return;
     }
-    long long woff = 0;
-    for (int i = 0; i < wid; i++) woff += s_w[i];
-    int64_t o = A.block_off[blockIdx.x] + woff + v - cnt;
+    int64_t o = A.block_off[blockIdx.x] + before;
     for (int j = 0; j < EXP_ITEMS; j++) {
         const int64_t e = base + j;
         if (e >= A.e_hi) break;
@@ -577,19 +567,8 @@ __global__ void __launch_bounds__(256) phi_expand_tri_kernel(const int32_t *__re
         s_h[0] = l; s_h[1] = 0;
         s_wr[0] = P.walk_off[l]; s_wr[1] = P.walk_off[l + 1];
     }
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    int v = cnt;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(v, d, 64);
-        if (lane >= d) v += t;
-    }
-    if (lane == 63) s_w[wid] = v;
-    __syncthreads();
-    int woff = 0;
-    for (int i = 0; i < wid; i++) woff += s_w[i];
-    const int total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-    int o = woff + v - cnt;                                       // this thread's first anchor inside the block
+    int total;
+    int o = phi_block_excl_scan<4>(cnt, s_w, &total);             // this thread's first anchor inside the block
     const int64_t gbase = block_off[blockIdx.x];
     const bool staged = total <= EXP_STAGE;
     uint32_t *dst = staged ? s_out : out_tri + 3 * gbase;

@@ -72,151 +72,7 @@ void phi_launch_event_off(hipStream_t st, const phi_ent_t *ev_e, int64_t n_ev, c
                        walk_off, n_walks, ev_off);
 }
 
-// ------------------------------------------------------------------ per run: counts, prefix sums, event records
-// exclusive prefix sums of int32 counts, three phases (1024 items per workgroup)
-template <class T>
-__global__ void __launch_bounds__(256) phi_scan_blocksum_kernel(const T *__restrict__ cnt, int64_t n,
-                                                                int32_t *__restrict__ blk)
-{
-    __shared__ int s_w[4];
-    const int64_t base = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-    int c = 0;
-#pragma unroll
-    for (int j = 0; j < 4; j++) if (base + j < n) c += cnt[base + j];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d, 64);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) blk[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-}
-
-// (off may be cnt itself: a thread reads its four counts before it writes its four sums, and nobody else's)
-template <class T>
-__global__ void __launch_bounds__(256) phi_scan_apply_kernel(const T *cnt, int64_t n,
-                                                             const int64_t *__restrict__ blk_off, int32_t *off)
-{
-    __shared__ int s_w[4];
-    const int64_t base = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-    int v[4], c = 0;
-#pragma unroll
-    for (int j = 0; j < 4; j++) { v[j] = (base + j < n) ? cnt[base + j] : 0; c += v[j]; }
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    int inc = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += t;
-    }
-    if (lane == 63) s_w[wid] = inc;
-    __syncthreads();
-    int woff = 0;
-    for (int i = 0; i < wid; i++) woff += s_w[i];
-    int run = (int)blk_off[blockIdx.x] + woff + inc - c;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        if (base + j < n) off[base + j] = run;
-        run += v[j];
-    }
-    if (base <= n && n < base + 4) off[n] = run - 0;   // total (the items past n are zero)
-}
-
-// 64-bit variant (flat base offsets of the walk entries)
-__global__ void __launch_bounds__(256) phi_scan_blocksum64_kernel(const int32_t *__restrict__ cnt, int64_t n,
-                                                                  int64_t *__restrict__ blk)
-{
-    __shared__ long long s_w[4];
-    const int64_t base = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-    long long c = 0;
-#pragma unroll
-    for (int j = 0; j < 4; j++) if (base + j < n) c += cnt[base + j];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d, 64);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) blk[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-}
-
-// single-workgroup exclusive scan of 64-bit block sums (a few thousand items)
-__global__ void __launch_bounds__(1024) phi_scan_sums64_kernel(const int64_t *__restrict__ v, int64_t n, int64_t *__restrict__ off)
-{
-    __shared__ long long s_part[1024];
-    const int tid = threadIdx.x;
-    const int64_t per = (n + 1023) / 1024;
-    const int64_t lo = min(n, tid * per), hi = min(n, lo + per);
-    long long s = 0;
-    for (int64_t i = lo; i < hi; i++) s += v[i];
-    s_part[tid] = s;
-    __syncthreads();
-    if (tid == 0) {
-        long long run = 0;
-        for (int i = 0; i < 1024; i++) { const long long t = s_part[i]; s_part[i] = run; run += t; }
-        off[n] = run;
-    }
-    __syncthreads();
-    long long run = s_part[tid];
-    for (int64_t i = lo; i < hi; i++) { off[i] = run; run += v[i]; }
-}
-
-__global__ void __launch_bounds__(256) phi_scan_apply64_kernel(const int32_t *__restrict__ cnt, int64_t n,
-                                                               const int64_t *__restrict__ blk_off, int64_t *__restrict__ off)
-{
-    __shared__ long long s_w[4];
-    const int64_t base = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-    long long v[4], c = 0;
-#pragma unroll
-    for (int j = 0; j < 4; j++) { v[j] = (base + j < n) ? cnt[base + j] : 0; c += v[j]; }
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    long long inc = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const long long t = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += t;
-    }
-    if (lane == 63) s_w[wid] = inc;
-    __syncthreads();
-    long long woff = 0;
-    for (int i = 0; i < wid; i++) woff += s_w[i];
-    long long run = blk_off[blockIdx.x] + woff + inc - c;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        if (base + j < n) off[base + j] = run;
-        run += v[j];
-    }
-    if (base <= n && n < base + 4) off[n] = run;
-}
-
-int64_t phi_scan_i32_num_blocks(int64_t n) { return (n + 1 + 1023) / 1024; }
-
-void phi_launch_scan_sums_i64(hipStream_t st, const int64_t *v, int64_t n, int64_t *off)
-{
-    hipLaunchKernelGGL(phi_scan_sums64_kernel, dim3(1), dim3(1024), 0, st, v, n, off);
-}
-
-void phi_launch_scan_i64(hipStream_t st, const int32_t *cnt, int64_t n, int64_t *off, int64_t *blk, int64_t *blk_off)
-{
-    const int64_t nb = phi_scan_i32_num_blocks(n);
-    hipLaunchKernelGGL(phi_scan_blocksum64_kernel, dim3((unsigned)nb), dim3(256), 0, st, cnt, n, blk);
-    phi_launch_scan_sums_i64(st, blk, nb, blk_off);
-    hipLaunchKernelGGL(phi_scan_apply64_kernel, dim3((unsigned)nb), dim3(256), 0, st, cnt, n, blk_off, off);
-}
-
-// off[0..n] = exclusive prefix sums of cnt[0..n); blk / blk_off: scratch of phi_scan_i32_num_blocks(n) (+1) items
-void phi_launch_scan_i32(hipStream_t st, const int32_t *cnt, int64_t n, int32_t *off, int32_t *blk, int64_t *blk_off)
-{
-    const int64_t nb = phi_scan_i32_num_blocks(n);
-    hipLaunchKernelGGL(phi_scan_blocksum_kernel<int32_t>, dim3((unsigned)nb), dim3(256), 0, st, cnt, n, blk);
-    phi_launch_scan_counts(st, blk, nb, blk_off);
-    hipLaunchKernelGGL(phi_scan_apply_kernel<int32_t>, dim3((unsigned)nb), dim3(256), 0, st, cnt, n, blk_off, off);
-}
-// the same over bytes (the anchor weights of a DP run)
-void phi_launch_scan_u8(hipStream_t st, const uint8_t *cnt, int64_t n, int32_t *off, int32_t *blk, int64_t *blk_off)
-{
-    const int64_t nb = phi_scan_i32_num_blocks(n);
-    hipLaunchKernelGGL(phi_scan_blocksum_kernel<uint8_t>, dim3((unsigned)nb), dim3(256), 0, st, cnt, n, blk);
-    phi_launch_scan_counts(st, blk, nb, blk_off);
-    hipLaunchKernelGGL(phi_scan_apply_kernel<uint8_t>, dim3((unsigned)nb), dim3(256), 0, st, cnt, n, blk_off, off);
-}
-
+// ------------------------------------------------------------------ per run: event records
 // One 48-byte record per event:
 //   int4  A = { compact step | overflow << 31, entry (phi_ent_t), End (inclusive), SB }
 //         End / SB = weight-1 anchors of the walk that end at or before / begin before the entry.  With the anchors sorted by

@@ -20,6 +20,7 @@
 #include <numeric>
 #include <vector>
 #include "phi_ctx.h"
+#include "phi_wave.h"
 
 #define HIPCHK(call) do { int rc_ = phi_hip_check(c, (call), #call); if (rc_) return rc_; } while (0)
 #define PHICHK(call) do { int rc_ = (call); if (rc_) return rc_; } while (0)
@@ -78,9 +79,7 @@ __global__ void __launch_bounds__(256) phi_gfa_split_scan_kernel(const uint8_t *
             uint32_t m = nl & (w >> 1) & (tab >> 2);
             int nc = __popc(m) + ((p == 0 && (w & 1u) && (tab & 2u)) ? 1 : 0);
             if (__ballot(nc > 0)) {
-                int inc = nc;
-#pragma unroll
-                for (int d = 1; d < 64; d <<= 1) { const int v = __shfl_up(inc, d, 64); if (lane >= d) inc += v; }
+                const int inc = phi_wave_incl_scan(nc);
                 const int total = __shfl(inc, 63, 64);
                 unsigned int base = 0;
                 if (lane == 0) base = atomicAdd(n_cand, (unsigned int)total);
@@ -143,9 +142,7 @@ __global__ void __launch_bounds__(256) phi_gfa_split_line_kernel(const uint8_t *
             uint32_t m = p < e ? eq16(text, p, e, '\t') : 0u;
             if (p < s) m &= ~0u << (s - p >= 16 ? 16 : (int)(s - p));
             const int cnt = __popc(m);
-            int inc = cnt;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) { const int v = __shfl_up(inc, d, 64); if (lane >= d) inc += v; }
+            const int inc = phi_wave_incl_scan(cnt);
             const int total = __shfl(inc, 63, 64);
             if (total >= need) {
                 int64_t q = -1;

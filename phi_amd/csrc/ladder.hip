@@ -25,6 +25,7 @@
 #include <math.h>
 #include <string.h>
 #include "phi_ctx.h"
+#include "phi_wave.h"
 
 #define HIPCHK(call) do { int rc_ = phi_hip_check(c, (call), #call); if (rc_) return rc_; } while (0)
 #define PHICHK(call) do { int rc_ = (call); if (rc_) return rc_; } while (0)
@@ -101,28 +102,15 @@ __global__ void __launch_bounds__(1024) ladder_scan_kernel(int64_t *__restrict__
                                                            int64_t *__restrict__ tab)
 {
     __shared__ long long s_a[16], s_b[16], s_R[LAD_MAXL + 1], s_B[LAD_MAXL + 1];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     long long ca = 0, cb = 0;
     for (int64_t t0 = 0; t0 < M; t0 += 1024) {
         const int64_t i = t0 + tid;
         const long long va = i < M ? (long long)a[i] : 0, vb = i < M ? (long long)b[i] : 0;
-        long long xa = va, xb = vb;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const long long ya = __shfl_up(xa, d), yb = __shfl_up(xb, d);
-            if (lane >= d) { xa += ya; xb += yb; }
-        }
-        if (lane == 63) { s_a[wv] = xa; s_b[wv] = xb; }
-        __syncthreads();
-        long long pa = 0, pb = 0, ta = 0, tb = 0;
-#pragma unroll
-        for (int v = 0; v < 16; v++) {
-            const long long qa = s_a[v], qb = s_b[v];
-            if (v < wv) { pa += qa; pb += qb; }
-            ta += qa; tb += qb;
-        }
+        long long ta, tb;
+        const long long pa = phi_block_excl_scan<16>(va, s_a, &ta), pb = phi_block_excl_scan<16>(vb, s_b, &tb);
         if (i < M) {
-            const long long ea = ca + pa + xa - va, eb = cb + pb + xb - vb;
+            const long long ea = ca + pa, eb = cb + pb;
             a[i] = ea; b[i] = eb;
             if (i % nwg == 0) { s_R[i / nwg] = ea; s_B[i / nwg] = eb; }     // the first workgroup of a band: where the band starts
         }
@@ -162,12 +150,7 @@ __global__ void __launch_bounds__(LAD_TPB) ladder_scatter_kernel(const int64_t *
         const unsigned long long m = __ballot(mine);
         long long x = 0;
         if (m) {                                              // (wave-uniform)
-            x = mine ? len : 0;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const long long y = __shfl_up(x, d);
-                if (lane >= d) x += y;
-            }
+            x = phi_wave_incl_scan(mine ? len : 0);
             if (mine) {
                 my_rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
                 my_pre = x - len;

@@ -12,7 +12,7 @@
 //              stages their starts in LDS, and for every entry checks the vertex' range, flags the vertex and flags the
 //              graph edge(s) to the next entry of the same walk (a short scan of the vertex' edge list).  The flags are
 //              bytes in buffers zeroed for the call; lanes that meet on a byte store the same value: no atomics
-//     scan     the vertex flags compacted (phi_compact: flag count, 64-bit scan, ordered write) into the list of kept
+//     scan     the vertex flags compacted (phi_compact of scan.hip: flag count, 64-bit scan, ordered write) into the list of kept
 //              vertices, which a scatter turns into new_id[]
 //     remap    the same tiling; every lane writes four consecutive entries new_id[in[src]] with one 16-byte store
 //     ends     the first and the last vertex of every kept walk (what the host pass of set_graph looks at)

@@ -216,18 +216,6 @@ int phi_upload_bytes(phi_ctx *c, DevBuf &b, const void *src, size_t bytes, hipSt
 static unsigned long long *logged_stripes(phi_ctx *c) { return c->d_stripes.as<unsigned long long>(); }
 static unsigned long long *emit_stripes(phi_ctx *c) { return c->d_stripes.as<unsigned long long>() + PHI_STRIPES * 8; }
 
-// off[0..n] = exclusive prefix sums of cnt[0..n): one workgroup for a few thousand items, the three-phase
-// scan beyond (the per-chunk counts of 250 Mbases of walks are half a million items: 1 ms in one workgroup)
-int phi_scan_counts_wide(phi_ctx *c, const int32_t *cnt, int64_t n, int64_t *off)
-{
-    if (n <= 8192) { phi_launch_scan_counts(c->stream, cnt, n, off); return PHI_OK; }
-    const int64_t nb = phi_scan_i32_num_blocks(n);
-    PHICHK(phi_dev_ensure(c, c->d_scan_blk64, (size_t)nb * 8));
-    PHICHK(phi_dev_ensure(c, c->d_scan_blkoff, (size_t)(nb + 1) * 8));
-    phi_launch_scan_i64(c->stream, cnt, n, off, c->d_scan_blk64.as<int64_t>(), c->d_scan_blkoff.as<int64_t>());
-    return PHI_OK;
-}
-
 // Called by everything that observes the read state.  A reset leaves nothing pending (phi_reset_reads swaps the context's
 // double buffers, see phi_ctx.h); in a group of processes the last gather of the hit vectors runs on a stream of its own
 // (phi_ipc.hip): the context's stream waits for it here.
@@ -490,10 +478,11 @@ int phi_ctx_create(int device_id, phi_ctx **out)
         phi_warm_dp_events(c->stream); (void)hipStreamSynchronize(c->stream); tm.lap("  code object: dp_events");
         phi_warm_solve_dev(c->stream); (void)hipStreamSynchronize(c->stream); tm.lap("  code object: solve_dev");
         phi_warm_reads_text(c->stream); (void)hipStreamSynchronize(c->stream); tm.lap("  code object: reads_text");
+        phi_warm_scan(c->stream); (void)hipStreamSynchronize(c->stream); tm.lap("  code object: scan");
     }
     phi_warm_sketch(c->stream); phi_warm_table(c->stream); phi_warm_anchors(c->stream); phi_warm_contexts(c->stream);
     phi_warm_dp(c->stream); phi_warm_dp_events(c->stream); phi_warm_solve_dev(c->stream); phi_warm_reads_text(c->stream);
-    phi_warm_walk_text(c->stream);
+    phi_warm_walk_text(c->stream); phi_warm_scan(c->stream);
     if (hipStreamSynchronize(c->stream) != hipSuccess) return bail(PHI_ERR_DEVICE);
     tm.lap("scalars + code objects");
     if (aux.get() != hipSuccess) { c->aux_stream = nullptr; return bail(PHI_ERR_DEVICE); }
@@ -583,7 +572,7 @@ int sketch_records(phi_ctx *c, const uint64_t *words, const unsigned long long *
     A.err = (uint32_t *)scalar(c, S_ERR);
     if (A.allslow) phi_launch_sketch_bytes(c->stream, PHI_MODE_COUNT, A, nullptr);
     else phi_launch_sketch(c->stream, PHI_MODE_COUNT, A);
-    PHICHK(phi_scan_counts_wide(c, c->d_blk_cnt.as<int32_t>(), nb, c->d_blk_off.as<int64_t>()));
+    PHICHK(phi_scan(c, c->d_blk_cnt.as<int32_t>(), nb, c->d_blk_off.as<int64_t>()));
     int64_t total = 0;
     HIPCHK(hipMemcpyAsync(&total, c->d_blk_off.as<int64_t>() + nb, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1470,12 +1459,7 @@ int phi_walk_minimizers(phi_ctx *c, int32_t walk, uint64_t *out_hash, int64_t *o
     PHICHK(phi_dev_ensure(c, oh, (size_t)n * 8));
     PHICHK(phi_dev_ensure(c, op, (size_t)n * 8));
     phi_launch_entry_len_range(c->stream, c->d_walk_vtx.as<int32_t>(), c->d_vlen.as<int32_t>(), e_lo, ne, lens.as<int32_t>());
-    {
-        const int64_t nb = phi_scan_i32_num_blocks(ne);
-        PHICHK(phi_dev_ensure(c, c->d_scan_blk64, (size_t)nb * 8));
-        PHICHK(phi_dev_ensure(c, c->d_scan_blkoff, (size_t)(nb + 1) * 8));
-        phi_launch_scan_i64(c->stream, lens.as<int32_t>(), ne, base.as<int64_t>(), c->d_scan_blk64.as<int64_t>(), c->d_scan_blkoff.as<int64_t>());
-    }
+    PHICHK(phi_scan(c, lens.as<int32_t>(), ne, base.as<int64_t>()));
     PhiExpandArgs X{};
     X.ent_cls = c->d_ent_cls.as<int32_t>(); X.e_lo = e_lo; X.e_hi = e_hi;
     X.cls_rec_off = c->d_cls_rec_off.as<int32_t>(); X.cls_rep = c->d_cls_rep.as<phi_ent_t>();
@@ -1486,7 +1470,7 @@ int phi_walk_minimizers(phi_ctx *c, int32_t walk, uint64_t *out_hash, int64_t *o
     PHICHK(phi_dev_ensure(c, c->d_blk_off, (size_t)(nb + 1) * 8));
     X.block_cnt = c->d_blk_cnt.as<int32_t>(); X.block_off = c->d_blk_off.as<int64_t>();
     phi_launch_expand_count(c->stream, X);
-    PHICHK(phi_scan_counts_wide(c, c->d_blk_cnt.as<int32_t>(), nb, c->d_blk_off.as<int64_t>()));
+    PHICHK(phi_scan(c, c->d_blk_cnt.as<int32_t>(), nb, c->d_blk_off.as<int64_t>()));
     int64_t total = 0;
     HIPCHK(hipMemcpyAsync(&total, c->d_blk_off.as<int64_t>() + nb, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));

@@ -390,6 +390,10 @@ void phi_ipc_launch_args(phi_ctx *c, PhiSketchArgs &A);  // every read launch: t
 // sums of the striped counters (waits for the stream): novel hashes logged (with duplicates), emitted records
 int phi_read_counts(phi_ctx *c, uint64_t *n_logged, uint64_t *n_emitted);
 int phi_spectrum_count(phi_ctx *c, uint64_t *n_distinct);
-int phi_scan_counts_wide(phi_ctx *c, const int32_t *cnt, int64_t n, int64_t *off);
-// flags[n] (0/1) -> ascending list of flagged indices (int32) in out
+// scan.hip: off[0..n] = exclusive prefix sums of cnt[0..n), off[n] = the total.  On the context's stream, not waited for; the
+// scratch is the context's (d_scan_blk, d_scan_blk64, d_scan_blkoff), sized inside: one scan of a context at a time.
+int phi_scan(phi_ctx *c, const uint8_t *cnt, int64_t n, int32_t *off);
+int phi_scan(phi_ctx *c, const int32_t *cnt, int64_t n, int32_t *off);   // off may be cnt
+int phi_scan(phi_ctx *c, const int32_t *cnt, int64_t n, int64_t *off);   // one workgroup up to 8192 items, three phases beyond
+// flags[n] (0/1) -> ascending list of flagged indices (int32) in out (waits for the stream)
 int phi_compact(phi_ctx *c, const uint8_t *flags, int64_t n, DevBuf &out, int64_t *n_out);

@@ -115,7 +115,6 @@ int64_t phi_sketch_num_blocks(int64_t n_bases);
 int phi_sketch_win_reads(int k, int w, int64_t uniform_len, int64_t n_reads, int64_t n_bases);
 int64_t phi_sketch_read_chunks(int k, int w, int64_t uniform_len, int64_t n_reads, int64_t n_bases);
 void phi_launch_sketch(hipStream_t st, int mode, const PhiSketchArgs &A, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
-void phi_launch_scan_counts(hipStream_t st, const int32_t *cnt, int64_t n, int64_t *off);
 
 // table.hip
 // Insert every walk-minimiser hash; u_rep[slot] = smallest record index holding that hash
@@ -219,9 +218,6 @@ void phi_launch_csr_count(hipStream_t st, const uint32_t *triples, int64_t n, in
 void phi_launch_csr_scatter(hipStream_t st, const uint32_t *triples, int64_t n, int64_t n_ids, const int32_t *off, int32_t *cur,
                             int32_t *idx);
 void phi_launch_csr_sort(hipStream_t st, const int32_t *off, int64_t n_ids, int32_t *idx);
-int64_t phi_compact_num_blocks(int64_t n);
-void phi_launch_flag_count(hipStream_t st, const uint8_t *flags, int64_t n, int32_t *block_cnt);
-void phi_launch_flag_write(hipStream_t st, const uint8_t *flags, int64_t n, const int64_t *block_off, int32_t *out);
 void phi_launch_match_flags(hipStream_t st, const uint32_t *rec_slot, int64_t n_rec, const uint32_t *u_uid,
                             const uint8_t *hit, uint8_t *flags);
 
@@ -351,14 +347,8 @@ void phi_launch_blk_ev(hipStream_t st, const int32_t *blk_lo, int32_t n_blk, con
 void phi_launch_event_flags(hipStream_t st, const int32_t *walk_vtx, int64_t n_entries, const int32_t *cvtx, uint8_t *flags);
 void phi_launch_event_off(hipStream_t st, const phi_ent_t *ev_e, int64_t n_ev, const int64_t *walk_off, int32_t n_walks,
                           int64_t *ev_off);
-int64_t phi_scan_i32_num_blocks(int64_t n);
-void phi_launch_scan_i32(hipStream_t st, const int32_t *cnt, int64_t n, int32_t *off, int32_t *blk, int64_t *blk_off);
-// same with 64-bit sums: off[0..n] int64, blk int64 scratch
-void phi_launch_scan_i64(hipStream_t st, const int32_t *cnt, int64_t n, int64_t *off, int64_t *blk, int64_t *blk_off);
-void phi_launch_scan_sums_i64(hipStream_t st, const int64_t *v, int64_t n, int64_t *off);
 void phi_launch_dp_event_fill(hipStream_t st, const PhiDpEventArgs &A, const uint8_t *e_out, const int32_t *walk_vtx,
                               const int32_t *cvtx, const phi_ent_t *a_e1, const int32_t *wpre, int64_t n_entries);
-void phi_launch_scan_u8(hipStream_t st, const uint8_t *cnt, int64_t n, int32_t *off, int32_t *blk, int64_t *blk_off);
 int phi_dp_num_waves(int n_walks);
 void phi_launch_dp_words(hipStream_t st, const uint8_t *e_out, const int64_t *g_off, const uint8_t *g_span,
                          const uint8_t *a_weight, int64_t n_entries, uint64_t *word);
@@ -420,3 +410,4 @@ void phi_warm_dp_events(hipStream_t st);
 void phi_warm_solve_dev(hipStream_t st);
 void phi_warm_reads_text(hipStream_t st);
 void phi_warm_walk_text(hipStream_t st);
+void phi_warm_scan(hipStream_t st);

@@ -49,25 +49,6 @@ static int ensure_host_walks(phi_ctx *c)
 
 struct Seg { int32_t h; int64_t es, ee; };     // path segment: walk h, entries es..ee (inclusive)
 
-// flags[n] -> ascending indices in out; *n_out = count
-int phi_compact(phi_ctx *c, const uint8_t *flags, int64_t n, DevBuf &out, int64_t *n_out)
-{
-    *n_out = 0;
-    const int64_t nb = phi_compact_num_blocks(n);
-    if (nb == 0) return PHI_OK;
-    PHICHK(phi_dev_ensure(c, c->d_blk_cnt, (size_t)nb * 4));
-    PHICHK(phi_dev_ensure(c, c->d_blk_off, (size_t)(nb + 1) * 8));
-    phi_launch_flag_count(c->stream, flags, n, c->d_blk_cnt.as<int32_t>());
-    PHICHK(phi_scan_counts_wide(c, c->d_blk_cnt.as<int32_t>(), nb, c->d_blk_off.as<int64_t>()));
-    int64_t total = 0;
-    HIPCHK(hipMemcpyAsync(&total, c->d_blk_off.as<int64_t>() + nb, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    PHICHK(phi_dev_ensure(c, out, (size_t)std::max<int64_t>(total, 1) * 4));
-    phi_launch_flag_write(c->stream, flags, n, c->d_blk_off.as<int64_t>(), out.as<int32_t>());
-    *n_out = total;
-    return PHI_OK;
-}
-
 // the host copy of the kept anchors (a large model is solved on the device copy: solve_dev.hip)
 int phi_host_anchors(phi_ctx *c)
 {
@@ -105,22 +86,17 @@ static int dp_prepare_blocks(phi_ctx *c, int64_t n_dp)
     PHICHK(phi_dev_ensure(c, c->d_off_end, (size_t)(ne + 3) * 4));
     PHICHK(phi_dev_ensure(c, c->d_off_start, (size_t)(ne + 3) * 4));
     PHICHK(phi_dev_ensure(c, c->d_stepdiff, (size_t)(nk + 2) * 4));
-    {
-        const int64_t nb = phi_scan_i32_num_blocks(ne + 2);
-        PHICHK(phi_dev_ensure(c, c->d_scan_blk, (size_t)nb * 4));
-        PHICHK(phi_dev_ensure(c, c->d_scan_blkoff, (size_t)(nb + 1) * 8));
-    }
     int32_t *d_a = c->d_off_end.as<int32_t>(), *d_b = c->d_off_start.as<int32_t>();
     HIPCHK(hipMemsetAsync(c->d_stepdiff.p, 0, (size_t)(nk + 2) * 4, c->stream));
     if (getenv("PHI_CUT_COUNTED")) {                                   // (tests: the flags from counted coverage, as until round 4)
         HIPCHK(hipMemsetAsync(d_a, 0, (size_t)(ne + 3) * 4, c->stream));
         phi_launch_cut_cov(c->stream, c->d_a_e1.as<phi_ent_t>(), c->d_g_span.as<uint8_t>(), n_dp, d_a);
-        phi_launch_scan_i32(c->stream, d_a, ne + 1, d_b, c->d_scan_blk.as<int32_t>(), c->d_scan_blkoff.as<int64_t>());     // d_b[e + 1] = anchors a cut before e splits
+        PHICHK(phi_scan(c, d_a, ne + 1, d_b));                                                                               // d_b[e + 1] = anchors a cut before e splits
         phi_launch_cut_clean(c->stream, d_b, ne, d_a);                                                                       // d_a[e] = clean
     } else {
         phi_launch_cut_clean_direct(c->stream, c->d_g_off.as<int64_t>(), c->d_g_span.as<uint8_t>(), ne, d_a);               // d_a[e] = clean
     }
-    phi_launch_scan_i32(c->stream, d_a, ne + 1, d_b, c->d_scan_blk.as<int32_t>(), c->d_scan_blkoff.as<int64_t>());     // d_b[e] = clean entries before e
+    PHICHK(phi_scan(c, d_a, ne + 1, d_b));                                                                                   // d_b[e] = clean entries before e
     phi_launch_cut_events(c->stream, c->d_ev_e.as<phi_ent_t>(), c->n_ev, c->d_ev_off.as<int64_t>(), c->d_walk_off.as<int64_t>(), c->n_walks,
                           c->d_walk_vtx.as<int32_t>(), c->d_cvtx.as<int32_t>(), d_b, c->d_stepdiff.as<int32_t>());
     std::vector<int32_t> closed((size_t)nk + 2);
@@ -234,13 +210,8 @@ static int run_dp(phi_ctx *c, const std::vector<uint8_t> *wgt, DpHost &H, int64_
     int32_t *d_ent_src = c->d_ent.as<int32_t>(), *d_ent_h = c->d_ent.as<int32_t>() + n_ent;
     if (events) {
         // per run: prefix sums of the anchor weights -> one record per event (phi_dp_event_fill_kernel)
-        {
-            const int64_t nb = phi_scan_i32_num_blocks(n_dp);
-            PHICHK(phi_dev_ensure(c, c->d_wpre, (size_t)(n_dp + 1) * 4));
-            PHICHK(phi_dev_ensure(c, c->d_scan_blk, (size_t)nb * 4));
-            PHICHK(phi_dev_ensure(c, c->d_scan_blkoff, (size_t)(nb + 1) * 8));
-            phi_launch_scan_u8(c->stream, c->d_a_weight.as<uint8_t>(), n_dp, c->d_wpre.as<int32_t>(), c->d_scan_blk.as<int32_t>(), c->d_scan_blkoff.as<int64_t>());
-        }
+        PHICHK(phi_dev_ensure(c, c->d_wpre, (size_t)(n_dp + 1) * 4));
+        PHICHK(phi_scan(c, c->d_a_weight.as<uint8_t>(), n_dp, c->d_wpre.as<int32_t>()));
         PhiDpEventArgs A{};
         A.n_k = c->n_k; A.n_walks = c->n_walks; A.n_ev = c->n_ev;
         A.k_rec = c->d_k_rec.as<int32_t>(); A.k_in_packed = c->d_k_in.as<int32_t>();
@@ -627,7 +598,7 @@ int phi_solve_impl(phi_ctx *c)
         PHICHK(phi_dev_ensure(c, c->d_blk_off, (size_t)(nb + 1) * 8));
         X.block_cnt = c->d_blk_cnt.as<int32_t>(); X.block_off = c->d_blk_off.as<int64_t>();
         phi_launch_expand_count(c->stream, X);
-        PHICHK(phi_scan_counts_wide(c, c->d_blk_cnt.as<int32_t>(), nb, c->d_blk_off.as<int64_t>()));
+        PHICHK(phi_scan(c, c->d_blk_cnt.as<int32_t>(), nb, c->d_blk_off.as<int64_t>()));
         HIPCHK(hipMemcpyAsync(&n_kept, c->d_blk_off.as<int64_t>() + nb, 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
         if (n_kept >= (int64_t)1 << 31) return phi_fail(c, PHI_ERR_UNSUPPORTED, "more than 2^31 anchors in the model");
@@ -648,10 +619,7 @@ int phi_solve_impl(phi_ctx *c)
             // the selected records packed per class, then the anchors from those alone (contexts.hip)
             PHICHK(phi_dev_ensure(c, c->d_sel_off, (size_t)(c->n_cls + 1) * 4));
             PHICHK(phi_dev_ensure(c, c->d_sel_tri, (size_t)std::max<int64_t>(n_kept_rec, 1) * 12));
-            const int64_t nsb = phi_scan_i32_num_blocks(c->n_cls);
-            PHICHK(phi_dev_ensure(c, c->d_scan_blk, (size_t)nsb * 4));
-            PHICHK(phi_dev_ensure(c, c->d_scan_blkoff, (size_t)(nsb + 1) * 8));
-            phi_launch_scan_i32(c->stream, c->d_list3.as<int32_t>(), c->n_cls, c->d_sel_off.as<int32_t>(), c->d_scan_blk.as<int32_t>(), c->d_scan_blkoff.as<int64_t>());
+            PHICHK(phi_scan(c, c->d_list3.as<int32_t>(), c->n_cls, c->d_sel_off.as<int32_t>()));
             phi_launch_class_sel_tri(c->stream, c->d_flags2.as<uint8_t>(), c->d_cls_rec_off.as<int32_t>(), c->n_cls, c->d_sel_off.as<int32_t>(), c->d_cls_rep.as<phi_ent_t>(),
                                      c->d_rec_slot.as<uint32_t>(), c->d_u_uid.as<uint32_t>(), c->d_rec_e0.as<phi_ent_t>(), c->d_rec_e1.as<phi_ent_t>(), c->d_sel_tri.as<int32_t>());
             unsigned long long *d_ctr = c->d_ctr.as<unsigned long long>();
@@ -808,9 +776,6 @@ int phi_solve_impl(phi_ctx *c)
             const int64_t ne1 = c->n_entries + 1;
             PHICHK(phi_dev_ensure(c, c->d_off_end, (size_t)(ne1 + 2) * 4));      // (+2: also the scratch of dp_prepare_blocks)
             PHICHK(phi_dev_ensure(c, c->d_off_start, (size_t)(ne1 + 2) * 4));
-            const int64_t nb = phi_scan_i32_num_blocks(c->n_entries);
-            PHICHK(phi_dev_ensure(c, c->d_scan_blk, (size_t)nb * 4));
-            PHICHK(phi_dev_ensure(c, c->d_scan_blkoff, (size_t)(nb + 1) * 8));
             PHICHK(phi_dev_ensure(c, c->d_ev, (size_t)std::max<int64_t>(c->n_ev, 1) * 48));
         }
         PHICHK(phi_dev_ensure(c, c->d_top, (size_t)c->n_vtx * 5 * 4));
@@ -838,14 +803,10 @@ int phi_solve_impl(phi_ctx *c)
         PHICHK(phi_dev_ensure(c, c->d_sa_cur, (size_t)(n_ids + 1) * 4));
         PHICHK(phi_dev_ensure(c, c->d_sa_off, (size_t)(n_ids + 2) * 4));
         PHICHK(phi_dev_ensure(c, c->d_sa_idx, (size_t)n_dp * 4));
-        const int64_t nb = phi_scan_i32_num_blocks(n_ids);
-        PHICHK(phi_dev_ensure(c, c->d_scan_blk, (size_t)nb * 4));
-        PHICHK(phi_dev_ensure(c, c->d_scan_blkoff, (size_t)(nb + 1) * 8));
         HIPCHK(hipMemsetAsync(c->d_sa_cnt.p, 0, (size_t)(n_ids + 1) * 4, c->stream));
         HIPCHK(hipMemsetAsync(c->d_sa_cur.p, 0, (size_t)(n_ids + 1) * 4, c->stream));
         phi_launch_csr_count(c->stream, tri, n_dp, n_ids, c->d_sa_cnt.as<int32_t>(), (uint32_t *)scalar(c, S_ERR));
-        phi_launch_scan_i32(c->stream, c->d_sa_cnt.as<int32_t>(), n_ids, c->d_sa_off.as<int32_t>(), c->d_scan_blk.as<int32_t>(),
-                            c->d_scan_blkoff.as<int64_t>());
+        PHICHK(phi_scan(c, c->d_sa_cnt.as<int32_t>(), n_ids, c->d_sa_off.as<int32_t>()));
         phi_launch_csr_scatter(c->stream, tri, n_dp, n_ids, c->d_sa_off.as<int32_t>(), c->d_sa_cur.as<int32_t>(), c->d_sa_idx.as<int32_t>());
         phi_launch_csr_sort(c->stream, c->d_sa_off.as<int32_t>(), n_ids, c->d_sa_idx.as<int32_t>());
         int32_t total = 0;

@@ -1,0 +1,57 @@
+// Sums across the 64 lanes of a wave and across the waves of a workgroup: the one copy of the two idioms every scan,
+// compaction and counter of the device code is made of.  Device code only; workgroups are one-dimensional (the lane is
+// threadIdx.x & 63).  Integer sums only: the order of the additions is not part of the result.
+// (The sketch and DP kernels keep their own DPP scans and reductions, tuned to a register count: sketch.hip, dp.hip.)
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <type_traits>
+
+// the shuffles take (unsigned) int and (unsigned) long long: int64_t / uint64_t go through the latter
+template <class T>
+using phi_shfl_t = std::conditional_t<sizeof(T) == 8, std::conditional_t<std::is_signed<T>::value, long long, unsigned long long>, T>;
+
+// inclusive prefix sum over the lanes: lane l returns x of lanes 0..l
+template <class T>
+__device__ __forceinline__ T phi_wave_incl_scan(T x)
+{
+    static_assert(std::is_integral<T>::value && (sizeof(T) == 4 || sizeof(T) == 8), "int, uint32_t, int64_t, uint64_t");
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const T y = (T)__shfl_up((phi_shfl_t<T>)x, d, 64);
+        if (lane >= d) x += y;
+    }
+    return x;
+}
+
+// the sum over all 64 lanes, in every lane
+template <class T>
+__device__ __forceinline__ T phi_wave_sum(T x)
+{
+    static_assert(std::is_integral<T>::value && (sizeof(T) == 4 || sizeof(T) == 8), "int, uint32_t, int64_t, uint64_t");
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) x += (T)__shfl_xor((phi_shfl_t<T>)x, d, 64);
+    return x;
+}
+
+// Exclusive prefix sum over a workgroup of NW waves: returns the sum of `mine` over the threads before this one, and in
+// *total (optional) the sum over all of them.  s_w[NW] is LDS of the caller; one __syncthreads, which every thread of the
+// workgroup must reach.  A caller that comes back (a loop over tiles) puts a barrier of its own before the next call.
+template <int NW, class T>
+__device__ __forceinline__ T phi_block_excl_scan(T mine, T *s_w, T *total = nullptr)
+{
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const T inc = phi_wave_incl_scan(mine);
+    if (lane == 63) s_w[wid] = inc;
+    __syncthreads();
+    T woff = 0;
+    for (int i = 0; i < wid; i++) woff += s_w[i];
+    if (total) {
+        T t = 0;
+#pragma unroll
+        for (int i = 0; i < NW; i++) t += s_w[i];
+        *total = t;
+    }
+    return woff + inc - mine;
+}

@@ -22,6 +22,7 @@
 #include <stdint.h>
 #include <algorithm>
 #include "phi_kernels.h"
+#include "phi_wave.h"
 
 #define TXT_TILE 4096u          // bytes per workgroup of the line kernels: 256 lanes x 16 bytes
 
@@ -79,20 +80,13 @@ __global__ void __launch_bounds__(1024) phi_text_tiles_kernel(PhiTextArgs A, uin
     __shared__ uint32_t s_carry;
     if (threadIdx.x == 0) s_carry = 0;
     __syncthreads();
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     for (uint32_t base = 0; base < n_tiles; base += 1024) {
         const uint32_t i = base + threadIdx.x;
         const uint32_t v = i < n_tiles ? A.tile_cnt[i] : 0;
-        uint32_t x = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const uint32_t y = __shfl_up(x, o, 64); if (lane >= o) x += y; }
-        if (lane == 63) s_wave[wv] = x;
+        const uint32_t before = s_carry + phi_block_excl_scan<16>(v, s_wave);
+        if (i < n_tiles) A.tile_cnt[i] = before;
         __syncthreads();
-        uint32_t before = s_carry;
-        for (int k = 0; k < wv; k++) before += s_wave[k];
-        if (i < n_tiles) A.tile_cnt[i] = before + x - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) s_carry = before + x;
+        if (threadIdx.x == 1023) s_carry = before + v;
         __syncthreads();
     }
     if (threadIdx.x == 0) {
@@ -112,15 +106,8 @@ __global__ void __launch_bounds__(256) phi_text_lines_kernel(PhiTextArgs A)
     uint32_t n = 0;
 #pragma unroll
     for (int j = 0; j < 4; j++) n += __popc(lf_flags(w[j]));
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    uint32_t x = n;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const uint32_t y = __shfl_up(x, o, 64); if (lane >= o) x += y; }
     __shared__ uint32_t s[4];
-    if (lane == 63) s[wv] = x;
-    __syncthreads();
-    uint32_t r = A.tile_cnt[blockIdx.x] + x - n;
-    for (int k = 0; k < wv; k++) r += s[k];
+    uint32_t r = A.tile_cnt[blockIdx.x] + phi_block_excl_scan<4>(n, s);
     if (n == 0) return;
 #pragma unroll
     for (int j = 0; j < 16; j++) {
@@ -167,16 +154,6 @@ __global__ void __launch_bounds__(256) phi_text_classify_kernel(PhiTextArgs A)
 #define SCAN_ITEMS 8
 #define SCAN_BLOCK (256 * SCAN_ITEMS)
 
-__device__ __forceinline__ uint64_t wave_incl_scan64(uint64_t x, int lane)
-{
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint64_t y = __shfl_up((unsigned long long)x, o, 64);
-        if (lane >= o) x += y;
-    }
-    return x;
-}
-
 __global__ void __launch_bounds__(256) phi_text_scan_sums_kernel(PhiTextArgs A)
 {
     const uint32_t n = min(A.sum->n_nl, A.line_cap);
@@ -184,10 +161,9 @@ __global__ void __launch_bounds__(256) phi_text_scan_sums_kernel(PhiTextArgs A)
     if (base >= n) return;
     uint64_t t = 0;
     for (uint32_t i = base + threadIdx.x; i < min(n, base + SCAN_BLOCK); i += 256) t += A.pre[i];
-    const int lane = threadIdx.x & 63;
-    t = wave_incl_scan64(t, lane);
+    t = phi_wave_sum(t);
     __shared__ uint64_t s[4];
-    if (lane == 63) s[threadIdx.x >> 6] = t;
+    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = t;
     __syncthreads();
     if (threadIdx.x == 0) A.blk[blockIdx.x] = s[0] + s[1] + s[2] + s[3];
 }
@@ -200,18 +176,13 @@ __global__ void __launch_bounds__(1024) phi_text_scan_blocks_kernel(PhiTextArgs 
     __shared__ uint64_t s_carry;
     if (threadIdx.x == 0) s_carry = 0;
     __syncthreads();
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     for (uint32_t base = 0; base < nb; base += 1024) {
         const uint32_t i = base + threadIdx.x;
         const uint64_t v = i < nb ? A.blk[i] : 0;
-        const uint64_t x = wave_incl_scan64(v, lane);
-        if (lane == 63) s_wave[wv] = x;
+        const uint64_t before = s_carry + phi_block_excl_scan<16>(v, s_wave);
+        if (i < nb) A.blk[i] = before;
         __syncthreads();
-        uint64_t before = s_carry;
-        for (int k = 0; k < wv; k++) before += s_wave[k];
-        if (i < nb) A.blk[i] = before + x - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) s_carry = before + x;
+        if (threadIdx.x == 1023) s_carry = before + v;
         __syncthreads();
     }
     if (threadIdx.x == 0) A.pre[n] = s_carry;
@@ -227,13 +198,8 @@ __global__ void __launch_bounds__(256) phi_text_scan_apply_kernel(PhiTextArgs A)
     uint64_t v[SCAN_ITEMS], t = 0;
 #pragma unroll
     for (int j = 0; j < SCAN_ITEMS; j++) { v[j] = i0 + j < n ? A.pre[i0 + j] : 0; t += v[j]; }
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const uint64_t x = wave_incl_scan64(t, lane);
     __shared__ uint64_t s[4];
-    if (lane == 63) s[wv] = x;
-    __syncthreads();
-    uint64_t run = A.blk[blockIdx.x] + x - t;
-    for (int k = 0; k < wv; k++) run += s[k];
+    uint64_t run = A.blk[blockIdx.x] + phi_block_excl_scan<4>(t, s);
 #pragma unroll
     for (int j = 0; j < SCAN_ITEMS; j++) {
         if (i0 + j < n) A.pre[i0 + j] = run;

@@ -126,13 +126,7 @@ static int build_classes(phi_ctx *c, int32_t n_vtx, int32_t n_walks, int64_t n_e
                          c->d_ent_cls.as<int32_t>());
     PHICHK(phi_dev_ensure(c, c->d_list3, (size_t)nc * 4));
     phi_launch_class_len(c->stream, A, c->d_cls_rep.as<phi_ent_t>(), nc, c->d_list3.as<int32_t>(), c->d_cls_left.as<uint8_t>());
-    {
-        const int64_t nb = phi_scan_i32_num_blocks(nc);
-        PHICHK(phi_dev_ensure(c, c->d_scan_blk64, (size_t)nb * 8));
-        PHICHK(phi_dev_ensure(c, c->d_scan_blkoff, (size_t)(nb + 1) * 8));
-        phi_launch_scan_i64(c->stream, c->d_list3.as<int32_t>(), nc, c->d_cls_base.as<int64_t>(), c->d_scan_blk64.as<int64_t>(),
-                            c->d_scan_blkoff.as<int64_t>());
-    }
+    PHICHK(phi_scan(c, c->d_list3.as<int32_t>(), nc, c->d_cls_base.as<int64_t>()));
     int64_t run = 0;
     HIPCHK(hipMemcpyAsync(&run, c->d_cls_base.as<int64_t>() + nc, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));

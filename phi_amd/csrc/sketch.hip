@@ -1216,45 +1216,6 @@ __global__ void __launch_bounds__(TPB) phi_sketch_bytes_kernel(PhiSketchArgs A, 
     bytes_role<MODE>(A, batch_bad, blockIdx.x, gridDim.x, s_all);
 }
 
-// single-workgroup exclusive scan of per-block counts (off[n] = total).  Tiles of 4096 counts, four consecutive per thread:
-// the loads are coalesced whatever n is -- a chromosome-scale graph scans 1.3 M block counts here, six times per solve
-// (a thread summing its own contiguous share of the array, as before, read with a stride of 5 KB between lanes: 4.4 ms a call).
-__global__ void __launch_bounds__(1024) phi_scan_counts_kernel(const int32_t *__restrict__ cnt, int64_t n,
-                                                               int64_t *__restrict__ off)
-{
-    __shared__ int64_t s_w[16];
-    __shared__ int64_t s_carry;
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    if (tid == 0) s_carry = 0;
-    __syncthreads();
-    for (int64_t base = 0; base < n; base += 4096) {
-        const int64_t i0 = base + 4 * (int64_t)tid;
-        int32_t v[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) v[j] = i0 + j < n ? cnt[i0 + j] : 0;
-        const int64_t c = (int64_t)v[0] + v[1] + v[2] + v[3];
-        int64_t inc = c;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int64_t t = __shfl_up(inc, d, 64);
-            if (lane >= d) inc += t;
-        }
-        if (lane == 63) s_w[wid] = inc;
-        const int64_t carry = s_carry;
-        __syncthreads();
-        int64_t run = carry + inc - c;
-        for (int x = 0; x < wid; x++) run += s_w[x];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            if (i0 + j < n) off[i0 + j] = run;
-            run += v[j];
-        }
-        if (tid == 1023) s_carry = run;                   // (the last thread's running sum = everything up to the tile's end)
-        __syncthreads();
-    }
-    if (tid == 0) off[n] = s_carry;
-}
-
 // ---------------------------------------------------------------------------------- launchers
 
 void phi_launch_pack_ascii(hipStream_t st, const uint8_t *bases, int64_t n, uint64_t *words, int64_t n_words,
@@ -1414,11 +1375,6 @@ void phi_launch_sketch(hipStream_t st, int mode, const PhiSketchArgs &A0, hipEve
     if (mode == PHI_MODE_COUNT) launch_sketch_mode<PHI_MODE_COUNT>(st, nb, lds, A, t0, t1, false);
     else if (mode == PHI_MODE_WRITE) launch_sketch_mode<PHI_MODE_WRITE>(st, nb, lds, A, t0, t1, false);
     else launch_sketch_mode<PHI_MODE_PROBE>(st, nb, lds, A, t0, t1, pooled);
-}
-
-void phi_launch_scan_counts(hipStream_t st, const int32_t *cnt, int64_t n, int64_t *off)
-{
-    hipLaunchKernelGGL(phi_scan_counts_kernel, dim3(1), dim3(1024), 0, st, cnt, n, off);
 }
 
 // One empty launch loads this translation unit's code object onto the device: the HIP runtime does that lazily, at the

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include "phi_dev.h"
 #include "phi_kernels.h"
+#include "phi_wave.h"
 
 __global__ void phi_fill_u64_kernel(uint64_t *p, int64_t n, uint64_t v)
 {
@@ -254,8 +255,7 @@ __global__ void __launch_bounds__(256) phi_spectrum_insert_kernel(const uint64_t
             if (++probes > PHI_MAX_PROBE) { atomicOr(err, PHI_KERR_TABLE_FULL); break; }
         }
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) n_new += __shfl_xor(n_new, d, 64);
+    n_new = phi_wave_sum(n_new);
     if ((threadIdx.x & 63) == 0 && n_new)
         atomicAdd(sp_count + (size_t)((blockIdx.x * 4 + (threadIdx.x >> 6)) & (PHI_STRIPES - 1)) * 8, (unsigned long long)n_new);
 }
@@ -293,8 +293,7 @@ __global__ void __launch_bounds__(256) phi_spectrum_flush_kernel(const uint64_t 
             if (++probes > PHI_MAX_PROBE) { atomicOr(err, PHI_KERR_TABLE_FULL); break; }
         }
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) n_new += __shfl_xor(n_new, d, 64);
+    n_new = phi_wave_sum(n_new);
     if ((threadIdx.x & 63) == 0 && n_new)
         atomicAdd(sp_count + (size_t)((blockIdx.x * 4 + (threadIdx.x >> 6)) & (PHI_STRIPES - 1)) * 8, (unsigned long long)n_new);
 }
@@ -315,8 +314,7 @@ __global__ void __launch_bounds__(256) phi_count_flags_kernel(const uint8_t *__r
     int cnt = 0;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
         cnt += flags[i] != 0;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) cnt += __shfl_xor(cnt, d, 64);
+    cnt = phi_wave_sum(cnt);
     if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(n_out, (unsigned long long)cnt);
 }
 

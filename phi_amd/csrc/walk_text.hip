@@ -21,6 +21,7 @@
 #include <vector>
 #include "phi_ctx.h"
 #include "phi_dev.h"
+#include "phi_wave.h"
 
 #define HIPCHK(call) do { int rc_ = phi_hip_check(c, (call), #call); if (rc_) return rc_; } while (0)
 #define PHICHK(call) do { int rc_ = (call); if (rc_) return rc_; } while (0)
@@ -84,9 +85,7 @@ __global__ void __launch_bounds__(256) wt_count_kernel(const uint8_t *__restrict
         const int w = walk_of_tile(tile0, n_walks, t);
         bool rev = false;
         const uint32_t m = step_mask16(text, t * WT_TILE + 16 * (int64_t)threadIdx.x, (int64_t)walk_end[w], &rev);
-        int n = __popc(m);
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) n += __shfl_xor(n, d, 64);
+        const int n = phi_wave_sum((int)__popc(m));
         if ((threadIdx.x & 63) == 0 && n) atomicAdd(&s_cnt, n);
         if (rev) atomicOr(irregular, 1u);
         __syncthreads();
@@ -106,22 +105,14 @@ struct WtParseArgs {
 __global__ void __launch_bounds__(256) wt_parse_kernel(WtParseArgs A)
 {
     __shared__ int s_w[4];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     for (int64_t t = blockIdx.x; t < A.n_tiles; t += gridDim.x) {
         const int w = walk_of_tile(A.tile0, A.n_walks, t);
         const int64_t end = (int64_t)A.walk_end[w];
         const int64_t base = t * WT_TILE + 16 * (int64_t)threadIdx.x;
         bool rev = false;
         uint32_t m = step_mask16(A.text, base, end, &rev);
-        // rank of this thread's first step inside the tile: wave scan by shuffles, then the four waves' totals
-        const int n = __popc(m);
-        int inc = n;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const int v = __shfl_up(inc, d, 64); if (lane >= d) inc += v; }
-        if (lane == 63) s_w[wid] = inc;
-        __syncthreads();
-        int64_t rank = A.tile_off[t] + inc - n;
-        for (int x = 0; x < wid; x++) rank += s_w[x];
+        // rank of this thread's first step inside the tile
+        int64_t rank = A.tile_off[t] + phi_block_excl_scan<4>((int)__popc(m), s_w);
         __syncthreads();
         while (m) {
             const int j = __ffs((int)m) - 1;
@@ -277,7 +268,7 @@ int phi_walk_text_resolve(phi_ctx *c, const char *prefix, int32_t prefix_n, cons
                            d_end.as<unsigned long long>(), d_cnt.as<int32_t>(), d_flag.as<uint32_t>());
     }
     HIPCHK(hipMemsetAsync(d_cnt.as<int32_t>() + n_tiles, 0, 4, c->stream));
-    PHICHK(phi_scan_counts_wide(c, d_cnt.as<int32_t>(), n_tiles + 1, d_off.as<int64_t>()));
+    PHICHK(phi_scan(c, d_cnt.as<int32_t>(), n_tiles + 1, d_off.as<int64_t>()));
     hipLaunchKernelGGL(wt_walk_off_kernel, dim3((unsigned)(n_walks / 256 + 1)), dim3(256), 0, c->stream, d_tile0.as<int64_t>(), d_off.as<int64_t>(), n_walks, d_woff.as<int64_t>());
     HIPCHK(hipMemcpyAsync(walk_off_out, d_woff.p, ((size_t)n_walks + 1) * 8, hipMemcpyDeviceToHost, c->stream));
     uint32_t flag = 0;

@@ -100,3 +100,23 @@ def test_sixteen_wave_dense_dp_fits_the_lds(tmp_path):
     m = _meta(out.read_text(), "phi_dp_kernelILi16EE")
     assert m["vgpr_count"] <= 128 and m["vgpr_spill_count"] == 0 and m["private_segment_fixed_size"] == 0, m
     assert m["group_segment_fixed_size"] <= 160 * 1024, m
+
+
+def test_scan_kernels_compile_for_gfx950_without_scratch(tmp_path):
+    """Every kernel of scan.hip (the three-phase pair in its three instances, the single-workgroup scan in its two, the
+    compaction pair): no spill, no private segment."""
+    if not os.path.exists(HIPCC):
+        pytest.skip("hipcc not found")
+    out = tmp_path / "scan.s"
+    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-o", str(out),
+                           os.path.join(ROOT, "phi_amd", "csrc", "scan.hip")], stderr=subprocess.DEVNULL)
+    asm = out.read_text()
+    kernels = sorted(set(re.findall(r"^\s+\.name:\s+(\S+)$", asm.split("amdhsa.kernels:")[1], flags=re.M)))
+    kernels = [k for k in kernels if "kernel" in k]
+    for part, count in (("phi_scan_blocksum_kernel", 3), ("phi_scan_apply_kernel", 3), ("phi_scan_tiles_kernel", 2), ("phi_flag_count_kernel", 1),
+                        ("phi_flag_write_kernel", 1)):
+        assert sum(part in k for k in kernels) == count, (part, kernels)
+    for kernel in kernels:
+        m = _meta(asm, kernel)
+        print(kernel, m)
+        assert m["vgpr_spill_count"] == 0 and m["sgpr_spill_count"] == 0 and m["private_segment_fixed_size"] == 0, (kernel, m)
