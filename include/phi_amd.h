@@ -24,7 +24,11 @@
  * for the CHOPPED graph (at most 2^31 - 1 pieces, at most 2^32 - 64 chopped walk entries).  phi_vcf_genotypes / phi_vcf_walks:
  * one contig, fewer than 2^31 kept records, genotype text + matrix (4 bytes per record and sample) within device memory, fewer
  * than 65 535 ALT alleles per record, at most 1022 kept haplotypes (reference
- * included) and 2^32 - 64 walk entries, as for any graph.
+ * included) and 2^32 - 64 walk entries, as for any graph.  phi_add_reads_bam: BAM alignment records only (CRAM and SAM text are
+ * not read), a header of at most 1 GB, a record no longer than the stream's carry buffer (half of max_chunk_bytes, 16 MB at
+ * least; PHI_ERR_UNSUPPORTED beyond), the default filter of `samtools fastq` (flag & 0x900 == 0) and no other; not compared
+ * with samtools itself.  A BAM stream's device buffers -- two of (carry + max_chunk_bytes), twice that for the decoded bases and
+ * about 0.7 of it in tables: some 450 MB at a 64-MB chunk -- stay with the context until phi_ctx_destroy, as the text stream's do.
  */
 #ifndef PHI_AMD_H
 #define PHI_AMD_H
@@ -659,6 +663,52 @@ int phi_ladder_plan(phi_ctx *ctx, uint64_t seed, const double *fractions, int32_
 int phi_ladder_advance(phi_ctx *ctx, int32_t level);
 int phi_ladder_band(phi_ctx *ctx, int32_t band, int64_t *ordinals_out, int64_t cap, int64_t *n,
                     char *bases_out, int64_t bases_cap, int64_t *offsets_out, int64_t *n_bases);
+
+/*
+ * Reads from BAM: the records of the INFLATED BAM byte stream are found and decoded on the device.  Stands in
+ * for `samtools fastq` in front of ILP_index.cpp:313-328: the reads of a BAM file are, in file order, the sequences of the
+ * records with flag & 0x900 == 0 (secondary and supplementary alignments left out, both mates of a pair kept) and l_seq > 0, a
+ * record with flag & 0x10 reverse-complemented back to the read as sequenced, upper case, codes =ACMGRSVTWYHKDBN.  Dropped
+ * records get no ordinal (phi_reads_collect_*).  Rules from the SAM/BAM specification; not compared with samtools.
+ *
+ *   phi_reads_bam_begin        (ILP_index.cpp:313-328 fed by `samtools fastq`) opens the stream.  max_chunk_bytes: the largest
+ *                              piece the device takes at once (larger calls are cut); tile_bytes: bytes per tile of the record
+ *                              finder, 64 .. 49 152, <= 0 for the default (32 768).  PHI_ERR_STATE before phi_set_graph.
+ *   phi_add_reads_bam          (ILP_index.cpp:313-328 fed by `samtools fastq`) the next n >= 1 inflated bytes of the stream, pieces of
+ *                              any size, in stream order.  The header (magic, text, references) is consumed by the stream itself;
+ *                              whole records are decoded and go where phi_add_reads_device's go, the unfinished rest of a piece
+ *                              waits on the device for the next one.  PHI_ERR_INVALID, with the byte offset in the inflated stream
+ *                              in phi_last_error(), for a wrong magic, a header that is no header, and a record on the chain that
+ *                              is not well-formed (l_read_name >= 1, l_seq >= 0, block_size >= 32 + l_read_name + 4 n_cigar_op +
+ *                              (l_seq + 1) / 2 + l_seq): nothing of the failing piece is taken, what earlier pieces gave stays, the
+ *                              stream is failed and every further call on it is PHI_ERR_STATE.  PHI_ERR_UNSUPPORTED for a record
+ *                              longer than the carry buffer.
+ *   phi_add_reads_bam_parked   (ILP_index.cpp:313-328 fed by `samtools fastq`) the same with a parked piece (phi_text_park_add,
+ *                              phi_text_park_gzip_end) as the bytes; the piece stays the caller's to release.
+ *   phi_reads_bam_end          (ILP_index.cpp:313-328 fed by `samtools fastq`) closes the stream; info (may be NULL) is filled whatever
+ *                              the status.  A stream that ends inside the header or inside a record: PHI_ERR_INVALID with the
+ *                              offset; a failed stream: PHI_ERR_STATE.  A new stream may begin afterwards either way.
+ *   phi_reads_bam_last_batch   (ILP_index.cpp:313-328 fed by `samtools fastq`; tests) the reads the last piece gave, as
+ *                              phi_reads_text_last_batch.
+ */
+typedef struct {
+    int64_t n_records;                               /* records on the chain */
+    int64_t n_kept;                                  /* reads handed on */
+    int64_t n_secondary_supplementary;               /* dropped: flag & 0x900 */
+    int64_t n_empty;                                 /* dropped: l_seq == 0 (of those not dropped above) */
+    int64_t n_reverse;                               /* kept records with flag & 0x10 */
+    int64_t n_bases;
+    int64_t header_bytes;                            /* offset of the first record */
+    int64_t tiles, tiles_confirmed, tiles_rewalked;  /* tiles_confirmed: speculative lists the true chain used as they were */
+    int64_t batches, batches_without_offsets;        /* decoded batches handed to the sketch; those of one read length (>= 32) */
+    int32_t n_ref;
+    int32_t one_length;                              /* > 0: every kept read has that length; 0: several lengths, or no read */
+} phi_bam_info;
+int phi_reads_bam_begin(phi_ctx *ctx, int64_t max_chunk_bytes, int64_t tile_bytes);
+int phi_add_reads_bam(phi_ctx *ctx, const void *bytes, int64_t n);
+int phi_add_reads_bam_parked(phi_ctx *ctx, phi_text_park *park, int32_t index);
+int phi_reads_bam_end(phi_ctx *ctx, phi_bam_info *info);
+int phi_reads_bam_last_batch(phi_ctx *ctx, char *bases, int64_t cap_bases, int64_t *off, int64_t cap_reads, int64_t *n_reads, int64_t *n_bases);
 
 #ifdef __cplusplus
 }

@@ -32,8 +32,9 @@ enum {
     PHI_HOST_ERR_WALK = -2,     /* a walk holds a reverse-strand vertex (ILP_index.cpp:104-107 exits) */
     PHI_HOST_ERR_CYCLE = -3,    /* Kahn's algorithm did not reach every vertex: graph is not acyclic */
     PHI_HOST_ERR_INVALID = -4,
-    PHI_HOST_ERR_UNSUPPORTED = -5 /* a link onto the reverse strand of its target: the reference's own adjacency for it depends on
+    PHI_HOST_ERR_UNSUPPORTED = -5,/* a link onto the reverse strand of its target: the reference's own adjacency for it depends on
                                      the line's place in the file (gfa-base.cpp:269-303): refused, not guessed */
+    PHI_HOST_NEED_MORE = -6       /* phi_bam_header: the bytes given are a prefix of a header that may still be valid */
 };
 
 /* Parse S/L/W lines (plain or gzip), flip walks as gfa_walk_flip does, complete arcs with their
@@ -171,6 +172,15 @@ typedef struct phi_text_stream phi_text_stream;
 int phi_text_stream_open(const char *path, phi_text_stream **out, char *err, int err_cap);
 int64_t phi_text_stream_read(phi_text_stream *s, char *buf, int64_t cap, char *err, int err_cap);
 void phi_text_stream_close(phi_text_stream *s);
+
+/* The header of a BAM stream (SAM/BAM specification 4.2: magic BAM\1, l_text, text, n_ref, n_ref x (l_name, name, l_ref), all
+ * little-endian) from the first n INFLATED bytes of the stream: what stands in front of the records that phi_add_reads_bam
+ * (phi_amd.h) decodes, in the place of `samtools fastq` in front of ILP_index.cpp:313-328.
+ *   PHI_HOST_OK           *records_start = offset of the first alignment record, *n_ref = reference sequences
+ *   PHI_HOST_NEED_MORE    a valid prefix that ends inside the header; *records_start = a lower bound (> n) of the bytes needed
+ *   PHI_HOST_ERR_INVALID  not a BAM header (wrong magic, a negative l_text or n_ref, an l_name below 1); err names the byte offset
+ * Untrusted bytes: nothing outside bytes[0, n) is read, whatever the lengths in it say. */
+int phi_bam_header(const void *bytes, int64_t n, int64_t *records_start, int32_t *n_ref, char *err, int err_cap);
 
 /* Record id of the output: basename(gfa) minus extension + "_" + basename(reads), minus the last
  * extension of the whole string.  Returns the length or -1 if cap is too small. */

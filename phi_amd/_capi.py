@@ -37,6 +37,7 @@ SYMBOLS = [
     "phi_reads_collect_begin", "phi_reads_collect_end", "phi_reads_collect_release", "phi_ladder_plan", "phi_ladder_advance", "phi_ladder_band",
     "phi_set_graph_panel", "phi_panel_origin", "phi_panel_walks", "phi_panel_stats", "phi_panel_release",
     "phi_prefix_sums",
+    "phi_reads_bam_begin", "phi_add_reads_bam", "phi_add_reads_bam_parked", "phi_reads_bam_end", "phi_reads_bam_last_batch",
 ]
 PHI_PANEL_RETAIN = 1
 PHI_LADDER_MAX_LEVELS = 16
@@ -77,6 +78,12 @@ class PhiLadderInfo(C.Structure):
                 ("band_reads", C.c_int64 * PHI_LADDER_MAX_LEVELS), ("band_bases", C.c_int64 * PHI_LADDER_MAX_LEVELS),
                 ("threshold", C.c_uint64 * PHI_LADDER_MAX_LEVELS),
                 ("count_gpu_ms", C.c_double), ("scan_gpu_ms", C.c_double), ("scatter_gpu_ms", C.c_double), ("copy_gpu_ms", C.c_double)]
+
+
+class PhiBamInfo(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_records", "n_kept", "n_secondary_supplementary", "n_empty", "n_reverse", "n_bases", "header_bytes",
+                                         "tiles", "tiles_confirmed", "tiles_rewalked", "batches", "batches_without_offsets")] + [
+        ("n_ref", C.c_int32), ("one_length", C.c_int32)]
 
 
 class PhiResult(C.Structure):
@@ -160,6 +167,11 @@ def load():
     L.phi_text_park_destroy.argtypes = [vp]
     L.phi_text_park_destroy.restype = None
     L.phi_add_reads_text_parked.argtypes = [vp, vp, i32, C.POINTER(i32)]
+    L.phi_reads_bam_begin.argtypes = [vp, i64, i64]
+    L.phi_add_reads_bam.argtypes = [vp, vp, i64]
+    L.phi_add_reads_bam_parked.argtypes = [vp, vp, i32]
+    L.phi_reads_bam_end.argtypes = [vp, C.POINTER(PhiBamInfo)]
+    L.phi_reads_bam_last_batch.argtypes = [vp, vp, i64, vp, i64, C.POINTER(i64), C.POINTER(i64)]
     L.phi_reads_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
     L.phi_hits_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(i64)]
     L.phi_read_table.argtypes = [vp, C.POINTER(vp), C.POINTER(i64)]

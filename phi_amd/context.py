@@ -272,6 +272,42 @@ class Context:
         self._chk(self._L.phi_reads_text_detach_carry(self._h, C.byref(p), C.byref(n)))
         return C.string_at(p.value, n.value) if n.value else b""
 
+    # ------------------------------------------------------------------ reads from BAM: records found and decoded on the device
+    def reads_bam_begin(self, max_chunk_bytes=64 << 20, tile_bytes=0):
+        """Opens a BAM stream (phi_reads_bam_begin); tile_bytes <= 0: the default tile of the record finder."""
+        self._chk(self._L.phi_reads_bam_begin(self._h, int(max_chunk_bytes), int(tile_bytes)))
+
+    def add_reads_bam(self, data):
+        """The next INFLATED bytes of a BAM stream, pieces of any size in stream order: the header is consumed, whole
+        records are decoded on the device and scored (or collected), the unfinished rest waits for the next piece."""
+        buf = np.frombuffer(data, np.uint8) if not isinstance(data, np.ndarray) else data
+        self._chk(self._L.phi_add_reads_bam(self._h, _ptr(buf) if len(buf) else None, len(buf)))
+
+    def add_reads_bam_parked(self, park, index):
+        """add_reads_bam with the index-th piece of a TextPark as its bytes."""
+        self._chk(self._L.phi_add_reads_bam_parked(self._h, park._h, index))
+
+    def reads_bam_end(self):
+        """Closes the stream: the dict of phi_bam_info.  Raises PhiError -- with .info set -- when the stream ends inside its
+        header or inside a record, or had failed."""
+        info = _capi.PhiBamInfo()
+        rc = self._L.phi_reads_bam_end(self._h, C.byref(info))
+        d = {n: getattr(info, n) for n, _ in info._fields_}
+        if rc:
+            e = PhiError(rc, self._L.phi_last_error(self._h).decode())
+            e.info = d
+            raise e
+        return d
+
+    def reads_bam_last_batch(self):
+        """(uint8 bases, int64 offsets) of the reads the last piece of the BAM stream gave."""
+        nr, nb = C.c_int64(), C.c_int64()
+        self._chk(self._L.phi_reads_bam_last_batch(self._h, None, 0, None, 0, C.byref(nr), C.byref(nb)))
+        bases, off = np.zeros(nb.value, np.uint8), np.zeros(nr.value + 1, np.int64)
+        if nr.value:
+            self._chk(self._L.phi_reads_bam_last_batch(self._h, _ptr(bases), nb.value, _ptr(off), nr.value, C.byref(nr), C.byref(nb)))
+        return bases, off
+
     def add_reads_device(self, d_bases, d_read_off, n_reads, n_bases):
         self._chk(self._L.phi_add_reads_device(self._h, C.c_void_p(d_bases), C.c_void_p(d_read_off), n_reads, n_bases))
 

@@ -12,6 +12,13 @@
 //         indexed once (the reference's harness runs PHI once per sample x coverage on the same graph,
 //         data/run_batch_4_miqp.py:31-46), every job prints the log of a run of its own and writes its own FASTA
 //
+// -r reads.bam: a reads file is taken as BAM when it is gzip (BGZF or a single stream) and its inflated bytes begin with "BAM\1"
+// -- by content, not by name; a gzip FASTA whose junk before the first header begins with these four bytes is therefore read
+// as BAM.  The reads are the sequences `samtools fastq` would write with its default filter (records with flag & 0x900 left
+// out, reverse-flagged records turned back), found and decoded on the device (phi_add_reads_bam); rules from
+// the SAM/BAM specification, not compared with samtools.  Parking, several read sets, --coverage and --panels work as with
+// FASTQ; one GPU only (refused with --devices of several).  CRAM and SAM text are refused.  One [M::main] BAM line states the counts.
+//
 // --devices: one context and one host thread per GPU; every GPU builds the full index, the chunks of the reads file are
 // handed out in turn, the library's RCCL exchange (phi_comm_*) merges hit vectors and spectra once, and the first
 // GPU solves and reports.  A read set smaller than --shard-min-bases per GPU uses fewer GPUs.
@@ -32,6 +39,7 @@
 // harness that starts the next GPU job at once would find them still held.
 // Exit status: 0; 1 on any error; 3 when --dp-budget was given and ran out before the path was proven optimal.
 #include <errno.h>
+#include <fcntl.h>
 #include <stdarg.h>
 #include <getopt.h>
 #include <signal.h>
@@ -55,6 +63,7 @@
 #include <mutex>
 #include <thread>
 #include <vector>
+#include <zlib.h>
 #include "../../../include/phi_amd.h"
 #include "../../../include/phi_host.h"
 
@@ -140,6 +149,7 @@ struct Options {
     long long shard_min_bases = 50000000;                     // --shard-min-bases: text bytes of reads a further GPU must be worth
     float threshold = 1.0f;
     std::string gfa_file, reads_file, hap_file;               // (reads_file / hap_file: the first job's, for the usage text)
+    std::vector<int> reads_kinds;                             // per -r: its ReadsKind, decided once in main (from a regular file's first bytes)
     std::string vcf_ref;                                      // --vcf FILE --ref FILE: the graph from a phased VCF (gfa_file holds the VCF's name then)
     bool from_vcf = false;
     int vcf_max_len = 30;                                     // its segments' length (--chop N; gfa2gbwt -m 30, vcf2gfa.py:53)
@@ -231,6 +241,33 @@ static FileProbe probe_file(const std::string &path)
     }
     return p;
 }
+// ---- what a reads file holds, by CONTENT: BAM when it is gzip (BGZF or not) and its inflated bytes begin with "BAM\1" -- so a
+// gzip FASTA whose junk before the first header begins with these four bytes is read as BAM --; CRAM by its magic and SAM text
+// by a header line with its first field at its start (@HD\tVN:, @SQ\tSN:, @RG\tID:, @PG\tID:), both refused (only their names are known here); everything else is FASTA / FASTQ text.
+enum ReadsKind { READS_TEXT, READS_BAM, READS_CRAM, READS_SAM };
+// Only a REGULAR file is looked at, and with pread: nothing is ever consumed from a pipe, a FIFO or a process substitution
+// (-r <(samtools fastq x.bam)), which are text for the reader to take as it always has.  Decided once per -r (Options::reads_kinds).
+static ReadsKind reads_kind(const std::string &path)
+{
+    struct stat st;
+    if (stat(path.c_str(), &st) != 0 || !S_ISREG(st.st_mode)) return READS_TEXT;      // (the reader reports what cannot be opened)
+    const int fd = open(path.c_str(), O_RDONLY);
+    if (fd < 0) return READS_TEXT;
+    unsigned char u[8] = {0};
+    const ssize_t got = pread(fd, u, 7, 0);
+    close(fd);
+    if (got >= 4 && !memcmp(u, "CRAM", 4)) return READS_CRAM;
+    // SAM text: a header line with its first mandatory field (a FASTQ whose first read is merely NAMED HD, SQ, RG or PG stays text)
+    if (got == 7 && (!memcmp(u, "@HD\tVN:", 7) || !memcmp(u, "@SQ\tSN:", 7) || !memcmp(u, "@RG\tID:", 7) || !memcmp(u, "@PG\tID:", 7))) return READS_SAM;
+    if (got < 2 || u[0] != 0x1f || u[1] != 0x8b) return READS_TEXT;
+    gzFile gz = gzopen(path.c_str(), "rb");
+    if (!gz) return READS_TEXT;
+    unsigned char m[4];
+    const int n = gzread(gz, m, 4);
+    gzclose(gz);
+    return n == 4 && !memcmp(m, "BAM\1", 4) ? READS_BAM : READS_TEXT;
+}
+
 // a single-stream gzip file (not BGZF: that is the host pool's) of at least `least` bytes: one of the device inflaters' inputs
 static bool single_gzip(const FileProbe &p, int64_t least) { return p.regular && p.size >= std::max<int64_t>(least, 18) && p.gzip && !p.bgzf; }
 static bool read_file(const std::string &path, int64_t size, std::vector<char> &out)
@@ -503,6 +540,7 @@ struct Driver {
     phi_vcf *vcf = nullptr;                                   // --vcf: the reader's handle (the unit tables build_index writes the walks from)
     char err[512] = "";
     std::string reads_file, hap_file;                         // the job at hand, and the name in its FASTA
+    int reads_kind_now = 0;                                   // the job's ReadsKind (Options::reads_kinds)
     char hap_name[4096];
     std::atomic<bool> failed{false};                          // a GPU failed in the phase at hand (run_on_all)
     bool use_peers = false;                                   // the exchange: peer-mapped memory or RCCL (comm_id)
@@ -518,7 +556,7 @@ struct Driver {
     bool walks_retained = false;                              // --panels: the full entries are on the device (PHI_PANEL_RETAIN)
     phi_panel_info panel_info{};
     long long full_entries = 0;                               // walk entries handed to the panel step
-    explicit Driver(const Options &opt) : o(opt), devices(opt.devices), reads_file(opt.reads_files[0]), hap_file(opt.hap_files[0]) {}
+    explicit Driver(const Options &opt) : o(opt), devices(opt.devices), reads_file(opt.reads_files[0]), hap_file(opt.hap_files[0]), reads_kind_now(opt.reads_kinds.empty() ? 0 : opt.reads_kinds[0]) {}
 
     // the one error exit: the message, the reader thread stopped, status 1
     __attribute__((format(printf, 2, 3))) int fail(const char *fmt, ...)
@@ -857,8 +895,38 @@ struct Driver {
     // ---- reads (main.cpp:136-137) and stage 1b/2a (:615-655) on one GPU, chunk by chunk.  The chunks are taken in stream order,
     //      one GPU at a time (a chunk needs the unfinished rest of the one before); the sketch of a chunk runs on behind the turn.
     //      Text that is not laid out regularly goes through the host reader from that byte on.
+    // ---- a BAM reads file (reads_kind): the same chunks -- the BGZF layer inflated by the host pool, or a single gzip stream by
+    //      the device inflater, parked or not -- go to phi_add_reads_bam, which finds and decodes the records on the device
+    //      (DESIGN.md 4.14).  One GPU: main refuses a BAM with --devices of several.
+    int feed_reads_bam(phi_ctx *cx)
+    {
+        ReadsFeed &f = feed;
+        int r = phi_reads_bam_begin(cx, f.chunk_bytes, Knobs::num("PHI_BAM_TILE", 0));
+        const bool open = r == PHI_OK;
+        while (!r) {
+            const int slot = f.take_full();
+            Chunk &cb = *f.at(slot);
+            if (cb.n < 0) { r = PHI_ERR_INVALID; fprintf(stderr, "[E::main] %s\n", f.err); break; }
+            if (cb.n == 0) break;                             // (the end marker stays in the queue)
+            if (++f.n_chunks >= 2) f.pin_buffers(cx);
+            f.stream_fed += cb.n;
+            if (cb.parked >= 0) {
+                r = phi_add_reads_bam_parked(cx, f.park, cb.parked);
+                (void)phi_text_park_release(f.park, cb.parked);
+            } else r = phi_add_reads_bam(cx, cb.text, cb.n);
+            f.give_free(slot);
+        }
+        phi_bam_info bi;
+        if (open) { const int r2 = phi_reads_bam_end(cx, &bi); if (!r) r = r2; }
+        if (!r)
+            fprintf(stderr, "[M::main] BAM %s: %lld records, %lld reads kept (%lld stored reverse), %lld secondary/supplementary and %lld without sequence dropped; %d reference(s); "
+                            "%lld tiles, %lld confirmed, %lld walked again\n", reads_file.c_str(), (long long)bi.n_records, (long long)bi.n_kept, (long long)bi.n_reverse,
+                    (long long)bi.n_secondary_supplementary, (long long)bi.n_empty, (int)bi.n_ref, (long long)bi.tiles, (long long)bi.tiles_confirmed, (long long)bi.tiles_rewalked);
+        return r;
+    }
     int feed_reads(phi_ctx *cx)
     {
+        if (reads_kind_now == READS_BAM) return feed_reads_bam(cx);
         ReadsFeed &f = feed;
         int r = phi_reads_text_begin(cx, f.chunk_bytes);
         bool open = r == PHI_OK;
@@ -1008,6 +1076,7 @@ struct Driver {
             cpu0 += cputime(); t0_real = now;
             g_marks.clear();
             reads_file = o.reads_files[(size_t)job]; hap_file = o.hap_files[(size_t)job];
+            reads_kind_now = o.reads_kinds[(size_t)job];
             if (name_job()) return 1;
             feed.start(reads_file);
             if (run_on_all("reset", [&](int, phi_ctx *cx) -> int { return phi_reset_reads(cx); })) return 1;
@@ -1241,6 +1310,13 @@ int main(int argc, char *argv[])
         return 1;
     }
     if (o.reads_files.size() != o.hap_files.size()) { fprintf(stderr, "[E::main] %zu -r but %zu -o: several read sets against one graph are given as -r a.fq -o a.fa -r b.fq -o b.fa ...\n", o.reads_files.size(), o.hap_files.size()); return 1; }
+    for (const std::string &rf : o.reads_files) {
+        const ReadsKind kind = reads_kind(rf);
+        o.reads_kinds.push_back((int)kind);
+        if (kind == READS_CRAM) { fprintf(stderr, "[E::main] %s is a CRAM file: reads are taken from FASTA, FASTQ and BAM; convert it first (samtools view -b, or samtools fastq)\n", rf.c_str()); return 1; }
+        if (kind == READS_SAM) { fprintf(stderr, "[E::main] %s is SAM text: reads are taken from FASTA, FASTQ and BAM; convert it first (samtools view -b, or samtools fastq)\n", rf.c_str()); return 1; }
+        if (kind == READS_BAM && o.devices.size() > 1) { fprintf(stderr, "[E::main] %s is a BAM file: BAM reads run on one GPU, not together with --devices of several (a BAM is not sharded over contexts)\n", rf.c_str()); return 1; }
+    }
     if (!o.cov.empty()) {
         if (!(o.genome_size > 0.0)) { fprintf(stderr, "[E::main] --coverage needs --genome-size N (the bases of the region the coverages refer to)\n"); return 1; }
         if (o.devices.size() > 1) { fprintf(stderr, "[E::main] --coverage runs on one GPU: not together with --devices of several (sharded ladders are not supported)\n"); return 1; }

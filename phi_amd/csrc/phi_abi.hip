@@ -527,6 +527,7 @@ void phi_ctx_destroy(phi_ctx *c)
         if (T.h_sum) (void)hipHostFree(T.h_sum);
         if (T.ev_copy) (void)hipEventDestroy(T.ev_copy);
     }
+    phi_bam_drop(c);
     (void)hipStreamDestroy(c->own_stream);
     (void)hipStreamDestroy(c->aux_stream);
     delete c;
@@ -1644,3 +1645,13 @@ int phi_prof_read(phi_ctx *c, int64_t *n_launches, double *total_ms, int64_t *to
 }
 
 }  // extern "C"
+
+// a parked piece's device bytes for the streams that live beside their kernels (bam.hip): waits until they have landed
+int phi_text_park_piece_dev(phi_text_park *p, int32_t index, int device, const void **d, int64_t *n)
+{
+    phi_text_park::Piece *pc = park_piece(p, index);
+    if (!pc || p->device != device) return PHI_ERR_INVALID;
+    if (pc->ev && hipEventSynchronize(pc->ev) != hipSuccess) { (void)hipGetLastError(); return PHI_ERR_DEVICE; }
+    *d = pc->d.p; *n = pc->n;
+    return PHI_OK;
+}

@@ -213,6 +213,27 @@ struct phi_ctx {
         uint32_t why = 0, first_bad = 0;
     } text;
 
+    // ---- reads from BAM (phi_add_reads_bam, bam.hip): the device finds the records of the inflated byte stream and decodes them
+    struct PhiBamStream {
+        bool active = false, failed = false, header_done = false;
+        int32_t n_ref = 0;
+        uint32_t tile = 0, list_cap = 0, max_tiles = 0, max_rec = 0;   // bytes per tile; record starts a tile's list holds; table sizes
+        uint32_t carry_cap = 0, chunk_cap = 0;
+        std::vector<unsigned char> h_hdr;             // the stream's first bytes, until they hold the whole header
+        int64_t fed = 0;                              // bytes of the stream handed to the device so far, header included
+        DevBuf text[2];                               // [carry | piece]: the carry of piece i is copied in front of piece i + 1 in the other slot
+        DevBuf bases, roff, sum;                      // the decoded batch; the device summary
+        DevBuf t_first, t_exit, t_status, t_cnt, t_skip, t_list, t_has, t_has_pre, t_use, t_base;   // per tile
+        DevBuf rec_pos, rec_keep, kidx, klen, kseq, krev;                                             // per record / per kept record
+        int slot = 0;
+        uint32_t carry_len = 0, carry_at = 0;         // the carry: text[slot][carry_at, carry_at + carry_len)
+        void *h_sum = nullptr;                        // pinned
+        hipEvent_t ev_copy = nullptr;                 // the piece's copy (aux_stream) has landed
+        int64_t one_len = -1;                         // -1 no read yet, -2 several lengths, else the one length
+        int64_t dbg_reads = 0, dbg_bases = 0;         // what the last piece gave (phi_reads_bam_last_batch)
+        phi_bam_info info{};
+    } bam;
+
     // ---- a ladder of coverages from one read set (ladder.hip): the collected store, and its partition into bands
     struct PhiLadder {
         bool collecting = false, have_store = false, have_plan = false;
@@ -372,6 +393,10 @@ int chop_expand_entries(phi_ctx *c, const int32_t *d_in, int64_t n_in, const int
 extern const int phi_device_poison;
 int phi_dev_poison_fill(void *p, size_t bytes);         // 0 = filled
 static inline int phi_dev_poison(void *p, size_t bytes) { return phi_device_poison < 0 ? 0 : phi_dev_poison_fill(p, bytes); }
+// bam.hip
+void phi_bam_drop(phi_ctx *c);                         // the stream's buffers let go (the context's end)
+// a parked piece's bytes on `device`, landed (phi_abi.hip owns the park): PHI_ERR_INVALID when there is no such piece there
+int phi_text_park_piece_dev(phi_text_park *p, int32_t index, int device, const void **d, int64_t *n);
 // ladder.hip
 int phi_ladder_collect(phi_ctx *c, const void *d_bases, const void *d_read_off, int64_t n_reads, int64_t n_bases);   // the hook of phi_add_reads_device_impl
 void phi_ladder_drop(phi_ctx *c);                      // store and plan let go (a new graph, the context's end)

@@ -35,7 +35,9 @@ HOST_SYMBOLS = [
     "phi_vcf_rec_gt_index", "phi_vcf_rec_alt_off", "phi_vcf_alt_pos", "phi_vcf_alt_bytes", "phi_vcf_site_off", "phi_vcf_text", "phi_vcf_text_off",
     "phi_vcf_parse_gt", "phi_vcf_build", "phi_vcf_n_units", "phi_vcf_unit_first", "phi_vcf_n_real_sites", "phi_vcf_site_backbone",
     "phi_vcf_site_allele0", "phi_vcf_n_kept_haps", "phi_vcf_choice",
+    "phi_bam_header",
 ]
+PHI_HOST_NEED_MORE = -6
 
 WALK_TEXT_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_int32)
 
@@ -120,6 +122,7 @@ def host_lib():
     L.phi_vcf_parse_gt.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, C.c_int32, vp, vp, C.c_char_p, C.c_int]
     L.phi_vcf_build.argtypes = [vp, vp, vp, C.c_int32, C.POINTER(vp), C.c_char_p, C.c_int]
     L.phi_write_fasta.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int64]
+    L.phi_bam_header.argtypes = [vp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_char_p, C.c_int]
     for n in HOST_SYMBOLS:
         getattr(L, n)
     _host = L
@@ -169,6 +172,59 @@ def text_chunks(path, chunk_bytes=64 << 20):
             yield buf[:n].copy()
     finally:
         L.phi_text_stream_close(h)
+
+
+def bam_header(data):
+    """phi_bam_header on the first inflated bytes of a BAM stream: (status, records_start, n_ref, message); status 0,
+    PHI_HOST_NEED_MORE (records_start: a lower bound of the bytes needed) or PHI_HOST_ERR_INVALID."""
+    L = host_lib()
+    buf = np.frombuffer(data, np.uint8) if not isinstance(data, np.ndarray) else data
+    start, n_ref = C.c_int64(), C.c_int32()
+    err = C.create_string_buffer(256)
+    rc = L.phi_bam_header(buf.ctypes.data if len(buf) else None, len(buf), C.byref(start), C.byref(n_ref), err, 256)
+    return rc, start.value, n_ref.value, err.value.decode()
+
+
+def reads_file_kind(path):
+    """What the command line takes a reads file for, by content: "bam" (gzip whose inflated bytes begin with BAM\\1), "cram",
+    "sam" (plain text that begins with a SAM header line and its first field) or "text" (FASTA / FASTQ, plain or gzip).  Only a
+    regular file is looked at; a pipe, a missing or an unreadable file is "text", for the reader to take or to report."""
+    import gzip
+    try:
+        if not os.path.isfile(path):
+            return "text"
+        with open(path, "rb") as f:
+            head = f.read(7)
+        if head[:4] == b"CRAM":
+            return "cram"
+        if head[:2] == b"\x1f\x8b":
+            with gzip.open(path, "rb") as f:
+                return "bam" if f.read(4) == b"BAM\x01" else "text"
+    except (OSError, EOFError):
+        return "text"
+    return "sam" if head in (b"@HD\tVN:", b"@SQ\tSN:", b"@RG\tID:", b"@PG\tID:") else "text"
+
+
+class BamReads:
+    """A BAM reads file as an entry of ip_reads: its records are found and decoded on the device (Context.add_reads_bam) when
+    ILP_function scores the reads; the file's BGZF layer is inflated by the host pool (text_chunks)."""
+
+    def __init__(self, path, chunk_bytes=64 << 20):
+        self.path, self.chunk_bytes, self.info = path, chunk_bytes, None
+
+    def feed(self, ctx):
+        ctx.reads_bam_begin(self.chunk_bytes)
+        try:
+            for chunk in text_chunks(self.path, self.chunk_bytes):
+                ctx.add_reads_bam(chunk)
+        except Exception:
+            try:
+                ctx.reads_bam_end()
+            except PhiError:
+                pass
+            raise
+        self.info = ctx.reads_bam_end()
+        return self.info
 
 
 def reads_of_text(prefix, blocks=(), bases_cap=64 << 20, reads_cap=1 << 20, stream_offset=0):
@@ -549,7 +605,15 @@ class ILP_index:
         self.top_order_map = self.graph.top_order_map
 
     # -- ILP_index::read_ip_reads (ILP_index.cpp:313-328): appends (name, sequence) pairs
+    #    A BAM file (by content, as the command line decides: reads_file_kind) becomes ONE entry, a BamReads: its reads are
+    #    decoded on the device when ILP_function scores them, in the place of `samtools fastq` in front of this reader.
     def read_ip_reads(self, ip_reads, ip_reads_file):
+        kind = reads_file_kind(ip_reads_file)
+        if kind == "bam":
+            ip_reads.append(BamReads(ip_reads_file))
+            return
+        if kind in ("cram", "sam"):
+            raise HostError(-5, f"{ip_reads_file} is {kind.upper()}{' text' if kind == 'sam' else ''}: reads are taken from FASTA, FASTQ and BAM only")
         bases, off, names = read_reads(ip_reads_file)
         raw = bases.tobytes()
         for i, nm in enumerate(names):
@@ -565,8 +629,10 @@ class ILP_index:
         if self.graph is None:
             raise PhiError(_capi.PHI_ERR_STATE, "ILP_function before read_gfa")
         G = self.graph
-        seqs = [r[1] if isinstance(r, tuple) else r for r in ip_reads]
-        self._stamp(f"Graph has {G.n_vtx} vertices, {G.num_walks} walks and read has {len(seqs)} reads")
+        bams = [r for r in ip_reads if isinstance(r, BamReads)]
+        seqs = [r[1] if isinstance(r, tuple) else r for r in ip_reads if not isinstance(r, BamReads)]
+        if not bams:
+            self._stamp(f"Graph has {G.n_vtx} vertices, {G.num_walks} walks and read has {len(seqs)} reads")
         ctx = Context(self.device)
         try:
             flags = (_capi.PHI_FLAG_QCLP if self.is_qclp else 0) | (_capi.PHI_FLAG_MIXED if self.is_mixed else 0)
@@ -577,6 +643,12 @@ class ILP_index:
                 self._stamp(f"Graph chopped to {self.chop} bases: {cs['n_vtx_in']} -> {cs['n_vtx_out']} vertices, "
                             f"{cs['n_entries_in']} -> {cs['n_entries_out']} walk entries")
             ctx.add_reads(seqs)
+            for b in bams:
+                bi = b.feed(ctx)
+                print(f"BAM {b.path}: {bi['n_records']} records, {bi['n_kept']} reads kept ({bi['n_reverse']} reverse), "
+                      f"{bi['n_secondary_supplementary']} secondary/supplementary and {bi['n_empty']} without sequence dropped", file=self.log)
+            if bams:
+                self._stamp(f"Graph has {G.n_vtx} vertices, {G.num_walks} walks and read has {ctx.reads_stats()['n_reads']} reads")
             res = ctx.solve()
             if self.chop is not None:                          # the path in the caller's vertices: (segment, offset of the piece)
                 res["path_orig_vtx"], res["path_orig_off"] = ctx.chop_origin(res["path_vtx"])
