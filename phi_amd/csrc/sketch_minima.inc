@@ -1,6 +1,7 @@
-// sketch_minima.inc -- phase 2 of the sketch kernels (sketch.hip): the minima of the Q + 1 windows of a lane from the
-// k-mers at s_q.  Included by sketch_phases.inc (base positions) and by phi_sketch_win_kernel (windows of reads of one
-// length): the two differ in where a lane's k-mers lie, not in how their minima are taken.  Defines SQ, wv and wp.
+// sketch_minima.inc -- phase 2 of the sketch kernels: the minima of the Q + 1 windows of a lane from the
+// k-mers at s_q.  Included by sketch_phases.inc (base positions) and by phi_sketch_win_kernel (sketch.hip) and
+// phi_sketch_winfix_kernel (sketch_win_fixed.hip; windows of reads of one length): the two differ in where a lane's
+// k-mers lie, not in how their minima are taken.  Defines SQ, wv and wp.
     // ---- phase 2: minima of windows la = lane*Q .. lane*Q+Q  (window la = m[la .. la+w)); the
     //      k-mer of slot lane*Q + x is s_q[x + (x >> 3)]: constant offsets from one address
 #define SQ(x) s_q[(x) + ((x) >> 3)]

@@ -1,7 +1,8 @@
-// sketch_phases.inc -- phases 0 .. 3b of the sketch kernels (sketch.hip): staging of a chunk, canonical k-mers, window
-// minima, read starts, candidate flags, items.  Included in the body of phi_sketch_kernel (one chunk per wave) and of
-// phi_sketch_pool_kernel (a wave takes several chunks of a read batch): the text is the same, the kernels differ in what
-// surrounds it.  Expects the names both kernels declare before the #include.
+// sketch_phases.inc -- phases 0 .. 3b of the base-space sketch kernels: staging of a chunk, canonical k-mers, window
+// minima, read starts, candidate flags, items.  Included in the body of phi_sketch_kernel (sketch.hip: one chunk per
+// wave) and of phi_sketch_pool_kernel (sketch_pooled.hip: a wave takes several chunks of a read batch): the text is the
+// same, the kernels differ in what surrounds it.  Expects the names both kernels declare before the #include, and
+// sketch_dev.h.
     // ---- phase 0: stage the chunk's packed words and bitmaps (the only global reads up to the
     //      output phase).  Local base lb <-> base c0-32+lb; local bit lp <-> base c0-64+lp.
     unsigned long long my_bad = 0;

@@ -1,7 +1,8 @@
-// sketch_rounds.inc -- phases 4 + 5 of the one-wave-per-chunk sketch kernels (sketch.hip): the chunk's items on dense
+// sketch_rounds.inc -- phases 4 + 5 of the one-wave-per-chunk sketch kernels: the chunk's items on dense
 // lanes, 64 per round -- murmur3 of the item's minimum, the hash-change test against the item before it (the lane below;
-// lane 0 takes the last lane of the round before), ordered compaction, output.  Included by phi_sketch_kernel and by
-// phi_sketch_win_kernel; expects the names they declare before the #include.
+// lane 0 takes the last lane of the round before), ordered compaction, output.  Included by phi_sketch_kernel and
+// phi_sketch_win_kernel (sketch.hip) and by phi_sketch_winfix_kernel (sketch_win_fixed.hip); expects the names they
+// declare before the #include.
     if (ncand > 0) {
         uint64_t carry = PHI_EMPTY_KEY;
         for (int r0 = 0; r0 <= ncand; r0 += 64) {

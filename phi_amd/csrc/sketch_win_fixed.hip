@@ -1,6 +1,6 @@
 // sketch_win_fixed.hip -- the window-space read kernel with its whole geometry known at compile time: 150-bp reads at
-// the reference's defaults k = 31, w = 25 (its own data and every one-length bench set).  sketch.hip is compiled again here
-// for its helpers alone (as sketch_pooled.hip does for the pooled instances); phi_launch_sketch calls the launcher below
+// the reference's defaults k = 31, w = 25 (its own data and every one-length bench set).  The helpers it shares with the
+// kernels of sketch.hip and sketch_pooled.hip come from sketch_dev.h; phi_launch_sketch calls the launcher below
 // whenever it takes window space for such a batch.  PHI_SKETCH_WIN_FIXED=0 sends those batches to phi_sketch_win_kernel.
 //
 // What phi_sketch_win_kernel computes at run time is constant here:
@@ -12,9 +12,7 @@
 //  - every window of a lane exists (V = 96 = 8 G): phase 3 has no `imax`.
 // Phases 2 - 5, the byte-wise routine for bases outside ACGTacgt, the log, clean_finish and the epilogue are those of
 // phi_sketch_win_kernel, and so are its outputs.
-#define PHI_SKETCH_POOLED_TU 1
-#define PHI_SKETCH_WIN_FIXED_TU 1
-#include "sketch.hip"
+#include "sketch_dev.h"
 
 // reverse complement of 16 bases in 2 bits (first base in the top bits)
 __device__ __forceinline__ uint32_t revcomp16(uint32_t x)

@@ -14,6 +14,7 @@ from conftest import ROOT
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 SRC = os.path.join(ROOT, "phi_amd", "csrc", "sketch.hip")
+DEV = os.path.join(ROOT, "phi_amd", "csrc", "sketch_dev.h")            # constants, LDS geometry and helpers of the three sketch units
 
 
 @pytest.fixture(scope="module")
@@ -45,9 +46,9 @@ def test_read_kernel_fits_six_waves_per_simd(sketch_asm):
 
 
 def test_read_kernel_lds_fits_twenty_four_waves_per_cu():
-    # phi_wave_region_u64(w, k, pos = false) of sketch.hip, restated: dynamic LDS per wave of the read kernel
+    # phi_wave_region_u64(w, k, pos = false) of sketch_dev.h, restated: dynamic LDS per wave of the read kernel
     WCH, SWW, SBW = 512, 32, 16
-    src = open(SRC).read()
+    src = open(DEV).read()
     assert re.search(r"#define SWW 32\b", src) and re.search(r"#define SBW 16\b", src) and "#define PHI_WCH 512" in open(os.path.join(ROOT, "phi_amd", "csrc", "phi_kernels.h")).read()
 
     def region_bytes(w, k):
@@ -77,7 +78,7 @@ def pooled_asm(tmp_path_factory):
 
 def test_pooled_read_kernel_fits_six_waves_per_simd(pooled_asm):
     """The pooled instances (batches of 12 Mbases and more: C3, C4, C5s, C5) live at exactly the 80-VGPR line -- the reason
-    the file is compiled a second time with machine LICM off; a spill there is the 35 % the one-chunk kernel once lost."""
+    they have a translation unit of their own, compiled with machine LICM off; a spill there is the 35 % the one-chunk kernel once lost."""
     names = re.findall(r"\.name:\s+(\S*phi_sketch_pool_kernel\S*)", pooled_asm)
     assert names, "no pooled instance in sketch_pooled.hip"
     for name in sorted(set(n for n in names if not n.endswith(".kd"))):
@@ -87,6 +88,16 @@ def test_pooled_read_kernel_fits_six_waves_per_simd(pooled_asm):
         # chunk) in 36 bytes of scratch per lane; the generic instances spill scalars into vector lanes, not into scratch: the state every measurement of rounds 3-4 was taken in (C3 499 Gbases/s);
         # more than that is a change to look at.
         assert m["private_segment_fixed_size"] <= 36, (name, m)
+
+
+def test_only_the_pooled_instances_are_compiled_there(pooled_asm):
+    """sketch_pooled.hip takes its helpers from sketch_dev.h: its code object holds the three pooled instances and no other
+    kernel (a kernel that strayed into it would be compiled without machine LICM, and a second time)"""
+    kernels = re.findall(r"^\s+\.amdhsa_kernel (\S+)", pooled_asm, re.M)
+    assert len(kernels) == 3 and len(set(kernels)) == 3, kernels
+    assert all("phi_sketch_pool_kernel" in k for k in kernels), kernels
+    for inst in ("phi_sketch_pool_kernelILb1ELi31ELi25EE", "phi_sketch_pool_kernelILb1ELi0ELi0EE", "phi_sketch_pool_kernelILb0ELi0ELi0EE"):
+        assert sum(inst in k for k in kernels) == 1, (inst, kernels)
 
 
 def test_sixteen_wave_dense_dp_fits_the_lds(tmp_path):

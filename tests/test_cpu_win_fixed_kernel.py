@@ -45,7 +45,7 @@ def test_fixed_instance_fits_seven_waves_per_simd(fixed_asm):
 
 
 def test_only_the_fixed_kernel_is_compiled_there(fixed_asm):
-    """sketch.hip is included for its helpers alone: no second copy of its kernels (and of their host stubs)"""
+    """the helpers come from sketch_dev.h, which holds no kernel: no second copy of the kernels of sketch.hip (and of their host stubs)"""
     kernels = re.findall(r"^\s+\.amdhsa_kernel (\S+)", fixed_asm, re.M)
     assert len(kernels) == 1 and FIXED in kernels[0], kernels
 

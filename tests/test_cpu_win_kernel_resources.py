@@ -12,6 +12,7 @@ from conftest import ROOT
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 SRC = os.path.join(ROOT, "phi_amd", "csrc", "sketch.hip")
+DEV = os.path.join(ROOT, "phi_amd", "csrc", "sketch_dev.h")            # constants, LDS geometry and helpers of the three sketch units
 INSTANCES = ("phi_sketch_win_kernelILb1ELi31ELi25EE", "phi_sketch_win_kernelILb1ELi0ELi0EE", "phi_sketch_win_kernelILb0ELi0ELi0EE")
 
 
@@ -39,7 +40,7 @@ def test_window_kernel_fits_six_waves_per_simd(sketch_asm, name):
     assert m["vgpr_spill_count"] == 0 and m["private_segment_fixed_size"] == 0, m
 
 
-# sketch.hip restated: phi_wave_region_u64 (base space, items of 16 bits) and phi_sketch_win_reads / phi_win_region_u64
+# sketch_dev.h and sketch.hip restated: phi_wave_region_u64 (base space, items of 16 bits), phi_win_region_u64 / phi_sketch_win_reads
 WCH, SWW, SBW, Q = 512, 32, 16, 8
 
 
@@ -72,9 +73,9 @@ def _win_reads(k, w, L):
 
 
 def test_window_kernel_formulas_match_the_source():
-    src = open(SRC).read()
-    assert re.search(r"#define SWW 32\b", src) and re.search(r"#define SBW 16\b", src) and re.search(r"#define Q 8\b", src)
-    assert "const int kmers = 9 * R * s;" in src and "const int minima = 9 * (64 + 1) + phi_win_items_u64(w, k);" in src
+    dev, src = open(DEV).read(), open(SRC).read()
+    assert re.search(r"#define SWW 32\b", dev) and re.search(r"#define SBW 16\b", dev) and re.search(r"#define Q 8\b", dev)
+    assert "const int kmers = 9 * R * s;" in dev and "const int minima = 9 * (64 + 1) + phi_win_items_u64(w, k);" in dev
     assert "if (R > 928 / L) R = (int)(928 / L);" in src
 
 

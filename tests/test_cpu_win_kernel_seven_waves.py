@@ -12,6 +12,8 @@ from conftest import ROOT
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 SRC = os.path.join(ROOT, "phi_amd", "csrc", "sketch.hip")
+DEV = os.path.join(ROOT, "phi_amd", "csrc", "sketch_dev.h")            # constants, LDS geometry and helpers of the three sketch units
+POOLED = os.path.join(ROOT, "phi_amd", "csrc", "sketch_pooled.hip")
 FLAGSHIP = "phi_sketch_win_kernelILb1ELi31ELi25EE"
 GENERIC = ("phi_sketch_win_kernelILb1ELi0ELi0EE", "phi_sketch_win_kernelILb0ELi0ELi0EE")
 
@@ -60,11 +62,11 @@ def test_generic_instances_fit_seven_waves_per_simd(sketch_asm, name):
 def test_only_the_window_kernel_declares_seven_waves():
     src = open(SRC).read()
     assert re.search(r"__launch_bounds__\(TPB, 7\) phi_sketch_win_kernel\(", src)
-    assert re.search(r"__launch_bounds__\(TPB, 6\) phi_sketch_pool_kernel\(", src)
+    assert re.search(r"__launch_bounds__\(TPB, 6\) phi_sketch_pool_kernel\(", open(POOLED).read())
     assert re.search(r"__launch_bounds__\(TPB, MODE == PHI_MODE_PROBE \? 6 : 1\) phi_sketch_kernel\(", src)
 
 
-# sketch.hip restated (see test_cpu_win_kernel_resources.py for the rest of the geometry)
+# sketch_dev.h and sketch.hip restated (see test_cpu_win_kernel_resources.py for the rest of the geometry)
 WCH, SWW, SBW, Q = 512, 32, 16, 8
 
 
@@ -106,7 +108,7 @@ def _win_reads(k, w, L):
 
 def test_region_formula_matches_the_source():
     src = open(SRC).read()
-    assert re.search(r"static inline int phi_win_region_u64\(int R, int s, int w, int k\) \{ return phi_win_mp_u64\(R, s, w, k\); \}", src)
+    assert re.search(r"static inline int phi_win_region_u64\(int R, int s, int w, int k\) \{ return phi_win_mp_u64\(R, s, w, k\); \}", open(DEV).read())
     assert "while (R > 0 && phi_win_region_u64(R, s, w, k) + SWW + SBW > phi_wave_region_u64(w, k, false)) R--;" in src
     # the staged words and the bitmap alias the start of the wave's region
     assert "uint64_t *s_words = s_mp;" in src and "unsigned long long *s_bad = (unsigned long long *)s_mp;" in src
