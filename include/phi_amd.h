@@ -189,6 +189,60 @@ int phi_panel_origin(phi_ctx *ctx, const int32_t *vtx, int64_t n, int32_t *orig_
 int phi_panel_walks(phi_ctx *ctx, int32_t *orig_walk, int32_t cap, int32_t *n_kept);
 int phi_panel_stats(phi_ctx *ctx, phi_panel_info *out);
 int phi_panel_release(phi_ctx *ctx);
+/* phi_set_graph_panel, further flag: a collected read store (phi_reads_collect_end done) survives the call, so that the same
+ * reads can be scored against the panel's index with phi_reads_collect_score; a ladder plan is dropped and the read state is
+ * reset as ever.  Without the flag the store goes with the graph it was collected under, as before. */
+#define PHI_PANEL_KEEP_READS 2u
+
+/*
+ * THE PANEL CHOSEN FROM THE READS: graphs of more walks than the DP takes (1022).  The reference lists them as future work
+ * and is compared with a tool that answers the question from the reads' k-mers before anything is inferred
+ * (data/vg_haplotypes.py:21-29: `vg haplotypes` samples haplotypes by k-mer counts of the read set); its own panels are drawn
+ * by name (data/chop_graph.sh:46-66).  The calls below stand in for that step: index the full graph without the DP, score the
+ * reads once, count per stretch of the graph and per walk how many of the walk's minimiser occurrences the reads hit, choose
+ * the walks that lead somewhere, and set the panel.  THE RULE OF THE CHOICE IS THIS PROJECT'S OWN: it is not `vg haplotypes`'
+ * (no diploid sampling, no k-mer presence/absence scoring against a haplotype index) and has not been compared with it.
+ *
+ *   phi_scout_graph   (stands in for the index `vg haplotypes` reads, data/vg_haplotypes.py:21-29, and for the full graph of
+ *                     data/chop_graph.sh:46-50)  The arrays of phi_set_graph; up to 65 535 walks.  Builds the index only
+ *                     -- classes of walk entries, class records, walk-minimiser table, read table, hit vectors -- and none of
+ *                     the DP's tables; no host copy of the walk entries is kept.  walk_vtx == NULL: the entries are on the
+ *                     device, left there by phi_walk_text_resolve, phi_vcf_walks_wide or retained by a panel call (or an
+ *                     earlier scout) with the same walk_off.  Afterwards the context is in state SCOUT and the full entries
+ *                     count as retained (PHI_PANEL_RETAIN): phi_set_graph_panel(..., walk_vtx = NULL, ...) with the same
+ *                     walk_off starts from them and keeps them.  On a scout every reads route, phi_reads_collect_*,
+ *                     phi_reset_reads, phi_reads_stats, phi_hits_buffer, phi_index_stats, phi_walk_minimizers and
+ *                     phi_walk_sharing work as on a set graph; phi_solve, phi_kept_anchors, phi_solve_stats,
+ *                     phi_path_sequence, the phi_comm_ / phi_ipc_ / phi_peers_ exchanges and the panel and chop accessors
+ *                     return PHI_ERR_STATE with a message that names the scout.  Any phi_set_graph* call ends the state.
+ *                     More than 65 535 walks: PHI_ERR_UNSUPPORTED; whatever phi_set_graph refuses of the arrays, the topology
+ *                     or the walks is refused the same way, except what only the DP's model forbids (walks that both start
+ *                     and end at interior vertices).
+ *   phi_scout_scores  (data/vg_haplotypes.py:21-29, the k-mer counting)  Vertex v lies in block (int64)topo_rank[v] *
+ *                     n_blocks / n_vtx; n_blocks <= 0: min(65 536, max(1, ceil(n_vtx / 1024))).  S[b * n_walks + h] = the
+ *                     number of minimiser occurrences (hash, pos) of walk h -- exactly the list phi_walk_minimizers(h)
+ *                     returns -- whose hash has its hit flag set in the current read generation and whose base pos (the
+ *                     k-mer's first base) lies in a vertex of block b.  The matrix is zeroed by the call, computed on the
+ *                     device (panel_score.hip) and stays there for phi_scout_choose until the scout state ends (4 bytes a
+ *                     cell, below 8 GB; any phi_set_graph* frees it); scores (host, may be NULL) receives a copy.  More than 65 536 blocks or n_blocks * n_walks >= 2^31: PHI_ERR_INVALID.  Not a scout:
+ *                     PHI_ERR_STATE.
+ *   phi_scout_choose  (data/vg_haplotypes.py:21-29 the sampling, data/chop_graph.sh:51-61 the list of names)  Copies the matrix
+ *                     of the last phi_scout_scores to the host and applies phi_panel_choose (include/phi_host.h has the
+ *                     rule): keep[n_walks], round_of[n_walks] (may be NULL).
+ */
+typedef struct {
+    int32_t n_blocks, n_walks;
+    int64_t n_classes_flagged;        /* classes with a record in another block than their first record's */
+    int64_t n_nonzero;                /* cells of the matrix that are not 0 */
+    double record_gpu_ms, class_gpu_ms, entry_gpu_ms;   /* HIP events on the context's stream */
+    double walk_sum_gpu_ms;           /* with PHI_SCOUT_REF set (profiles): the per-walk minimiser count kernel over the same entries
+                                         in the same call, which reads the same 4 bytes and one gather per entry; else 0 */
+} phi_scout_info;
+int phi_scout_graph(phi_ctx *ctx, int32_t n_vtx, const char *seq_concat, const int64_t *seq_off,
+                    const int64_t *adj_off, const int32_t *adj, int32_t n_walks,
+                    const int64_t *walk_off, const int32_t *walk_vtx, const int32_t *topo_rank);
+int phi_scout_scores(phi_ctx *ctx, int32_t n_blocks, int32_t *scores, phi_scout_info *info);
+int phi_scout_choose(phi_ctx *ctx, const uint8_t *always, int32_t n_want, uint8_t *keep, int32_t *round_of);
 
 /*
  * "Set graph" from a phased multi-sample VCF + reference FASTA (the reference's second input route, vcf2gfa.py:27-64: `vg construct
@@ -226,6 +280,11 @@ int phi_vcf_genotypes(phi_ctx *ctx, const char *text, int64_t n_text, const int6
                       int32_t n_samples, uint16_t *gt, int32_t *ploidy, uint8_t *flagged);
 int phi_vcf_walks(phi_ctx *ctx, const int32_t *unit_first, int64_t n_units, const int32_t *site_backbone, const int32_t *site_allele0,
                   int64_t n_sites, const int32_t *choice, int32_t n_haps, int64_t *walk_off_out);
+/* phi_vcf_walks for every haplotype of a population VCF (the input of data/vg_haplotypes.py:21-29 and of the full graph of
+ * data/chop_graph.sh:46-50): the same call with the limit of phi_scout_graph, 65 535 haplotypes, in the place of the DP's 1022.
+ * The entries are left for phi_scout_graph or phi_set_graph_panel (walk_vtx = NULL). */
+int phi_vcf_walks_wide(phi_ctx *ctx, const int32_t *unit_first, int64_t n_units, const int32_t *site_backbone, const int32_t *site_allele0,
+                       int64_t n_sites, const int32_t *choice, int32_t n_haps, int64_t *walk_off_out);
 int phi_vcf_stats(phi_ctx *ctx, phi_vcf_info *out);
 
 /*
@@ -659,6 +718,12 @@ typedef struct {
 int phi_reads_collect_begin(phi_ctx *ctx, int64_t first_ordinal);
 int phi_reads_collect_end(phi_ctx *ctx, int64_t *n_reads, int64_t *n_bases);
 int phi_reads_collect_release(phi_ctx *ctx);
+/* The same reads twice (the panel chosen from the reads: scored once against the scout's index to choose, once against the
+ * panel's index to infer; it stands in for running the reads through `vg haplotypes`, data/vg_haplotypes.py:21-29, and then
+ * through PHI on the reduced graph, data/chop_graph.sh:46-66): scores the whole collected store in stored order where it
+ * lies -- no ladder plan, no copy, no offsets read when the store is of one read length.  The read state afterwards is that
+ * of a context handed the same reads directly.  PHI_ERR_STATE while collecting, without a store, or without a graph. */
+int phi_reads_collect_score(phi_ctx *ctx);
 int phi_ladder_plan(phi_ctx *ctx, uint64_t seed, const double *fractions, int32_t n_levels, phi_ladder_info *info);
 int phi_ladder_advance(phi_ctx *ctx, int32_t level);
 int phi_ladder_band(phi_ctx *ctx, int32_t band, int64_t *ordinals_out, int64_t cap, int64_t *n,

@@ -182,6 +182,22 @@ void phi_text_stream_close(phi_text_stream *s);
  * Untrusted bytes: nothing outside bytes[0, n) is read, whatever the lengths in it say. */
 int phi_bam_header(const void *bytes, int64_t n, int64_t *records_start, int32_t *n_ref, char *err, int err_cap);
 
+/* The panel chosen from the reads: which walks of a graph of thousands to keep for the DP, from S[n_blocks * n_walks] =
+ * read support per block of the graph and walk (phi_scout_scores, phi_amd.h).  It stands in for what `vg haplotypes` answers
+ * from the reads' k-mers (data/vg_haplotypes.py:21-29) and for the lists of names of data/chop_graph.sh:46-66.  The rule is
+ * this project's own; it is not `vg haplotypes`' and has not been compared with it:
+ *   1. the walks with always[h] != 0 (always may be NULL) are in; more of them than n_want: PHI_HOST_ERR_INVALID, as is an
+ *      n_want below 1 or above min(n_walks, 1022)
+ *   2. in block b the walks are ordered by (-S[b][h], h)
+ *   3. round r = 0, 1, ...: votes[h] = the number of blocks whose r-th walk is h with S[b][h] > 0; the walks with votes that
+ *      are not yet in enter in the order (votes descending, total = sum over b of S[b][h] descending, id ascending) until the
+ *      panel holds n_want walks
+ *   4. a round that brings no votes ends the rounds; the rest is filled by (total descending, id ascending)
+ * keep[n_walks] receives the flags (exactly n_want of them set); round_of[n_walks] (may be NULL): -1 an always walk, r entered
+ * in round r, n_walks entered in the fill, -2 not chosen.  All host threads; the result does not depend on their number. */
+int phi_panel_choose(const int32_t *S, int32_t n_blocks, int32_t n_walks, const uint8_t *always, int32_t n_want, uint8_t *keep,
+                     int32_t *round_of);
+
 /* Record id of the output: basename(gfa) minus extension + "_" + basename(reads), minus the last
  * extension of the whole string.  Returns the length or -1 if cap is too small. */
 int phi_hap_name(const char *gfa_path, const char *reads_path, char *out, int cap);

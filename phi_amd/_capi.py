@@ -36,10 +36,13 @@ SYMBOLS = [
     "phi_vcf_genotypes", "phi_vcf_walks", "phi_vcf_stats",
     "phi_reads_collect_begin", "phi_reads_collect_end", "phi_reads_collect_release", "phi_ladder_plan", "phi_ladder_advance", "phi_ladder_band",
     "phi_set_graph_panel", "phi_panel_origin", "phi_panel_walks", "phi_panel_stats", "phi_panel_release",
+    "phi_scout_graph", "phi_scout_scores", "phi_scout_choose", "phi_reads_collect_score", "phi_vcf_walks_wide",
     "phi_prefix_sums",
     "phi_reads_bam_begin", "phi_add_reads_bam", "phi_add_reads_bam_parked", "phi_reads_bam_end", "phi_reads_bam_last_batch",
 ]
 PHI_PANEL_RETAIN = 1
+PHI_PANEL_KEEP_READS = 2
+PHI_SCOUT_MAX_WALKS = 65535
 PHI_LADDER_MAX_LEVELS = 16
 PHI_INFLATE_NO_FINDER = 1
 PHI_INFLATE_CHUNK_DEFAULT = 64 << 10          # include/phi_amd.h
@@ -65,6 +68,11 @@ class PhiPanelInfo(C.Structure):
                 ("n_edges_in", C.c_int64), ("n_edges_out", C.c_int64), ("n_entries_in", C.c_int64), ("n_entries_out", C.c_int64),
                 ("mark_gpu_ms", C.c_double), ("scan_gpu_ms", C.c_double), ("remap_gpu_ms", C.c_double),
                 ("reduce_host_s", C.c_double), ("kahn_host_s", C.c_double)]
+
+
+class PhiScoutInfo(C.Structure):
+    _fields_ = [("n_blocks", C.c_int32), ("n_walks", C.c_int32), ("n_classes_flagged", C.c_int64), ("n_nonzero", C.c_int64),
+                ("record_gpu_ms", C.c_double), ("class_gpu_ms", C.c_double), ("entry_gpu_ms", C.c_double), ("walk_sum_gpu_ms", C.c_double)]
 
 
 class PhiVcfInfo(C.Structure):
@@ -138,6 +146,11 @@ def load():
     L.phi_panel_walks.argtypes = [vp, vp, i32, C.POINTER(i32)]
     L.phi_panel_stats.argtypes = [vp, C.POINTER(PhiPanelInfo)]
     L.phi_panel_release.argtypes = [vp]
+    L.phi_scout_graph.argtypes = [vp, i32, vp, vp, vp, vp, i32, vp, vp, vp]
+    L.phi_scout_scores.argtypes = [vp, i32, vp, C.POINTER(PhiScoutInfo)]
+    L.phi_scout_choose.argtypes = [vp, vp, i32, vp, vp]
+    L.phi_reads_collect_score.argtypes = [vp]
+    L.phi_vcf_walks_wide.argtypes = [vp, vp, i64, vp, vp, i64, vp, i32, vp]
     L.phi_vcf_genotypes.argtypes = [vp, vp, i64, vp, vp, i64, i32, vp, vp, vp]
     L.phi_vcf_walks.argtypes = [vp, vp, i64, vp, vp, i64, vp, i32, vp]
     L.phi_vcf_stats.argtypes = [vp, C.POINTER(PhiVcfInfo)]

@@ -65,7 +65,7 @@ class Context:
         self._chk(self._L.phi_set_params(self._h, k, w, C.c_float(threshold), recombination, flags))
         self.k, self.w = k, w
 
-    def set_graph(self, seq_concat, seq_off, adj_off, adj, walk_off, walk_vtx, top_rank, chop=None, keep=None, retain=False):
+    def set_graph(self, seq_concat, seq_off, adj_off, adj, walk_off, walk_vtx, top_rank, chop=None, keep=None, retain=False, keep_reads=False):
         """Arrays of phi_set_graph: bytes + int64/int32 numpy arrays.  chop=N: every vertex is first cut into pieces of at
         most N bases (phi_set_graph_chopped: what `hal2vg --chop N` does in the reference's pipeline); returns the chopped
         walks' offsets, and path_vtx, kept_anchors ... then speak of the chopped graph (chop_origin maps back).
@@ -73,7 +73,9 @@ class Context:
         (phi_set_graph_panel, the rule of phi_amd.panel; top_rank is not used: the panel's ranks are made by the library),
         then chopped when chop is given; returns the panel's (chopped) walk offsets, and path_vtx, path_hap ... speak of the
         panel (panel_origin, panel_walks map back).  retain=True keeps the full walk entries on the device: a later call
-        with walk_vtx=None and the same walk_off starts from them (panel_release lets them go)."""
+        with walk_vtx=None and the same walk_off starts from them (panel_release lets them go); after scout_graph the
+        entries are retained without it.  keep_reads=True (with keep=mask): a collected read store survives the call, for
+        collect_score against the panel's index."""
         seq_off = np.ascontiguousarray(seq_off, np.int64)
         adj_off = np.ascontiguousarray(adj_off, np.int64)
         adj = np.ascontiguousarray(adj, np.int32)
@@ -90,11 +92,12 @@ class Context:
             self._chk(self._L.phi_set_graph_panel(self._h, self.n_vtx, _ptr(buf), _ptr(seq_off), _ptr(adj_off), _ptr(adj),
                                                   self.n_walks, _ptr(walk_off), _ptr(walk_vtx), keep.ctypes.data,
                                                   int(chop) if chop is not None else 0,
-                                                  _capi.PHI_PANEL_RETAIN if retain else 0, walk_off_out.ctypes.data))
+                                                  (_capi.PHI_PANEL_RETAIN if retain else 0) | (_capi.PHI_PANEL_KEEP_READS if keep_reads else 0),
+                                                  walk_off_out.ctypes.data))
             self.n_walks = len(walk_off_out) - 1
             return walk_off_out
-        if retain:
-            raise ValueError("retain=True goes with keep=mask")
+        if retain or keep_reads:
+            raise ValueError("retain=True and keep_reads=True go with keep=mask")
         if chop is not None:
             walk_off_out = np.zeros(self.n_walks + 1, np.int64)
             self._chk(self._L.phi_set_graph_chopped(self._h, self.n_vtx, _ptr(buf), _ptr(seq_off), _ptr(adj_off), _ptr(adj),
@@ -105,7 +108,76 @@ class Context:
                                         self.n_walks, _ptr(walk_off), _ptr(walk_vtx), _ptr(top_rank)))
         return None
 
-    def set_graph_vcf(self, vcf_path, fasta_path, max_len=30, keep_samples=None):
+    # ------------------------------------------------------------------ the panel chosen from the reads
+    def scout_graph(self, seq_concat, seq_off, adj_off, adj, walk_off, walk_vtx, top_rank):
+        """The index of a graph of up to 65 535 walks without the DP (phi_scout_graph): the arrays of set_graph; walk_vtx=None
+        takes entries the device holds (walk text resolved there, vcf_graph(wide=True), or retained by a panel or an earlier
+        scout with the same walk_off).  Afterwards the reads routes, collect_*, reads_stats, walk_minimizers ... work as on a
+        set graph, solve() and what follows it raise PhiError (PHI_ERR_STATE); scout_scores, scout_choose and
+        set_graph(..., walk_vtx=None, keep=mask) follow."""
+        seq_off = np.ascontiguousarray(seq_off, np.int64)
+        adj_off = np.ascontiguousarray(adj_off, np.int64)
+        adj = np.ascontiguousarray(adj, np.int32)
+        walk_off = np.ascontiguousarray(walk_off, np.int64)
+        walk_vtx = np.ascontiguousarray(walk_vtx, np.int32) if walk_vtx is not None else None
+        top_rank = np.ascontiguousarray(top_rank, np.int32)
+        buf = np.frombuffer(seq_concat, np.uint8) if not isinstance(seq_concat, np.ndarray) else seq_concat
+        n_vtx, n_walks = len(seq_off) - 1, len(walk_off) - 1
+        self._chk(self._L.phi_scout_graph(self._h, n_vtx, _ptr(buf), _ptr(seq_off), _ptr(adj_off), _ptr(adj), n_walks, _ptr(walk_off),
+                                          _ptr(walk_vtx), _ptr(top_rank)))
+        self.n_vtx, self.n_walks = n_vtx, n_walks
+
+    def scout_scores(self, n_blocks=0, copy=True):
+        """Read support per block of the graph and per walk (phi_scout_scores) from the reads scored so far: (S int32
+        [blocks, walks] -- None with copy=False --, info dict: n_blocks, n_walks, n_classes_flagged, n_nonzero, GPU
+        milliseconds).  n_blocks=0: one block per 1024 vertices."""
+        info = _capi.PhiScoutInfo()
+        if not copy or not hasattr(self, "n_vtx"):              # (no graph was ever set: the library says so)
+            self._chk(self._L.phi_scout_scores(self._h, int(n_blocks), None, C.byref(info)))
+            return None, {n: getattr(info, n) for n, _ in info._fields_}
+        nb = int(n_blocks) if n_blocks > 0 else min(65536, max(1, (self.n_vtx + 1023) // 1024))     # (the default of phi_scout_scores)
+        S = np.zeros((nb, self.n_walks), np.int32)
+        self._chk(self._L.phi_scout_scores(self._h, nb, S.ctypes.data, C.byref(info)))
+        return S, {n: getattr(info, n) for n, _ in info._fields_}
+
+    def scout_choose(self, n_want, always=None):
+        """The rule of phi_amd.panel.choose_panel on the matrix of the last scout_scores (phi_scout_choose): (keep uint8
+        [walks], round_of int32[walks])."""
+        keep, round_of = np.zeros(self.n_walks, np.uint8), np.zeros(self.n_walks, np.int32)
+        if always is not None:
+            always = np.ascontiguousarray(np.asarray(always) != 0, np.uint8)
+            if always.shape != (self.n_walks,):
+                raise ValueError(f"always must hold one flag per walk ({self.n_walks}), not {always.shape}")
+        self._chk(self._L.phi_scout_choose(self._h, always.ctypes.data if always is not None else None, int(n_want), keep.ctypes.data,
+                                           round_of.ctypes.data))
+        return keep, round_of
+
+    def collect_reads(self, reads, text=False):
+        """collect_begin, the reads through add_reads (a list of sequences or (concat, offsets)) or, with text=True, pieces of
+        FASTA / FASTQ text through the text route (which must take all of it), collect_end: (reads, bases) in the store."""
+        self.collect_begin(0)
+        try:
+            if text:
+                self.reads_text_begin()
+                for piece in reads:
+                    if self.add_reads_text(piece):
+                        raise ValueError("collect_reads: the reads text is irregular (parse it on the host and pass sequences)")
+                pending, _ = self.reads_text_end()
+                tail = _parse_reads_tail(pending)
+                if tail:
+                    self.add_reads(tail)
+            else:
+                self.add_reads(reads)
+        finally:
+            out = self.collect_end()
+        return out
+
+    def collect_score(self):
+        """Scores the whole collected store where it lies (phi_reads_collect_score): the read state is then that of a
+        context handed the same reads directly."""
+        self._chk(self._L.phi_reads_collect_score(self._h))
+
+    def set_graph_vcf(self, vcf_path, fasta_path, max_len=30, keep_samples=None, auto_panel=None, reads=None, always=None, n_blocks=0, text=False):
         """ "Set graph" from a phased VCF + reference FASTA (the graph of phi_amd.vcf2gfa, no GFA in between): vcf_graph(), then
         phi_set_graph takes the walk entries from where the device left them.  Returns the host graph description (VcfGraph:
         hap_id2name, the arrays, walk_off, n_other_contig / n_ref_mismatch / warnings()) with .stats = vcf_stats() plus host
@@ -114,8 +186,40 @@ class Context:
         ALL samples' records, only the kept samples' haplotypes are written as walks (the reference is the sample "REF"), and
         the panel step then removes what no kept walk uses.  v.hap_id2name, v.num_walks and v.walk_off then speak of the kept
         walks, v.kept_haps names them among all haplotypes; path_vtx speaks of the panel graph (panel_origin maps back to
-        v's vertices).  The limit of 1022 haplotypes applies to the kept ones."""
+        v's vertices).  The limit of 1022 haplotypes applies to the kept ones.
+        auto_panel=N with reads=...: the panel of N haplotypes is chosen from the reads (phi_amd.panel.auto_panel: every
+        haplotype's walk is written, up to 65 535, the reads are scored against the index of them all, and the N that lead
+        the blocks of the graph are kept; always=[haplotype names] are kept whatever the reads say).  The reads are scored
+        against the panel when the call returns: solve() follows.  v.auto holds what the choice did, the rest as with
+        keep_samples.  A VCF of at most N haplotypes takes the ordinary route and the reads are added."""
         import time
+        if auto_panel is not None:
+            if keep_samples is not None or reads is None:
+                raise ValueError("auto_panel=N goes with reads=... and without keep_samples")
+            from . import panel as _panel
+            v = self.vcf_graph(vcf_path, fasta_path, max_len, wide=True)
+            t4 = time.perf_counter()
+            if v.num_walks <= int(auto_panel):
+                self.set_graph(v.seq_concat, v.seq_off, v.adj_off, v.adj, v.walk_off, None, v.top_order_map)
+                self.collect_reads(reads, text=text)
+                self.collect_score()
+                v.auto = None
+            else:
+                mask = None
+                if always is not None:
+                    missing = [a for a in always if a not in v.hap_id2name]
+                    if missing:
+                        raise ValueError("the VCF holds no haplotype named " + ", ".join(missing))
+                    mask = np.array([n in set(always) for n in v.hap_id2name], np.uint8)
+                A = dict(seq_concat=v.seq_concat, seq_off=v.seq_off, adj_off=v.adj_off, adj=v.adj, walk_off=v.walk_off, walk_vtx=None,
+                         top_rank=v.top_order_map)
+                v.auto = _panel.auto_panel(self, A, reads, int(auto_panel), always=mask, n_blocks=n_blocks, text=text)
+                v.kept_haps = np.flatnonzero(v.auto["keep"]).astype(np.int32)
+                v.hap_id2name = [v.hap_id2name[h] for h in v.kept_haps.tolist()]
+                v.num_walks = len(v.kept_haps)
+                v.walk_off = v.auto["walk_off"]
+            v.stats["set_graph_s"] = time.perf_counter() - t4
+            return v
         v = self.vcf_graph(vcf_path, fasta_path, max_len, keep_samples=keep_samples)
         t4 = time.perf_counter()
         if keep_samples is None:
@@ -125,11 +229,11 @@ class Context:
         v.stats["set_graph_s"] = time.perf_counter() - t4
         return v
 
-    def vcf_graph(self, vcf_path, fasta_path, max_len=30, keep_samples=None):
+    def vcf_graph(self, vcf_path, fasta_path, max_len=30, keep_samples=None, wide=False):
         """The VCF route up to "set graph": the host reads the fixed columns and builds the per-vertex arrays
         (ilp_index.VcfGraph), the device parses the genotype text (phi_vcf_genotypes; records it flags go through the host's
         scalar parser) and writes the walk entries (phi_vcf_walks): walk_entries() returns them, set_graph(..., walk_vtx=None)
-        takes them."""
+        takes them.  wide=True: up to 65 535 haplotypes (phi_vcf_walks_wide), for scout_graph."""
         import time
         from .ilp_index import VcfGraph
         t0 = time.perf_counter()
@@ -156,7 +260,7 @@ class Context:
             v.num_walks = len(v.kept_haps)
         walk_off = np.zeros(v.num_walks + 1, np.int64)
         choice = np.ascontiguousarray(v.choice, np.int32)
-        self._chk(self._L.phi_vcf_walks(self._h, _ptr(v.unit_first), v.n_units, _ptr(v.site_backbone), _ptr(v.site_allele0), v.n_real_sites,
+        self._chk((self._L.phi_vcf_walks_wide if wide else self._L.phi_vcf_walks)(self._h, _ptr(v.unit_first), v.n_units, _ptr(v.site_backbone), _ptr(v.site_allele0), v.n_real_sites,
                                         _ptr(choice), v.num_walks, _ptr(walk_off)))
         t4 = time.perf_counter()
         v.walk_off = walk_off

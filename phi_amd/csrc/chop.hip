@@ -311,6 +311,7 @@ int phi_set_graph_chopped(phi_ctx *c, int32_t n_vtx, const char *seq_concat, con
 int phi_chop_origin(phi_ctx *c, const int32_t *vtx, int64_t n, int32_t *orig_vtx, int32_t *orig_off)
 {
     if (!c || n < 0 || (n > 0 && !vtx)) return PHI_ERR_INVALID;
+    PHICHK(phi_refuse_scout(c, "phi_chop_origin"));
     if (!c->have_graph || !c->chop.on) return phi_fail(c, PHI_ERR_STATE, "phi_chop_origin: the graph was not set with phi_set_graph_chopped");
     const auto &first = c->chop.first;
     for (int64_t i = 0; i < n; i++) {
@@ -326,6 +327,7 @@ int phi_chop_origin(phi_ctx *c, const int32_t *vtx, int64_t n, int32_t *orig_vtx
 int phi_chop_stats(phi_ctx *c, phi_chop_info *out)
 {
     if (!c || !out) return PHI_ERR_INVALID;
+    PHICHK(phi_refuse_scout(c, "phi_chop_stats"));
     if (!c->have_graph || !c->chop.on) return phi_fail(c, PHI_ERR_STATE, "phi_chop_stats: the graph was not set with phi_set_graph_chopped");
     *out = c->chop.info;
     return PHI_OK;

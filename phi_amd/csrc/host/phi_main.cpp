@@ -6,6 +6,7 @@
 //         [--device N | --devices 0,1,..] [--dp-budget RUNS]
 //         [--coverage C0,C1,.. --genome-size N [--seed S]]   (-o 'out.{cov}x.fa': one FASTA per coverage)
 //         [--keep-samples A,B,.. | --drop-samples A,B,.. | --panels N0,N1,.. [--panel-seed S] [--panel-always NAME,..]]
+//         [--panel-auto N [--panel-blocks B] [--panel-always NAME,..]]   (the panel of N walks chosen from the reads)
 //                                                             a panel of the graph's haplotypes, subset inside "set graph"
 //                                                             (data/chop_graph.sh:46-66); -o 'out.{panel}.fa': one FASTA per panel
 //   ./PHI -g <target.gfa> -r a.fq -o a.fa -r b.fq -o b.fa ...      several read sets against ONE graph: the graph is parsed and
@@ -167,7 +168,10 @@ struct Options {
     std::vector<std::string> panel_names;                     // the sizes as written on the command line
     std::vector<int> panel_sizes;
     unsigned long long panel_seed = 0;
-    bool panel() const { return have_keep || have_drop || !panel_sizes.empty(); }
+    // --panel-auto N [--panel-blocks B]: the panel of N walks chosen from the reads, per read set (phi_scout_graph, phi_scout_scores,
+    // phi_scout_choose: in the place of `vg haplotypes`, data/vg_haplotypes.py:21-29, in front of data/chop_graph.sh:46-66)
+    int panel_auto = 0, panel_blocks = 0;
+    bool panel() const { return have_keep || have_drop || !panel_sizes.empty() || panel_auto > 0; }
     int argc = 0;
     char **argv = nullptr;
     bool detached = false;
@@ -556,6 +560,11 @@ struct Driver {
     bool walks_retained = false;                              // --panels: the full entries are on the device (PHI_PANEL_RETAIN)
     phi_panel_info panel_info{};
     long long full_entries = 0;                               // walk entries handed to the panel step
+    // --panel-auto: the graph holds more walks than asked for (else the ordinary route); the scout has been set once (the
+    // context has its parameters and retains the full entries); the walk offsets the scout and the panel are set with
+    bool auto_on = false, auto_scouted = false;
+    std::vector<int64_t> auto_walk_off;
+    bool panel_on() const { return o.panel() && (o.panel_auto <= 0 || auto_on); }
     explicit Driver(const Options &opt) : o(opt), devices(opt.devices), reads_file(opt.reads_files[0]), hap_file(opt.hap_files[0]), reads_kind_now(opt.reads_kinds.empty() ? 0 : opt.reads_kinds[0]) {}
 
     // the one error exit: the message, the reader thread stopped, status 1
@@ -745,6 +754,12 @@ struct Driver {
     {
         if (!o.panel()) return 0;
         const std::vector<std::string> have = samples_in_order();
+        if (o.panel_auto > 0) {
+            if (!o.panel_always.empty() && check_names("--panel-always", o.panel_always, have)) return 1;
+            auto_on = phi_graph_n_walks(g) > o.panel_auto;
+            if (!auto_on) fprintf(stderr, "[M::main] --panel-auto %d: the graph holds %d walks, no more than asked for: the ordinary route, every walk kept\n", o.panel_auto, phi_graph_n_walks(g));
+            return 0;
+        }
         if (o.have_keep) { if (check_names("--keep-samples", o.keep_samples, have)) return 1; mask_of(o.keep_samples, false); return 0; }
         if (o.have_drop) { if (check_names("--drop-samples", o.drop_samples, have)) return 1; mask_of(o.drop_samples, true); return 0; }
         if (check_names("--panel-always", o.panel_always, have)) return 1;
@@ -763,7 +778,7 @@ struct Driver {
         }
         return 0;
     }
-    const char *walk_name(int32_t h) const { return phi_graph_hap_name(g, o.panel() ? kept_walks[(size_t)h] : h); }
+    const char *walk_name(int32_t h) const { return phi_graph_hap_name(g, panel_on() ? kept_walks[(size_t)h] : h); }
     // "Panel: kept 13 of 49 walks (6 of 24 samples + REF): V -> V' vertices, E -> E' edges, X -> X' walk entries"
     void log_panel()
     {
@@ -782,12 +797,91 @@ struct Driver {
                 (int)kept_walks.size(), phi_graph_n_walks(g), in.size(), all.size(), ref_in ? " + REF" : "", (long long)phi_graph_n_vtx(g), (long long)pi.n_vtx_out,
                 (long long)phi_graph_adj_off(g)[phi_graph_n_vtx(g)], (long long)pi.n_edges_out, (long long)full_entries, (long long)pi.n_entries_out);
     }
+    // ---- --panel-auto, stage 1a: the index of EVERY walk without the DP (phi_scout_graph).  The first time from the graph's entries
+    //      (the host's, those resolved on the device, or written there from the VCF's tables); for a further read set from the
+    //      entries the context retained.
+    int scout_index()
+    {
+        const uint32_t flags = (o.is_qclp ? PHI_FLAG_QCLP : 0) | (o.is_mixed ? PHI_FLAG_MIXED : 0);
+        Stage st("phi_scout_graph (index of every walk)");
+        const int32_t n_walks = phi_graph_n_walks(g);
+        int r = auto_scouted ? 0 : phi_set_params(ctx, o.k, o.w, o.threshold, o.recombination, flags);
+        if (!r) r = phi_set_solve_budget(ctx, o.dp_budget >= 0 ? o.dp_budget : 0);
+        if (!r && !auto_scouted) {
+            auto_walk_off.assign((size_t)n_walks + 1, 0);
+            if (vcf) r = phi_vcf_walks_wide(ctx, phi_vcf_unit_first(vcf), phi_vcf_n_units(vcf), phi_vcf_site_backbone(vcf), phi_vcf_site_allele0(vcf),
+                                            phi_vcf_n_real_sites(vcf), phi_vcf_choice(vcf), phi_vcf_n_kept_haps(vcf), auto_walk_off.data());
+            else memcpy(auto_walk_off.data(), phi_graph_walk_off(g), auto_walk_off.size() * 8);
+        }
+        if (!r)
+            r = phi_scout_graph(ctx, phi_graph_n_vtx(g), phi_graph_seq_concat(g), phi_graph_seq_off(g), phi_graph_adj_off(g), phi_graph_adj(g), n_walks,
+                                auto_walk_off.data(), auto_scouted || vcf ? nullptr : phi_graph_walk_vtx(g), phi_graph_topo_rank(g));
+        if (r == PHI_ERR_WALK) fprintf(stderr, "Error: %s\n", phi_last_error(ctx));
+        if (r) { failed = true; return fail_on(ctx, "scout graph", r); }
+        auto_scouted = true;
+        full_entries = auto_walk_off[(size_t)n_walks];
+        return 0;
+    }
+    // ---- --panel-auto, one read set: collected and scored against the scout, the panel chosen and set, the same reads scored
+    //      against the panel's index, then solve and report as ever
+    int run_auto_job()
+    {
+        int rc;
+        const int32_t n_walks = phi_graph_n_walks(g);
+        if ((rc = phi_reads_collect_begin(ctx, 0))) return fail_on(ctx, "collect", rc);
+        if (Stage st("reads: text -> device, records (collected)"); run_on_all("reads", [&](int, phi_ctx *cx) -> int { return feed_reads(cx); })) return 1;
+        if (feed.reader.get() != PHI_HOST_OK) return fail("[E::main] %s\n", feed.err);
+        if ((rc = phi_reads_collect_end(ctx, nullptr, nullptr))) return fail_on(ctx, "collect", rc);
+        if (Stage st("reads scored against every walk"); (rc = phi_reads_collect_score(ctx))) return fail_on(ctx, "reads", rc);
+        phi_scout_info si;
+        std::vector<uint8_t> always((size_t)n_walks, 0);
+        for (int32_t h = 0; h < n_walks; h++)
+            always[(size_t)h] = std::find(o.panel_always.begin(), o.panel_always.end(), sample_of(phi_graph_hap_name(g, h))) != o.panel_always.end();
+        std::vector<int32_t> round_of((size_t)n_walks, -2);
+        keep.assign((size_t)n_walks, 0);
+        {
+            Stage st("panel from the reads (scores, choice)");
+            if ((rc = phi_scout_scores(ctx, o.panel_blocks, nullptr, &si))) return fail_on(ctx, "panel scores", rc);
+            if ((rc = phi_scout_choose(ctx, always.data(), o.panel_auto, keep.data(), round_of.data()))) return fail_on(ctx, "panel choice", rc);
+        }
+        int rounds = 0;
+        kept_walks.clear();
+        for (int32_t h = 0; h < n_walks; h++) {
+            if (keep[(size_t)h]) kept_walks.push_back(h);
+            if (round_of[(size_t)h] >= 0 && round_of[(size_t)h] < n_walks) rounds = std::max(rounds, round_of[(size_t)h] + 1);
+        }
+        stamp("main");
+        fprintf(stderr, "Panel (from the reads): kept %d of %d walks in %d rounds over %d blocks:", (int)kept_walks.size(), n_walks, rounds, si.n_blocks);
+        for (size_t i = 0; i < kept_walks.size(); i++) fprintf(stderr, "%s%s", i ? "," : " ", phi_graph_hap_name(g, kept_walks[i]));
+        fprintf(stderr, "\n");
+        {
+            Stage st("phi_set_graph_panel (index of the chosen walks)");
+            rc = phi_set_graph_panel(ctx, phi_graph_n_vtx(g), phi_graph_seq_concat(g), phi_graph_seq_off(g), phi_graph_adj_off(g), phi_graph_adj(g), n_walks,
+                                     auto_walk_off.data(), nullptr, keep.data(), o.chop, PHI_PANEL_RETAIN | PHI_PANEL_KEEP_READS, nullptr);
+            if (rc == PHI_ERR_WALK) fprintf(stderr, "Error: %s\n", phi_last_error(ctx));
+            if (rc) return fail_on(ctx, "graph", rc);
+        }
+        walks_retained = true;
+        if ((rc = phi_panel_stats(ctx, &panel_info))) return fail_on(ctx, "panel", rc);
+        log_panel();
+        phi_chop_info ci;
+        if (o.chop && !phi_chop_stats(ctx, &ci)) {
+            stamp("main");
+            fprintf(stderr, "Graph chopped to %d bases: %lld -> %lld vertices, %lld -> %lld walk entries\n", ci.max_len, (long long)ci.n_vtx_in,
+                    (long long)ci.n_vtx_out, (long long)ci.n_entries_in, (long long)ci.n_entries_out);
+        }
+        if (Stage st("reads scored against the panel"); (rc = phi_reads_collect_score(ctx))) return fail_on(ctx, "reads", rc);
+        const int status = solve_and_report();
+        if (status == 1) return 1;
+        if ((rc = phi_reads_collect_release(ctx))) return fail_on(ctx, "collect release", rc);
+        return status;
+    }
     // ---- stage 1a: walks (ILP_index.cpp:556-611) on every GPU, while the reads are still being read
     int build_index()
     {
         const uint32_t flags = (o.is_qclp ? PHI_FLAG_QCLP : 0) | (o.is_mixed ? PHI_FLAG_MIXED : 0);
         Stage st("phi_set_graph (index build)");
-        if (o.panel()) {
+        if (panel_on()) {
             kept_walks.clear();
             for (int32_t h = 0; h < phi_graph_n_walks(g); h++) if (keep[(size_t)h]) kept_walks.push_back(h);
             if (kept_walks.empty()) return fail("[E::main] the panel keeps no walk\n");
@@ -798,7 +892,7 @@ struct Driver {
             // the reference's model.optimize() has no limit (ILP_index.cpp:1412-1418): none here unless --dp-budget asks for one
             if (!r) r = phi_set_solve_budget(cx, o.dp_budget >= 0 ? o.dp_budget : 0);
             std::vector<int64_t> vcf_walk_off;
-            if (!r && vcf && o.panel()) {
+            if (!r && vcf && panel_on()) {
                 // the graph is built from ALL samples' records; only the kept haplotypes' choice columns become walks, and the
                 // panel step, with every walk kept, removes what nobody uses
                 const int64_t n_sites = phi_vcf_n_real_sites(vcf);
@@ -814,7 +908,7 @@ struct Driver {
                     r = phi_set_graph_panel(cx, phi_graph_n_vtx(g), phi_graph_seq_concat(g), phi_graph_seq_off(g), phi_graph_adj_off(g), phi_graph_adj(g),
                                             n_kept, vcf_walk_off.data(), nullptr, all.data(), 0, 0, nullptr);
                 if (!r && cx == ctx) full_entries = vcf_walk_off[(size_t)n_kept];
-            } else if (!r && o.panel()) {
+            } else if (!r && panel_on()) {
                 // --panels: the full entries stay on the device behind the first panel, and every later one starts from them
                 const uint32_t pf = panels.empty() ? 0u : PHI_PANEL_RETAIN;
                 r = phi_set_graph_panel(cx, phi_graph_n_vtx(g), phi_graph_seq_concat(g), phi_graph_seq_off(g), phi_graph_adj_off(g), phi_graph_adj(g),
@@ -837,7 +931,7 @@ struct Driver {
             if (r == PHI_ERR_WALK && n_dev == 1) fprintf(stderr, "Error: %s\n", phi_last_error(cx));
             return r;
         });
-        if (!rc && o.panel()) {
+        if (!rc && panel_on()) {
             if (!panels.empty()) walks_retained = true;
             int prc = phi_panel_stats(ctx, &panel_info);
             if (prc) return fail_on(ctx, "panel", prc);
@@ -965,7 +1059,7 @@ struct Driver {
     int report(const phi_result &res)
     {
         const double t_report = realtime();
-        const int32_t n_walks = o.panel() ? (int32_t)kept_walks.size() : phi_graph_n_walks(g);      // (the names printed are the kept walks' own)
+        const int32_t n_walks = panel_on() ? (int32_t)kept_walks.size() : phi_graph_n_walks(g);      // (the names printed are the kept walks' own)
         int rc;
         fprintf(stderr, "Number of Minimizers\n");
         for (int32_t h = 0; h < n_walks; h++) fprintf(stderr, "%s : %d\n", walk_name(h), (int)res.n_minimizers[h]);
@@ -1033,13 +1127,13 @@ struct Driver {
         }
         // a panel: the (unchopped) vertices are the panel graph's; g's own through phi_panel_origin
         std::vector<int32_t> orig;
-        if (o.panel()) {
+        if (panel_on()) {
             orig.resize((size_t)res.n_path);
             const int rc = phi_panel_origin(ctx, o.chop ? seg.data() : res.path_vtx, res.n_path, orig.data());
             if (rc) { fprintf(stderr, "\n[E::main] recombination report: %s: %s\n", phi_strerror(rc), phi_last_error(ctx)); return; }
         }
         for (int64_t i = 0; i < res.n_path; i++) {
-            const int32_t v = o.panel() ? orig[(size_t)i] : o.chop ? seg[(size_t)i] : res.path_vtx[i];
+            const int32_t v = panel_on() ? orig[(size_t)i] : o.chop ? seg[(size_t)i] : res.path_vtx[i];
             const int64_t len = o.chop ? std::max<int64_t>(0, std::min<int64_t>(o.chop, so[v + 1] - so[v] - at[(size_t)i])) : so[v + 1] - so[v];
             str_id += len;                                    // (the reference adds the vertex length before testing the label: :1515-1523)
             if (i > 0 && res.path_hap[i] != prev_hap) {
@@ -1083,6 +1177,10 @@ struct Driver {
             loaded();
         }
         if (!hap_pattern.empty()) hap_file = hap_pattern;
+        if (auto_on) {                                        // (--panel-auto: the scout again for a further read set, from the retained entries)
+            if ((job > 0 || !first_of_run) && scout_index()) return 1;
+            return run_auto_job();
+        }
         const bool ladder = !o.cov.empty();                  // (one GPU: main refuses --coverage with --devices of several)
         int rc;
         if (ladder && (rc = phi_reads_collect_begin(ctx, 0))) return fail_on(ctx, "collect", rc);
@@ -1130,8 +1228,8 @@ struct Driver {
             if ((rc = phi_reads_stats(cx, &nr, nullptr, nullptr, nullptr))) return fail_on(cx, "reads", rc);
             total_reads += nr;
         }
-        stamp("ILP_function"); fprintf(stderr, "Graph has %d vertices, %d walks and read has %d reads\n", o.panel() ? (int)panel_info.n_vtx_out : phi_graph_n_vtx(g),
-                                      o.panel() ? (int)kept_walks.size() : phi_graph_n_walks(g), (int)total_reads);
+        stamp("ILP_function"); fprintf(stderr, "Graph has %d vertices, %d walks and read has %d reads\n", panel_on() ? (int)panel_info.n_vtx_out : phi_graph_n_vtx(g),
+                                      panel_on() ? (int)kept_walks.size() : phi_graph_n_walks(g), (int)total_reads);
         phi_result res;
         if (Stage st("phi_solve (filter, exact solve, decode)"); (rc = phi_solve(ctx, &res))) return fail_on(ctx, "solve", rc);
         if (report(res)) return 1;
@@ -1201,7 +1299,7 @@ static int run(const Options &o)
     int status = 0;
     for (size_t pj = 0; pj < n_panels; pj++) {
         if (!d.panels.empty()) d.mask_of(d.panels[pj], false);
-        if (d.build_index()) return 1;
+        if (d.auto_on ? d.scout_index() : d.build_index()) return 1;
         d.feed.mark(d.feed.index_built);                     // (the reader thread stops parking chunks: they are taken as they come now)
         if (pj == 0 && d.setup_exchange()) return 1;
         // ---- one job per read set (-r a -o a.fa -r b -o b.fa ...): the graph, its index and the communicator are made once
@@ -1228,7 +1326,8 @@ int main(int argc, char *argv[])
                                            {"devices", required_argument, 0, 303}, {"shard-min-bases", required_argument, 0, 304}, {"chop", required_argument, 0, 305}, {"vcf", required_argument, 0, 306}, {"ref", required_argument, 0, 307},
                                            {"coverage", required_argument, 0, 308}, {"genome-size", required_argument, 0, 309}, {"seed", required_argument, 0, 310},
                                            {"keep-samples", required_argument, 0, 311}, {"drop-samples", required_argument, 0, 312}, {"panels", required_argument, 0, 313},
-                                           {"panel-seed", required_argument, 0, 314}, {"panel-always", required_argument, 0, 315}, {0, 0, 0, 0}};
+                                           {"panel-seed", required_argument, 0, 314}, {"panel-always", required_argument, 0, 315},
+                                           {"panel-auto", required_argument, 0, 316}, {"panel-blocks", required_argument, 0, 317}, {0, 0, 0, 0}};
     int c;
     std::string gfa_arg, vcf_arg;
     // main.cpp:38 declares -h with an argument; a bare -h falls into the usage branch either way
@@ -1288,6 +1387,8 @@ int main(int argc, char *argv[])
             if (o.panel_sizes.empty() || o.panel_sizes.size() > 16) { fprintf(stderr, "[E::main] --panels takes 1 to 16 sizes\n"); return 1; }
         }
         else if (c == 314) o.panel_seed = strtoull(optarg, nullptr, 10);
+        else if (c == 316) { o.panel_auto = atoi(optarg); if (o.panel_auto < 1 || o.panel_auto > 1022) { fprintf(stderr, "[E::main] --panel-auto takes the number of walks to keep, 1 to 1022\n"); return 1; } }
+        else if (c == 317) { o.panel_blocks = atoi(optarg); if (o.panel_blocks < 1 || o.panel_blocks > 65536) { fprintf(stderr, "[E::main] --panel-blocks takes a number of blocks, 1 to 65536\n"); return 1; } }
         else if (c == 304) o.shard_min_bases = std::max<long long>(1, atoll(optarg));
         else if (c == 303) {                                   // --devices 0,1,2,...: shard the reads over these GPUs
             o.devices.clear();
@@ -1325,7 +1426,12 @@ int main(int argc, char *argv[])
                 if (h.find("{cov}") == std::string::npos) { fprintf(stderr, "[E::main] --coverage with several coverages: -o must contain {cov} (got %s), e.g. -o 'out.{cov}x.fa'\n", h.c_str()); return 1; }
     } else if (o.genome_size != 0.0) { fprintf(stderr, "[E::main] --genome-size goes with --coverage\n"); return 1; }
     if ((int)o.have_keep + (int)o.have_drop + (int)!o.panel_sizes.empty() > 1) { fprintf(stderr, "[E::main] --keep-samples, --drop-samples and --panels exclude each other\n"); return 1; }
-    if (o.panel_sizes.empty() && !o.panel_always.empty()) { fprintf(stderr, "[E::main] --panel-always goes with --panels\n"); return 1; }
+    if (o.panel_auto > 0) {
+        if (o.have_keep || o.have_drop || !o.panel_sizes.empty()) { fprintf(stderr, "[E::main] --panel-auto chooses the panel from the reads: not together with --keep-samples, --drop-samples or --panels\n"); return 1; }
+        if (!o.cov.empty()) { fprintf(stderr, "[E::main] --panel-auto is not supported together with --coverage\n"); return 1; }
+        if (o.devices.size() > 1) { fprintf(stderr, "[E::main] --panel-auto runs on one GPU: not together with --devices of several\n"); return 1; }
+    } else if (o.panel_blocks) { fprintf(stderr, "[E::main] --panel-blocks goes with --panel-auto\n"); return 1; }
+    if (o.panel_sizes.empty() && o.panel_auto <= 0 && !o.panel_always.empty()) { fprintf(stderr, "[E::main] --panel-always goes with --panels or --panel-auto\n"); return 1; }
     if (!o.panel_sizes.empty()) {
         if (!o.cov.empty()) { fprintf(stderr, "[E::main] --panels is not supported together with --coverage\n"); return 1; }
         if (o.devices.size() > 1) { fprintf(stderr, "[E::main] --panels runs on one GPU: not together with --devices of several\n"); return 1; }

@@ -265,6 +265,25 @@ void phi_ladder_drop(phi_ctx *c)
     S.n_reads = S.n_bases = 0; S.one_len = -1;
 }
 
+// PHI_PANEL_KEEP_READS (panel.hip): the finished store leaves the context -- without its plan, whose bands belong to nothing
+// after the call -- so that the phi_ladder_drop of the set-graph stages finds nothing, and comes back once the panel is set
+void phi_ladder_detach(phi_ctx *c, phi_ctx::PhiLadder &out)
+{
+    auto &S = c->ladder;
+    out = phi_ctx::PhiLadder{};
+    if (!S.have_store || S.collecting) return;
+    (void)hipStreamSynchronize(c->stream);
+    ladder_drop_plan(c);
+    std::swap(out, S);
+}
+
+void phi_ladder_attach(phi_ctx *c, phi_ctx::PhiLadder &in)
+{
+    if (!in.have_store) return;
+    phi_ladder_drop(c);
+    std::swap(c->ladder, in);
+}
+
 extern "C" {
 
 int phi_reads_collect_begin(phi_ctx *c, int64_t first_ordinal)
@@ -301,6 +320,20 @@ int phi_reads_collect_release(phi_ctx *c)
     HIPCHK(hipSetDevice(c->device));
     phi_ladder_drop(c);
     return PHI_OK;
+}
+
+int phi_reads_collect_score(phi_ctx *c)
+{
+    if (!c) return PHI_ERR_INVALID;
+    auto &S = c->ladder;
+    if (S.collecting) return phi_fail(c, PHI_ERR_STATE, "phi_reads_collect_score while collecting: phi_reads_collect_end first");
+    if (!S.have_store) return phi_fail(c, PHI_ERR_STATE, "phi_reads_collect_score without a collected read set");
+    if (!c->have_graph) return phi_fail(c, PHI_ERR_STATE, "phi_reads_collect_score before phi_set_graph");
+    HIPCHK(hipSetDevice(c->device));
+    if (S.n_reads == 0) return PHI_OK;
+    // the store as one resident batch, where it lies; one read length: no offsets, as phi_ladder_advance hands its bands over
+    const void *d_off = S.one_len > 0 && S.one_len <= 0x7FFFFFFF ? nullptr : S.d_off.p;
+    return phi_score_resident_batch(c, S.d_bases.p, d_off, S.n_reads, S.n_bases);
 }
 
 int phi_ladder_plan(phi_ctx *c, uint64_t seed, const double *fractions, int32_t n_levels, phi_ladder_info *info)

@@ -193,7 +193,7 @@ int phi_set_graph_panel(phi_ctx *c, int32_t n_vtx, const char *seq_concat, const
     if (n_vtx <= 0 || n_walks <= 0 || !seq_concat || !seq_off || !adj_off || !walk_off || !keep)
         return phi_fail(c, PHI_ERR_INVALID, "phi_set_graph_panel: null pointer or empty graph");
     if (adj_off[n_vtx] > 0 && !adj) return phi_fail(c, PHI_ERR_INVALID, "phi_set_graph_panel: adj is null");
-    if (flags & ~(uint32_t)PHI_PANEL_RETAIN) return phi_fail(c, PHI_ERR_INVALID, "phi_set_graph_panel: unknown flags %u", flags);
+    if (flags & ~(uint32_t)(PHI_PANEL_RETAIN | PHI_PANEL_KEEP_READS)) return phi_fail(c, PHI_ERR_INVALID, "phi_set_graph_panel: unknown flags %u", flags);
     HIPCHK(hipSetDevice(c->device));
     if (c->ipc) return phi_fail(c, PHI_ERR_STATE, "phi_set_graph on a context in a group of processes: phi_ipc_destroy first (the peers have this context's hit vectors mapped)");
     PhiStageTimer tm("set_graph_panel");
@@ -201,9 +201,11 @@ int phi_set_graph_panel(phi_ctx *c, int32_t n_vtx, const char *seq_concat, const
     const int64_t n_edges = adj_off[n_vtx], n_in = walk_off[n_walks];
     auto &P = c->panel;
     // ---- where the full entries are: the caller's, freshly resolved on this context, or retained by an earlier call
-    enum { FROM_HOST, FROM_RESOLVED, FROM_RETAINED } from = FROM_HOST;
+    enum { FROM_HOST, FROM_RESOLVED, FROM_RETAINED, FROM_SCOUT } from = FROM_HOST;
     if (!walk_vtx) {
-        if (c->walks_on_device && c->walks_on_device_n == n_in && (int32_t)(c->wtext.ends.size() / 2) == n_walks) from = FROM_RESOLVED;
+        const bool same_off = P.full_off.size() == (size_t)n_walks + 1 && std::equal(P.full_off.begin(), P.full_off.end(), walk_off);
+        if (c->scout.on && same_off) from = FROM_SCOUT;           // (phi_scout_graph: the full entries are the scout's walks)
+        else if (c->walks_on_device && c->walks_on_device_n == n_in && (int32_t)(c->wtext.ends.size() / 2) == n_walks) from = FROM_RESOLVED;
         else if (P.d_full.p && P.full_off.size() == (size_t)n_walks + 1 && std::equal(P.full_off.begin(), P.full_off.end(), walk_off)) from = FROM_RETAINED;
         else return phi_fail(c, PHI_ERR_STATE, "phi_set_graph_panel without walk_vtx: these walks are neither freshly resolved on this context nor retained by an earlier panel");
     }
@@ -216,8 +218,23 @@ int phi_set_graph_panel(phi_ctx *c, int32_t n_vtx, const char *seq_concat, const
     c->have_graph = false;
     c->chop.on = false;
     P.on = false;
+    phi_scout_end(c);                                          // (the choice has been made: the score matrix goes before the panel's index is built)
     c->solved = false;
+    // PHI_PANEL_KEEP_READS: a finished store steps aside while the graph is set anew (every stage below drops what it finds) and
+    // comes back when the panel stands; on failure it goes, as the graph it was collected under has
+    struct KeptReads {
+        phi_ctx *c;
+        phi_ctx::PhiLadder store;
+        ~KeptReads() { for (DevBuf *b : {&store.d_bases, &store.d_off}) phi_dev_free(*b); }
+    } kept_reads{c, {}};
+    if (flags & PHI_PANEL_KEEP_READS) phi_ladder_detach(c, kept_reads.store);
     phi_ladder_drop(c);
+    if (from == FROM_SCOUT) {                                  // the scout's entries count as retained, and stay so
+        phi_dev_free(P.d_full);
+        std::swap(P.d_full, c->d_walk_vtx);
+        from = FROM_RETAINED;
+        flags |= PHI_PANEL_RETAIN;
+    }
     std::vector<int64_t> kin((size_t)n_kept), kout((size_t)n_kept + 1, 0);
     for (int32_t k = 0; k < n_kept; k++) {
         kin[(size_t)k] = walk_off[kept[(size_t)k]];
@@ -384,12 +401,14 @@ int phi_set_graph_panel(phi_ctx *c, int32_t n_vtx, const char *seq_concat, const
     P.kept.swap(kept);
     P.info = info;
     P.on = true;
+    phi_ladder_attach(c, kept_reads.store);
     return PHI_OK;
 }
 
 int phi_panel_origin(phi_ctx *c, const int32_t *vtx, int64_t n, int32_t *orig_vtx)
 {
     if (!c || n < 0 || (n > 0 && (!vtx || !orig_vtx))) return PHI_ERR_INVALID;
+    PHICHK(phi_refuse_scout(c, "phi_panel_origin"));
     if (!c->have_graph || !c->panel.on) return phi_fail(c, PHI_ERR_STATE, "phi_panel_origin: the graph was not set with phi_set_graph_panel");
     const auto &origin = c->panel.origin;
     for (int64_t i = 0; i < n; i++) {
@@ -403,6 +422,7 @@ int phi_panel_origin(phi_ctx *c, const int32_t *vtx, int64_t n, int32_t *orig_vt
 int phi_panel_walks(phi_ctx *c, int32_t *orig_walk, int32_t cap, int32_t *n_kept)
 {
     if (!c || !n_kept) return PHI_ERR_INVALID;
+    PHICHK(phi_refuse_scout(c, "phi_panel_walks"));
     if (!c->have_graph || !c->panel.on) return phi_fail(c, PHI_ERR_STATE, "phi_panel_walks: the graph was not set with phi_set_graph_panel");
     const auto &kept = c->panel.kept;
     *n_kept = (int32_t)kept.size();
@@ -413,6 +433,7 @@ int phi_panel_walks(phi_ctx *c, int32_t *orig_walk, int32_t cap, int32_t *n_kept
 int phi_panel_stats(phi_ctx *c, phi_panel_info *out)
 {
     if (!c || !out) return PHI_ERR_INVALID;
+    PHICHK(phi_refuse_scout(c, "phi_panel_stats"));
     if (!c->have_graph || !c->panel.on) return phi_fail(c, PHI_ERR_STATE, "phi_panel_stats: the graph was not set with phi_set_graph_panel");
     *out = c->panel.info;
     return PHI_OK;

@@ -99,6 +99,7 @@ int phi_comm_init(phi_ctx *c, const void *id, int32_t rank, int32_t n_ranks)
 {
     if (!c || !id || n_ranks < 1 || rank < 0 || rank >= n_ranks) return PHI_ERR_INVALID;
     if (c->comm) return phi_fail(c, PHI_ERR_STATE, "phi_comm_init: this context already has a communicator");
+    PHICHK(phi_refuse_scout(c, "phi_comm_init"));
     std::string why;
     const RcclApi *api = rccl_api(&why);
     if (!api) return phi_fail(c, PHI_ERR_DEVICE, "%s", why.c_str());
@@ -142,6 +143,7 @@ int phi_comm_allreduce_hits(phi_ctx *c)
 {
     if (!c) return PHI_ERR_INVALID;
     if (!c->have_graph) return phi_fail(c, PHI_ERR_STATE, "phi_comm_allreduce_hits before phi_set_graph");
+    PHICHK(phi_refuse_scout(c, "phi_comm_allreduce_hits / phi_comm_exchange"));
     PhiComm *pc = c->comm;
     if (!pc) return phi_fail(c, PHI_ERR_STATE, "no communicator: call phi_comm_init first");
     const RcclApi *api = pc->api;
@@ -263,6 +265,7 @@ int phi_peers_join(phi_ctx *c, void *group, int32_t rank)
     if (!c || !g || rank < 0 || rank >= g->n) return PHI_ERR_INVALID;
     int rc = PHI_OK;
     if (!c->have_graph) rc = phi_fail(c, PHI_ERR_STATE, "phi_peers_join before phi_set_graph");
+    if (!rc) rc = phi_refuse_scout(c, "phi_peers_join");
     if (!rc && hipSetDevice(c->device) != hipSuccess) rc = PHI_ERR_DEVICE;
     if (!rc) {
         g->ctx[(size_t)rank] = c;

@@ -119,6 +119,15 @@ struct phi_ctx {
         DevBuf d_full;                                // PHI_PANEL_RETAIN: the full graph's walk entries, for the next panel
         std::vector<int64_t> full_off;                // their walk offsets (empty: nothing retained)
     } panel;
+    // ---- the scout (phi_scout_graph, set_graph.hip): the index of a graph of up to 65 535 walks without the DP's tables.  have_graph
+    //      is set, so the reads routes and the index's accessors work; what needs the DP asks phi_refuse_scout first.  The
+    //      full entries are d_walk_vtx and count as retained: panel.full_off names them, phi_set_graph_panel moves them to
+    //      panel.d_full
+    struct PhiScout {
+        bool on = false;
+        DevBuf d_scores;                              // [n_blocks * n_walks] read support per block and walk (panel_score.hip)
+        int32_t n_blocks = 0;                         // 0: no phi_scout_scores yet on this scout
+    } scout;
     // ---- "set graph" from a phased VCF (phi_vcf_genotypes, phi_vcf_walks): what the last calls did
     struct PhiVcf {
         bool have = false;
@@ -354,6 +363,12 @@ int phi_fail(phi_ctx *c, int code, const char *fmt, ...);
 int phi_dev_ensure(phi_ctx *c, DevBuf &b, size_t bytes);
 int phi_dev_grow_keep(phi_ctx *c, DevBuf &b, size_t bytes, size_t keep);   // grows and KEEPS the first `keep` bytes
 void phi_dev_free(DevBuf &b);                          // to the pool of large buffers or back to the driver (waits for the device)
+// the scout state ends (any phi_set_graph*, a new scout): its score matrix, up to 8 GB, goes with it
+static inline void phi_scout_end(phi_ctx *c)
+{
+    c->scout.on = false; c->scout.n_blocks = 0;
+    phi_dev_free(c->scout.d_scores);
+}
 // temporaries of one call: let go, through phi_dev_free, when the scope ends
 struct PhiDevGuard {
     std::vector<DevBuf *> b;
@@ -400,11 +415,19 @@ int phi_text_park_piece_dev(phi_text_park *p, int32_t index, int device, const v
 // ladder.hip
 int phi_ladder_collect(phi_ctx *c, const void *d_bases, const void *d_read_off, int64_t n_reads, int64_t n_bases);   // the hook of phi_add_reads_device_impl
 void phi_ladder_drop(phi_ctx *c);                      // store and plan let go (a new graph, the context's end)
+// PHI_PANEL_KEEP_READS: a collected store taken out of the context (its plan dropped) before the graph is set anew, and put back
+void phi_ladder_detach(phi_ctx *c, phi_ctx::PhiLadder &out);
+void phi_ladder_attach(phi_ctx *c, phi_ctx::PhiLadder &in);
 // a batch whose data stays where it is: scored, waited for, and replayed if the overflow list of novel hashes ran full
 int phi_score_resident_batch(phi_ctx *c, const void *d_bases, const void *d_read_off, int64_t n_reads, int64_t n_bases);
 void phi_pool_flush(int device);                    // the pool of large device buffers let go (phi_abi.hip) back to the driver
 int phi_hip_check(phi_ctx *c, hipError_t e, const char *what);
 int phi_sync_check(phi_ctx *c);
+// PHI_ERR_STATE naming the scout when the context holds one (phi_scout_graph: an index without the DP), else PHI_OK
+static inline int phi_refuse_scout(phi_ctx *c, const char *what)
+{
+    return c->scout.on ? phi_fail(c, PHI_ERR_STATE, "%s on a scout graph (phi_scout_graph builds the index without the DP: phi_set_graph_panel sets the chosen panel)", what) : PHI_OK;
+}
 // pinned host buffer of at least `bytes` (contents are not kept)
 int phi_pin_ensure(phi_ctx *c, size_t bytes);
 int phi_host_anchors(phi_ctx *c);                      // the host copy of the kept anchors, fetched if it is not there

@@ -289,6 +289,7 @@ int phi_ipc_init(phi_ctx *c, const void *id, int32_t rank, int32_t n_ranks)
 {
     if (!c || !id || n_ranks < 1 || n_ranks > PHI_IPC_MAX || rank < 0 || rank >= n_ranks) return PHI_ERR_INVALID;
     if (!c->have_graph) return phi_fail(c, PHI_ERR_STATE, "phi_ipc_init before phi_set_graph");
+    PHICHK(phi_refuse_scout(c, "phi_ipc_init"));
     if (c->ipc) return phi_fail(c, PHI_ERR_STATE, "phi_ipc_init: this context already belongs to a group");
     HIPCHK(hipSetDevice(c->device));
     char name[PHI_COMM_ID_BYTES + 1];

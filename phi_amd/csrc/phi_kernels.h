@@ -247,6 +247,7 @@ void phi_launch_entry_csr(hipStream_t st, const phi_ent_t *a_e1, int64_t n_a, in
 // dp.hip
 #define PHI_DP_CHUNK 128        // steps staged through LDS at a time
 #define PHI_DP_RING 2048        // steps whose leaving states are kept in LDS
+#define PHI_SCOUT_MAX_WALKS 65535   // phi_scout_graph: the index without the DP (a walk id fits 16 bits wherever a scout's tables hold one)
 #define PHI_DP_MAX_WALKS 1022       // one walk per lane of sixteen waves; a walk id + 1 has 10 bits in the packed tops
 
 struct PhiDpArgs {

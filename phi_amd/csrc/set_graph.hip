@@ -219,6 +219,7 @@ int set_graph_check_args(phi_ctx *c, int32_t n_vtx, const char *seq_concat, cons
     c->have_graph = false;
     c->chop.on = false;
     c->panel.on = false;
+    phi_scout_end(c);
     c->solved = false;
     phi_ladder_drop(c);                                        // (a collected read set and its bands belong to the graph they were collected under)
     return PHI_OK;
@@ -694,4 +695,73 @@ extern "C" int phi_set_graph(phi_ctx *c, int32_t n_vtx, const char *seq_concat, 
                              const int32_t *topo_rank)
 {
     return set_graph_impl(c, n_vtx, seq_concat, seq_off, adj_off, adj, n_walks, walk_off, walk_vtx, topo_rank);
+}
+
+// ---- phi_scout_graph: a second schedule over the stages above, for graphs of more walks than the DP takes.  It runs the
+// checks, the uploads, validate_topology and the GPU thread as it is (walk-entry pass without masks, classes, minimiser
+// table, read table, per-walk minimiser counts, hit vectors), then reset_read_state; it leaves out everything that serves
+// the DP alone -- start_pinning, start_dp_buffers, the host copy of the walk entries, refuse_interior_ends (a refusal of the
+// DP's model), build_step_stream, late_uploads_and_events.  Nothing of the index holds a walk id in a fixed-size field:
+// the classes, their records and both tables are keyed by context and hash, the per-walk counts are 64-bit sums over
+// contiguous entry ranges, and the walk-entry pass without masks only searches walk_off.  The limit of 65 535 walks is the
+// one panel_score.hip's matrix and the choice work with.
+// The full entries stay in d_walk_vtx (the index reads them) and count as retained: panel.full_off names them, and
+// phi_set_graph_panel(walk_vtx = NULL) with the same offsets moves them to panel.d_full before it starts.
+extern "C" int phi_scout_graph(phi_ctx *c, int32_t n_vtx, const char *seq_concat, const int64_t *seq_off, const int64_t *adj_off,
+                               const int32_t *adj, int32_t n_walks, const int64_t *walk_off, const int32_t *walk_vtx,
+                               const int32_t *topo_rank)
+{
+    if (!c) return PHI_ERR_INVALID;
+    if (n_vtx <= 0 || n_walks <= 0 || !seq_concat || !seq_off || !adj_off || !walk_off || !topo_rank)
+        return phi_fail(c, PHI_ERR_INVALID, "phi_scout_graph: null pointer or empty graph");
+    if (adj_off[n_vtx] > 0 && !adj) return phi_fail(c, PHI_ERR_INVALID, "phi_scout_graph: adj is null");
+    if (n_walks > PHI_SCOUT_MAX_WALKS) return phi_fail(c, PHI_ERR_UNSUPPORTED, "phi_scout_graph: more than %d walks", PHI_SCOUT_MAX_WALKS);
+    HIPCHK(hipSetDevice(c->device));
+    if (c->ipc || c->peers || c->comm) return phi_fail(c, PHI_ERR_STATE, "phi_scout_graph on a context that exchanges with others (a scout graph is one GPU's: leave the group first)");
+    PHICHK(set_graph_check_offsets(c, n_vtx, seq_off, adj_off, n_walks, walk_off));
+    auto &P = c->panel;
+    enum { FROM_HOST, IN_PLACE, FROM_RETAINED } from = FROM_HOST;
+    if (!walk_vtx) {
+        const bool same_off = P.full_off.size() == (size_t)n_walks + 1 && std::equal(P.full_off.begin(), P.full_off.end(), walk_off);
+        if (c->walks_on_device && c->walks_on_device_n == walk_off[n_walks] && (int32_t)(c->wtext.ends.size() / 2) == n_walks) from = IN_PLACE;
+        else if (c->scout.on && same_off) from = IN_PLACE;
+        else if (P.d_full.p && same_off) from = FROM_RETAINED;
+        else return phi_fail(c, PHI_ERR_STATE, "phi_scout_graph without walk_vtx: these walks are neither freshly resolved on this context nor retained by an earlier panel or scout");
+    }
+    c->have_graph = false;
+    c->chop.on = false;
+    P.on = false;
+    phi_scout_end(c);
+    c->solved = false;
+    phi_ladder_drop(c);
+    // (on failure below the context holds no graph and retains nothing)
+    if (from == FROM_RETAINED) { phi_dev_free(c->d_walk_vtx); std::swap(c->d_walk_vtx, P.d_full); }
+    else phi_dev_free(P.d_full);
+    P.full_off.clear();
+
+    SetGraph S(c, n_vtx, seq_concat, seq_off, adj_off, adj, n_walks, walk_off, walk_vtx, topo_rank);
+    PhiStageTimer &tm = S.tm;
+    S.n_edges = adj_off[n_vtx]; S.n_entries = walk_off[n_walks];
+    if (c->dp_alloc_future.valid()) (void)c->dp_alloc_future.get();
+    c->n_vtx = n_vtx; c->n_walks = n_walks; c->n_entries = S.n_entries;
+    start_uploads(S);
+    PHICHK(validate_topology(S));
+    tm.lap("scout: validate graph, copies");
+    c->dp_nw = 1;                                              // (no masks: the walk-entry pass does not look at it)
+    if (!c->h_walk_vtx.resize(0)) return phi_fail(c, PHI_ERR_NOMEM, "host allocation failed");
+    S.cnt_edge.assign((size_t)std::max<int64_t>(S.n_edges, 1), 0);
+    S.want_masks = false;
+    S.gpu = std::async(std::launch::async, [&S]() { return gpu_thread(S); });
+    copy_graph_to_host(S);                                     // (the per-vertex arrays and walk_off: phi_walk_minimizers, phi_walk_sharing)
+    PHICHK(S.edges_future.get());
+    PHICHK(report_walk_errors(S));
+    PHICHK(S.gpu.get());
+    tm.lap("scout: index on the GPU thread");
+    c->dp_events = false; c->dp_dense_ready = false; c->n_k = 0; c->n_ev = 0;
+    reset_read_state(c);
+    stage_release(c);
+    P.full_off.assign(walk_off, walk_off + n_walks + 1);
+    c->scout.on = true;
+    c->have_graph = true;
+    return PHI_OK;
 }

@@ -312,14 +312,14 @@ int phi_vcf_genotypes(phi_ctx *c, const char *text, int64_t n_text, const int64_
 // vcf2gfa.py:27-64, the W-lines that are never written: every kept haplotype's walk over units from the choice matrix
 // (vcf.hip), then chop.hip's count / scan / expand with unit_first in the place of first; the entries and their offsets
 // are left where phi_walk_text_resolve leaves them.
-int phi_vcf_walks(phi_ctx *c, const int32_t *unit_first, int64_t n_units, const int32_t *site_backbone, const int32_t *site_allele0,
-                  int64_t n_sites, const int32_t *choice, int32_t n_haps, int64_t *walk_off_out)
+static int vcf_walks(phi_ctx *c, const int32_t *unit_first, int64_t n_units, const int32_t *site_backbone, const int32_t *site_allele0,
+                     int64_t n_sites, const int32_t *choice, int32_t n_haps, int64_t *walk_off_out, int32_t max_haps)
 {
     if (!c) return PHI_ERR_INVALID;
     if (!unit_first || !walk_off_out || n_units < 1 || n_sites < 0 || n_haps < 1 || (n_sites > 0 && (!site_backbone || !site_allele0 || !choice)))
         return phi_fail(c, PHI_ERR_INVALID, "phi_vcf_walks: null pointer or empty table");
     if (n_units > INT32_MAX - 1 || n_units < 2 * n_sites + 1) return phi_fail(c, PHI_ERR_INVALID, "phi_vcf_walks: %lld units for %lld sites", (long long)n_units, (long long)n_sites);
-    if (n_haps > PHI_DP_MAX_WALKS) return phi_fail(c, PHI_ERR_UNSUPPORTED, "more than %d walks", PHI_DP_MAX_WALKS);
+    if (n_haps > max_haps) return phi_fail(c, PHI_ERR_UNSUPPORTED, "more than %d walks", max_haps);
     if (unit_first[0] != 0) return phi_fail(c, PHI_ERR_INVALID, "phi_vcf_walks: unit_first must start at 0");
     for (int64_t u = 0; u < n_units; u++)
         if (unit_first[u + 1] <= unit_first[u]) return phi_fail(c, PHI_ERR_INVALID, "phi_vcf_walks: unit %lld holds no segment", (long long)u);
@@ -361,6 +361,19 @@ int phi_vcf_walks(phi_ctx *c, const int32_t *unit_first, int64_t n_units, const 
     c->vcf.have = true;
     tm.lap("unit walks, count, scan, expand");
     return PHI_OK;
+}
+
+int phi_vcf_walks(phi_ctx *c, const int32_t *unit_first, int64_t n_units, const int32_t *site_backbone, const int32_t *site_allele0,
+                  int64_t n_sites, const int32_t *choice, int32_t n_haps, int64_t *walk_off_out)
+{
+    return vcf_walks(c, unit_first, n_units, site_backbone, site_allele0, n_sites, choice, n_haps, walk_off_out, PHI_DP_MAX_WALKS);
+}
+
+// every haplotype of a population VCF, for phi_scout_graph (set_graph.hip): the same body, the scout's limit
+int phi_vcf_walks_wide(phi_ctx *c, const int32_t *unit_first, int64_t n_units, const int32_t *site_backbone, const int32_t *site_allele0,
+                       int64_t n_sites, const int32_t *choice, int32_t n_haps, int64_t *walk_off_out)
+{
+    return vcf_walks(c, unit_first, n_units, site_backbone, site_allele0, n_sites, choice, n_haps, walk_off_out, PHI_SCOUT_MAX_WALKS);
 }
 
 int phi_vcf_stats(phi_ctx *c, phi_vcf_info *out)

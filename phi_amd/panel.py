@@ -48,7 +48,14 @@ def _as_arrays(g):
         return g
     if hasattr(g, "arrays"):
         return g.arrays()
-    return dict(seq_concat=g.seq_concat, seq_off=g.seq_off, adj_off=g.adj_off, adj=g.adj, walk_off=g.walk_off, walk_vtx=g.walk_vtx)
+    # (the host readers' graphs, a VcfGraph among them: their ranks are top_order_map; walk_vtx is None where the device holds the entries)
+    out = dict(seq_concat=g.seq_concat, seq_off=g.seq_off, adj_off=g.adj_off, adj=g.adj, walk_off=g.walk_off, walk_vtx=getattr(g, "walk_vtx", None))
+    rank = getattr(g, "top_rank", None)
+    if rank is None:
+        rank = getattr(g, "top_order_map", None)
+    if rank is not None:
+        out["top_rank"] = rank
+    return out
 
 
 def induced_arrays(A, keep):
@@ -151,3 +158,76 @@ def nested_panels(samples, sizes, seed, always=()):
     keys = splitmix64(seed, np.arange(len(rest)))
     order = sorted(range(len(rest)), key=lambda i: (int(keys[i]), i))
     return [always + [rest[i] for i in order[:n]] for n in sizes]
+
+
+def choose_panel(S, n_want, always=None):
+    """The rule of phi_panel_choose (include/phi_host.h) restated in numpy: which n_want walks to keep, from S[block, walk] =
+    read support per block of the graph and walk (Context.scout_scores).  It stands in for what `vg haplotypes` answers from
+    the reads' k-mers (data/vg_haplotypes.py:21-29) and for the lists of names of data/chop_graph.sh:46-66; the rule is this
+    project's own, it is not `vg haplotypes`' and has not been compared with it.
+      1. the `always` walks are in (more of them than n_want: ValueError; 1 <= n_want <= min(walks, 1022))
+      2. in block b the walks are ordered by (-S[b, h], h)
+      3. round r: votes[h] = blocks whose r-th walk is h with S[b, h] > 0; walks with votes that are not yet in enter by
+         (votes descending, total S[:, h].sum() descending, id ascending) until the panel holds n_want
+      4. a round without votes ends the rounds; the rest is filled by (total descending, id ascending)
+    Returns (keep uint8[walks], round_of int32[walks]: -1 always, r entered in round r, walks = the fill, -2 not chosen)."""
+    S = np.asarray(S, np.int64)
+    n_blocks, n_walks = S.shape
+    keep = np.zeros(n_walks, np.uint8) if always is None else (np.asarray(always) != 0).astype(np.uint8)
+    if keep.shape != (n_walks,):
+        raise ValueError(f"always must hold one flag per walk ({n_walks})")
+    if n_blocks < 1 or n_walks < 1 or not 1 <= n_want <= min(n_walks, 1022) or int(keep.sum()) > n_want:
+        raise ValueError("choose_panel: n_want must lie in 1 .. min(walks, 1022) and hold the always-kept walks")
+    round_of = np.where(keep != 0, -1, -2).astype(np.int32)
+    total = S.sum(0)
+    ids = np.arange(n_walks)
+    order = np.argsort(-S, axis=1, kind="stable")               # (stable: equal scores stay in id order)
+    n_in = int(keep.sum())
+    for r in range(n_walks):
+        if n_in >= n_want:
+            break
+        pick = order[:, r]
+        pick = pick[S[np.arange(n_blocks), pick] > 0]
+        if len(pick) == 0:
+            break
+        votes = np.bincount(pick, minlength=n_walks)
+        cand = ids[(votes > 0) & (keep == 0)]
+        cand = cand[np.lexsort((cand, -total[cand], -votes[cand]))][:n_want - n_in]
+        keep[cand] = 1
+        round_of[cand] = r
+        n_in += len(cand)
+    if n_in < n_want:
+        rest = ids[keep == 0]
+        rest = rest[np.lexsort((rest, -total[rest]))][:n_want - n_in]
+        keep[rest] = 1
+        round_of[rest] = n_walks
+    return keep, round_of
+
+
+def auto_panel(ctx, A, reads, n_want, always=None, n_blocks=0, chop=None, text=False):
+    """The panel chosen from the reads, start to end, on one Context: a graph of thousands of walks in, the reads scored
+    against a panel of n_want of them out (ctx.solve() follows).  In the place of `vg haplotypes` in front of the inference
+    (data/vg_haplotypes.py:21-29) and of the panels by name of data/chop_graph.sh:46-66; the rule of the choice
+    (choose_panel) is this project's own and has not been compared with `vg haplotypes`.
+      1. scout    ctx.scout_graph: the index of every walk, no DP
+      2. collect  the reads into a store on the device (ctx.collect_reads; text=True: pieces of FASTA / FASTQ text)
+      3. score    ctx.collect_score: the hit vector of the full index
+      4. scores   ctx.scout_scores(n_blocks): read support per block and walk, on the device
+      5. choose   ctx.scout_choose(n_want, always)
+      6. panel    ctx.set_graph(..., walk_vtx=None, keep=chosen, chop=chop, keep_reads=True) from the entries the scout retained
+      7. score    ctx.collect_score: the same reads against the panel's index
+    A: the arrays of set_graph as a dict (seq_concat, seq_off, adj_off, adj, walk_off, walk_vtx -- None for entries the device
+    holds --, top_rank).  Returns a dict: keep, round_of, n_rounds, walk_off (the panel's), info (scout_scores'), n_reads,
+    n_bases."""
+    A = _as_arrays(A)
+    ctx.scout_graph(A["seq_concat"], A["seq_off"], A["adj_off"], A["adj"], A["walk_off"], A.get("walk_vtx"), A["top_rank"])
+    n_reads, n_bases = ctx.collect_reads(reads, text=text)
+    ctx.collect_score()
+    _, info = ctx.scout_scores(n_blocks, copy=False)
+    keep, round_of = ctx.scout_choose(n_want, always)
+    walk_off = ctx.set_graph(A["seq_concat"], A["seq_off"], A["adj_off"], A["adj"], A["walk_off"], None, None, chop=chop, keep=keep,
+                             keep_reads=True)
+    ctx.collect_score()
+    entered = round_of[(round_of >= 0) & (round_of < len(round_of))]
+    return dict(keep=keep, round_of=round_of, n_rounds=int(entered.max()) + 1 if len(entered) else 0, walk_off=walk_off, info=info,
+                n_reads=n_reads, n_bases=n_bases)
