@@ -775,6 +775,62 @@ int phi_add_reads_bam_parked(phi_ctx *ctx, phi_text_park *park, int32_t index);
 int phi_reads_bam_end(phi_ctx *ctx, phi_bam_info *info);
 int phi_reads_bam_last_batch(phi_ctx *ctx, char *bases, int64_t cap_bases, int64_t *off, int64_t cap_reads, int64_t *n_reads, int64_t *n_bases);
 
+/*
+ * VARIANT CALLS of the inferred path, or of any walk, against a reference walk of the set graph, made on the device
+ * (DESIGN.md 4.16).  No reference counterpart: the reference's one product is a FASTA (ILP_index.cpp:1577-1581).  The
+ * comparison the calls serve is the one the reference makes the other way round -- PanGenie's VCF turned into a FASTA with
+ * `bcftools consensus` (data/run_PG.py:54-60) so that it can be set beside PHI's output at all -- and any comparison with a
+ * truth VCF.  THE RULE IS THIS PROJECT'S OWN: it is not `vg deconstruct`'s and has not been compared with it or `bcftools`.
+ *
+ * The rule.  The set graph is the one phi_set_graph* was given (after a chop the pieces, after a panel the panel graph); all
+ * ids are its ids.  The query is the path of the last phi_solve or a walk; r is a walk.
+ *   1. A vertex is SHARED when it lies on the query and on walk r.  The graph is acyclic, so shared vertices come in the same
+ *      order on both; where they do not: PHI_ERR_WALK.  No shared vertex at all: PHI_ERR_UNSUPPORTED.
+ *   2. Calls cover the part between the first and the last shared vertex, both included; what either has outside it is not
+ *      called.  ref_span / query_span give that part in bases of walk r and of the query's sequence ([first, behind last)).
+ *   3. Consecutive shared vertices a, b (query indices i < i', indices on r p < p'): no call when i' = i + 1 and p' = p + 1,
+ *      else one call: REF = the sequences of r's vertices p + 1 .. p' - 1, ALT = those of the query's i + 1 .. i' - 1, POS = the
+ *      0-based base offset of REF's first byte along walk r.  If REF or ALT is empty both get the last base of a in front and
+ *      POS moves one back.
+ *   4. Nothing is normalised: no common prefix or suffix is trimmed, nothing is left-aligned (`bcftools norm` does that), the
+ *      bytes are the graph's own in their original case.  Calls come in ascending POS and do not overlap.
+ *   5. A call whose REF and ALT are the same bytes (other vertices, the same sequence) is returned like any other;
+ *      phi_write_calls_vcf (phi_host.h) drops it and counts it.
+ *   6. anchor[k] = the query index i of call k's left anchor a.
+ *
+ *   phi_calls_path   (no reference counterpart; for the comparison of data/run_PG.py:54-60) the path of the last phi_solve
+ *                    against walk ref_walk.  PHI_ERR_STATE without a solved path.
+ *   phi_calls_walk   (no reference counterpart; for the comparison of data/run_PG.py:54-60) walk `walk` against walk ref_walk:
+ *                    a leave-one-out truth -- the dropped sample's own calls -- is made by the same code.
+ *   phi_calls_stats  (no reference counterpart) what the last successful call did: sizes, the algorithmic bytes as DESIGN.md
+ *                    4.16 counts them, GPU milliseconds per stage by HIP events on the context's stream.
+ * The buffers behind phi_calls are owned by the context and stay valid until the next phi_calls_*, phi_solve, phi_set_graph*
+ * or phi_ctx_destroy.  Limits: fewer than 2^31 calls, a query and a reference walk of fewer than 2^31 - 1 entries each, an
+ * allele of fewer than 2^31 bytes (PHI_ERR_UNSUPPORTED beyond); byte offsets are 64-bit.  walk or ref_walk outside the set
+ * graph's walks (after a panel: the kept ones, renumbered): PHI_ERR_INVALID.  Before phi_set_graph or on a scout:
+ * PHI_ERR_STATE.  After any refusal the context stays usable: graph, reads and result are as they were.
+ */
+typedef struct {
+    int64_t n_calls;
+    const int64_t *pos;                              /* [n_calls] 0-based, in bases of the reference walk */
+    const int64_t *ref_off, *alt_off;                /* [n_calls + 1] call k's REF = ref_bytes[ref_off[k], ref_off[k + 1]) */
+    const char *ref_bytes, *alt_bytes;
+    const int32_t *anchor;                           /* [n_calls] rule 6 */
+    int64_t n_shared, n_query, n_ref;                /* shared vertices; vertices of the query and of the reference walk */
+    int64_t ref_span[2], query_span[2];              /* rule 2 */
+    double gpu_ms;                                   /* first launch to last kernel, by HIP events */
+} phi_calls;
+typedef struct {
+    int64_t n_query, n_ref, n_shared, n_pairs, n_calls;
+    int64_t ref_bytes, alt_bytes;
+    int64_t ref_bases, query_bases;                  /* bases of the whole reference walk and of the whole query */
+    int64_t bytes_moved;                             /* the algorithmic bytes of all kernels */
+    double table_gpu_ms, shared_gpu_ms, pairs_gpu_ms, fill_gpu_ms, gpu_ms;
+} phi_calls_info;
+int phi_calls_path(phi_ctx *ctx, int32_t ref_walk, phi_calls *out);
+int phi_calls_walk(phi_ctx *ctx, int32_t walk, int32_t ref_walk, phi_calls *out);
+int phi_calls_stats(phi_ctx *ctx, phi_calls_info *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -205,6 +205,18 @@ int phi_hap_name(const char *gfa_path, const char *reads_path, char *out, int ca
 /* ">" name " LN:" len, then the sequence in 80-column lines. */
 int phi_write_fasta(const char *path, const char *name, const char *seq, int64_t len);
 
+/* The calls of phi_calls_path / phi_calls_walk (phi_amd.h; no reference counterpart, the file serves the comparison of
+ * data/run_PG.py:54-60) as plain-text VCFv4.2: ##fileformat, ##source, ##contig=<ID=contig,length=contig_len>, the INFO line
+ * of PH and the FORMAT line of GT, the column line with one sample, then per call
+ *     contig  pos + 1  .  REF  ALT  .  PASS  PH=<ph[k]>  GT  1
+ * (tabs; INFO is "." where ph is NULL or ph[k] is NULL or empty; the bytes of REF and ALT as they are, case kept).  A call
+ * whose REF and ALT are the same bytes is not written and counted in *n_dropped; *n_written = the records written (either
+ * may be NULL).  PHI_HOST_ERR_INVALID, with a message, for a path that ends in ".gz" (the project has no deflate writer:
+ * nothing is written) and for a call with an empty allele; PHI_HOST_ERR_IO when the file cannot be written. */
+int phi_write_calls_vcf(const char *path, const char *contig, int64_t contig_len, const char *sample, int64_t n_calls, const int64_t *pos,
+                        const int64_t *ref_off, const char *ref_bytes, const int64_t *alt_off, const char *alt_bytes, const char *const *ph,
+                        int64_t *n_written, int64_t *n_dropped, char *err, int err_cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,6 +39,7 @@ SYMBOLS = [
     "phi_scout_graph", "phi_scout_scores", "phi_scout_choose", "phi_reads_collect_score", "phi_vcf_walks_wide",
     "phi_prefix_sums",
     "phi_reads_bam_begin", "phi_add_reads_bam", "phi_add_reads_bam_parked", "phi_reads_bam_end", "phi_reads_bam_last_batch",
+    "phi_calls_path", "phi_calls_walk", "phi_calls_stats",
 ]
 PHI_PANEL_RETAIN = 1
 PHI_PANEL_KEEP_READS = 2
@@ -92,6 +93,18 @@ class PhiBamInfo(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("n_records", "n_kept", "n_secondary_supplementary", "n_empty", "n_reverse", "n_bases", "header_bytes",
                                          "tiles", "tiles_confirmed", "tiles_rewalked", "batches", "batches_without_offsets")] + [
         ("n_ref", C.c_int32), ("one_length", C.c_int32)]
+
+
+class PhiCalls(C.Structure):
+    _fields_ = [("n_calls", C.c_int64), ("pos", C.POINTER(C.c_int64)), ("ref_off", C.POINTER(C.c_int64)), ("alt_off", C.POINTER(C.c_int64)),
+                ("ref_bytes", C.c_void_p), ("alt_bytes", C.c_void_p), ("anchor", C.POINTER(C.c_int32)),
+                ("n_shared", C.c_int64), ("n_query", C.c_int64), ("n_ref", C.c_int64),
+                ("ref_span", C.c_int64 * 2), ("query_span", C.c_int64 * 2), ("gpu_ms", C.c_double)]
+
+
+class PhiCallsInfo(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_query", "n_ref", "n_shared", "n_pairs", "n_calls", "ref_bytes", "alt_bytes", "ref_bases", "query_bases", "bytes_moved")] + [
+        (n, C.c_double) for n in ("table_gpu_ms", "shared_gpu_ms", "pairs_gpu_ms", "fill_gpu_ms", "gpu_ms")]
 
 
 class PhiResult(C.Structure):
@@ -185,6 +198,9 @@ def load():
     L.phi_add_reads_bam_parked.argtypes = [vp, vp, i32]
     L.phi_reads_bam_end.argtypes = [vp, C.POINTER(PhiBamInfo)]
     L.phi_reads_bam_last_batch.argtypes = [vp, vp, i64, vp, i64, C.POINTER(i64), C.POINTER(i64)]
+    L.phi_calls_path.argtypes = [vp, i32, C.POINTER(PhiCalls)]
+    L.phi_calls_walk.argtypes = [vp, i32, i32, C.POINTER(PhiCalls)]
+    L.phi_calls_stats.argtypes = [vp, C.POINTER(PhiCallsInfo)]
     L.phi_reads_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
     L.phi_hits_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(i64)]
     L.phi_read_table.argtypes = [vp, C.POINTER(vp), C.POINTER(i64)]

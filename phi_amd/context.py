@@ -630,6 +630,36 @@ class Context:
         self._chk(self._L.phi_path_sequence(self._h, buf, hap_len))
         return buf.raw[:hap_len]
 
+    # ------------------------------------------------------------------ variant calls against a reference walk
+    def calls(self, ref_walk, walk=None):
+        """The path of the last solve() (walk=None: phi_calls_path) or walk `walk` of the set graph (phi_calls_walk) as
+        variant calls against walk ref_walk, made on the device by the rule of include/phi_amd.h: a dict of n_calls, pos
+        (int64, 0-based in bases of the reference walk), ref_off / alt_off (int64[n + 1]), ref_bytes / alt_bytes (bytes),
+        anchor (int32: the query index of each call's left anchor), n_shared, n_query, n_ref, ref_span, query_span
+        (tuples [first, behind last) in bases) and gpu_ms.  phi_amd.calls has apply() and write_vcf() over it."""
+        r = _capi.PhiCalls()
+        if walk is None:
+            self._chk(self._L.phi_calls_path(self._h, int(ref_walk), C.byref(r)))
+        else:
+            self._chk(self._L.phi_calls_walk(self._h, int(walk), int(ref_walk), C.byref(r)))
+        n = r.n_calls
+        out = {f: getattr(r, f) for f in ("n_calls", "n_shared", "n_query", "n_ref", "gpu_ms")}
+        out["pos"] = np.ctypeslib.as_array(r.pos, shape=(n,)).copy() if n else np.zeros(0, np.int64)
+        out["anchor"] = np.ctypeslib.as_array(r.anchor, shape=(n,)).copy() if n else np.zeros(0, np.int32)
+        out["ref_off"] = np.ctypeslib.as_array(r.ref_off, shape=(n + 1,)).copy()
+        out["alt_off"] = np.ctypeslib.as_array(r.alt_off, shape=(n + 1,)).copy()
+        out["ref_bytes"] = C.string_at(r.ref_bytes, int(out["ref_off"][n])) if out["ref_off"][n] else b""
+        out["alt_bytes"] = C.string_at(r.alt_bytes, int(out["alt_off"][n])) if out["alt_off"][n] else b""
+        out["ref_span"] = (r.ref_span[0], r.ref_span[1])
+        out["query_span"] = (r.query_span[0], r.query_span[1])
+        return out
+
+    def calls_stats(self):
+        """What the last calls() did (phi_calls_stats): sizes, the algorithmic bytes, GPU milliseconds per stage."""
+        r = _capi.PhiCallsInfo()
+        self._chk(self._L.phi_calls_stats(self._h, C.byref(r)))
+        return {n: getattr(r, n) for n, _ in _capi.PhiCallsInfo._fields_}
+
     # ------------------------------------------------------------------ evaluation
     def edit_distances(self, a_list, b_list, max_distance=-1):
         """edlib NW edit distance of every pair (a_list[i], b_list[i]) of byte strings on the GPU (phi_edit_distances):

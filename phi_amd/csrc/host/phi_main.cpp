@@ -9,6 +9,8 @@
 //         [--panel-auto N [--panel-blocks B] [--panel-always NAME,..]]   (the panel of N walks chosen from the reads)
 //                                                             a panel of the graph's haplotypes, subset inside "set graph"
 //                                                             (data/chop_graph.sh:46-66); -o 'out.{panel}.fa': one FASTA per panel
+//         [--calls FILE [--calls-ref NAME] [--calls-contig NAME]]   the inferred haplotype as variant calls against a reference walk
+//                                                             (plain-text VCF; one --calls per -o, in order, same placeholder)
 //   ./PHI -g <target.gfa> -r a.fq -o a.fa -r b.fq -o b.fa ...      several read sets against ONE graph: the graph is parsed and
 //         indexed once (the reference's harness runs PHI once per sample x coverage on the same graph,
 //         data/run_batch_4_miqp.py:31-46), every job prints the log of a run of its own and writes its own FASTA
@@ -139,6 +141,13 @@ static void usage(FILE *fp, int k, int w, int R, int q, int m, float T, int t, c
     fprintf(fp, "    -r INT       Read [%s]\n", r);
     fprintf(fp, "    -o INT       Output haplotype [%s]\n", o);
     fprintf(fp, "    -d bool      Debug mode [%d]\n", d);
+    fprintf(fp, "    --calls FILE           the inferred haplotype as variant calls (plain-text VCFv4.2, no .gz) against a reference walk of\n");
+    fprintf(fp, "                           the graph; one per -o, in order, with the same {cov} / {panel} placeholder where -o takes one.\n");
+    fprintf(fp, "                           The rule is this program's own (not vg deconstruct's): nothing is trimmed or left-aligned\n");
+    fprintf(fp, "    --calls-ref NAME       the reference walk, named as the log names walks (SAMPLE.HAP); required with -g, REF.0 with --vcf;\n");
+    fprintf(fp, "                           under a panel it must be among the kept walks (--panel-always keeps it)\n");
+    fprintf(fp, "    --calls-contig NAME    the contig of the records [--vcf: the VCF's contig; -g: the reference walk's name].  With -g POS\n");
+    fprintf(fp, "                           counts the walk's own bases from 1: a W-line's start offset is not kept by the reader\n");
 }
 
 struct Options {
@@ -171,6 +180,10 @@ struct Options {
     // --panel-auto N [--panel-blocks B]: the panel of N walks chosen from the reads, per read set (phi_scout_graph, phi_scout_scores,
     // phi_scout_choose: in the place of `vg haplotypes`, data/vg_haplotypes.py:21-29, in front of data/chop_graph.sh:46-66)
     int panel_auto = 0, panel_blocks = 0;
+    // --calls FILE [--calls-ref NAME] [--calls-contig NAME]: the inferred path written as variant calls against a reference walk
+    // (phi_calls_path, phi_write_calls_vcf; no reference counterpart: for the comparison of data/run_PG.py:54-60); one per -o
+    std::vector<std::string> calls_files;
+    std::string calls_ref, calls_contig;
     bool panel() const { return have_keep || have_drop || !panel_sizes.empty() || panel_auto > 0; }
     int argc = 0;
     char **argv = nullptr;
@@ -565,6 +578,9 @@ struct Driver {
     bool auto_on = false, auto_scouted = false;
     std::vector<int64_t> auto_walk_off;
     bool panel_on() const { return o.panel() && (o.panel_auto <= 0 || auto_on); }
+    // --calls: the job, coverage and panel at hand (what the placeholders of the job's --calls name stand for)
+    int job_now = 0;
+    std::string cov_now, panel_now;
     explicit Driver(const Options &opt) : o(opt), devices(opt.devices), reads_file(opt.reads_files[0]), hap_file(opt.hap_files[0]), reads_kind_now(opt.reads_kinds.empty() ? 0 : opt.reads_kinds[0]) {}
 
     // the one error exit: the message, the reader thread stopped, status 1
@@ -1096,6 +1112,7 @@ struct Driver {
             if (phi_write_fasta(hap_file.c_str(), hap_name, seq.get(), res.hap_len) != PHI_HOST_OK) return fail("[E::main] cannot write %s\n", hap_file.c_str());
         }
         stamp("ILP_function"); fprintf(stderr, "Haplotype of size: %d written to: %s\n", (int)res.hap_len, hap_file.c_str());
+        if (!o.calls_files.empty() && write_calls(res)) return 1;
         fprintf(stderr, "[M::%s] PHI Version: %s\n[M::%s] CMD:", "main", PHI_VERSION, "main");
         for (int i = 0; i < o.argc; ++i) fprintf(stderr, " %s", o.argv[i]);
         fprintf(stderr, "\n[M::%s] Real time: %.3f sec; CPU: %.3f sec; Peak RSS: %.3f GB\n", "main", realtime() - t0_real, cputime(), peakrss() / 1024.0 / 1024.0 / 1024.0);
@@ -1110,6 +1127,51 @@ struct Driver {
                 o.detached ? "; teardown detached" : "");
         g_marks.print();
         print_resident();
+        return 0;
+    }
+    // ---- --calls: the reference walk among the context's walks (after a panel: the kept ones, through phi_panel_walks' ids).
+    //      1 with a message when the graph holds no such walk or the panel has dropped it: never another walk silently
+    int calls_ref_walk(int32_t *out)
+    {
+        const std::string want = !o.calls_ref.empty() ? o.calls_ref : "REF.0";      // (main refuses -g without --calls-ref)
+        int32_t in_g = -1;
+        for (int32_t h = 0; h < phi_graph_n_walks(g) && in_g < 0; h++)
+            if (want == phi_graph_hap_name(g, h)) in_g = h;
+        if (in_g < 0) return fail("[E::main] --calls-ref %s: the graph holds no walk of that name (walks are named SAMPLE.HAP, as the log prints them)\n", want.c_str());
+        if (!panel_on()) { *out = in_g; return 0; }
+        for (size_t k = 0; k < kept_walks.size(); k++)
+            if (kept_walks[k] == in_g) { *out = (int32_t)k; return 0; }
+        return fail("[E::main] --calls-ref %s: the panel does not keep this walk, and calls are made against no other; keep it with --panel-always %s (or --keep-samples)\n",
+                    want.c_str(), sample_of(want.c_str()).c_str());
+    }
+    // the path of the solve just reported as calls against the reference walk, written beside the FASTA
+    int write_calls(const phi_result &res)
+    {
+        std::string file = o.calls_files[(size_t)job_now];
+        for (size_t at; !cov_now.empty() && (at = file.find("{cov}")) != std::string::npos;) file.replace(at, 5, cov_now);
+        for (size_t at; !panel_now.empty() && (at = file.find("{panel}")) != std::string::npos;) file.replace(at, 7, panel_now);
+        int32_t r = 0;
+        if (calls_ref_walk(&r)) return 1;
+        Stage st("calls (device) + VCF write");
+        phi_calls cl;
+        phi_calls_info ci;
+        int rc;
+        if ((rc = phi_calls_path(ctx, r, &cl)) || (rc = phi_calls_stats(ctx, &ci))) return fail_on(ctx, "calls", rc);
+        const char *ref_name = walk_name(r);
+        const bool vcf_ref = o.from_vcf && !strcmp(ref_name, "REF.0");
+        const std::string contig = !o.calls_contig.empty() ? o.calls_contig : vcf_ref ? phi_vcf_contig(vcf) : ref_name;
+        const int64_t contig_len = vcf_ref ? phi_vcf_ref_len(vcf) : ci.ref_bases;
+        std::vector<const char *> ph((size_t)cl.n_calls);
+        for (int64_t k = 0; k < cl.n_calls; k++) ph[(size_t)k] = walk_name(res.path_hap[cl.anchor[k] + 1]);
+        int64_t n_written = 0, n_dropped = 0;
+        char werr[512] = "";
+        if (phi_write_calls_vcf(file.c_str(), contig.c_str(), contig_len, hap_name, cl.n_calls, cl.pos, cl.ref_off, cl.ref_bytes, cl.alt_off, cl.alt_bytes,
+                                ph.data(), &n_written, &n_dropped, werr, sizeof werr) != PHI_HOST_OK)
+            return fail("[E::main] %s\n", werr[0] ? werr : "cannot write the calls");
+        stamp("main");
+        fprintf(stderr, "Calls: %lld written to %s, %lld dropped as REF = ALT; called span [%lld,%lld) of %s (%lld bases), [%lld,%lld) of the haplotype\n",
+                (long long)n_written, file.c_str(), (long long)n_dropped, (long long)cl.ref_span[0], (long long)cl.ref_span[1], ref_name, (long long)ci.ref_bases,
+                (long long)cl.query_span[0], (long long)cl.query_span[1]);
         return 0;
     }
     // ---- recombination report (:1508-1550): segments in output coordinates
@@ -1177,6 +1239,7 @@ struct Driver {
             loaded();
         }
         if (!hap_pattern.empty()) hap_file = hap_pattern;
+        job_now = job;
         if (auto_on) {                                        // (--panel-auto: the scout again for a further read set, from the retained entries)
             if ((job > 0 || !first_of_run) && scout_index()) return 1;
             return run_auto_job();
@@ -1210,12 +1273,14 @@ struct Driver {
             lr += li.band_reads[j]; lb += li.band_bases[j];
             hap_file = pattern;
             for (size_t at; (at = hap_file.find("{cov}")) != std::string::npos;) hap_file.replace(at, 5, o.cov_names[j]);
+            cov_now = o.cov_names[j];
             fprintf(stderr, "Coverage %sx: fraction %.6f, %lld reads, %lld bases\n", o.cov_names[j].c_str(), fr[j], (long long)lr, (long long)lb);
             const int r = solve_and_report();
             if (r == 1) return 1;
             if (r) status = r;
         }
         hap_file = pattern;
+        cov_now.clear();
         if ((rc = phi_reads_collect_release(ctx))) return fail_on(ctx, "collect release", rc);
         return status;
     }
@@ -1230,6 +1295,7 @@ struct Driver {
         }
         stamp("ILP_function"); fprintf(stderr, "Graph has %d vertices, %d walks and read has %d reads\n", panel_on() ? (int)panel_info.n_vtx_out : phi_graph_n_vtx(g),
                                       panel_on() ? (int)kept_walks.size() : phi_graph_n_walks(g), (int)total_reads);
+        if (int32_t r = 0; !o.calls_files.empty() && calls_ref_walk(&r)) return 1;      // (a --calls-ref the panel dropped: before the solve)
         phi_result res;
         if (Stage st("phi_solve (filter, exact solve, decode)"); (rc = phi_solve(ctx, &res))) return fail_on(ctx, "solve", rc);
         if (report(res)) return 1;
@@ -1307,6 +1373,7 @@ static int run(const Options &o)
             if (!d.panels.empty()) {
                 d.hap_pattern = o.hap_files[(size_t)job];
                 for (size_t at; (at = d.hap_pattern.find("{panel}")) != std::string::npos;) d.hap_pattern.replace(at, 7, o.panel_names[pj]);
+                d.panel_now = o.panel_names[pj];
             }
             const int r = d.run_job(job, pj == 0 && job == 0);
             if (r == 1) return 1;
@@ -1327,7 +1394,8 @@ int main(int argc, char *argv[])
                                            {"coverage", required_argument, 0, 308}, {"genome-size", required_argument, 0, 309}, {"seed", required_argument, 0, 310},
                                            {"keep-samples", required_argument, 0, 311}, {"drop-samples", required_argument, 0, 312}, {"panels", required_argument, 0, 313},
                                            {"panel-seed", required_argument, 0, 314}, {"panel-always", required_argument, 0, 315},
-                                           {"panel-auto", required_argument, 0, 316}, {"panel-blocks", required_argument, 0, 317}, {0, 0, 0, 0}};
+                                           {"panel-auto", required_argument, 0, 316}, {"panel-blocks", required_argument, 0, 317},
+                                           {"calls", required_argument, 0, 318}, {"calls-ref", required_argument, 0, 319}, {"calls-contig", required_argument, 0, 320}, {0, 0, 0, 0}};
     int c;
     std::string gfa_arg, vcf_arg;
     // main.cpp:38 declares -h with an argument; a bare -h falls into the usage branch either way
@@ -1389,6 +1457,9 @@ int main(int argc, char *argv[])
         else if (c == 314) o.panel_seed = strtoull(optarg, nullptr, 10);
         else if (c == 316) { o.panel_auto = atoi(optarg); if (o.panel_auto < 1 || o.panel_auto > 1022) { fprintf(stderr, "[E::main] --panel-auto takes the number of walks to keep, 1 to 1022\n"); return 1; } }
         else if (c == 317) { o.panel_blocks = atoi(optarg); if (o.panel_blocks < 1 || o.panel_blocks > 65536) { fprintf(stderr, "[E::main] --panel-blocks takes a number of blocks, 1 to 65536\n"); return 1; } }
+        else if (c == 318) o.calls_files.push_back(optarg);
+        else if (c == 319) o.calls_ref = optarg;
+        else if (c == 320) o.calls_contig = optarg;
         else if (c == 304) o.shard_min_bases = std::max<long long>(1, atoll(optarg));
         else if (c == 303) {                                   // --devices 0,1,2,...: shard the reads over these GPUs
             o.devices.clear();
@@ -1438,6 +1509,17 @@ int main(int argc, char *argv[])
         if (o.panel_sizes.size() > 1)
             for (const std::string &h : o.hap_files)
                 if (h.find("{panel}") == std::string::npos) { fprintf(stderr, "[E::main] --panels with several sizes: -o must contain {panel} (got %s), e.g. -o 'out.{panel}.fa'\n", h.c_str()); return 1; }
+    }
+    if (o.calls_files.empty()) {
+        if (!o.calls_ref.empty() || !o.calls_contig.empty()) { fprintf(stderr, "[E::main] --calls-ref and --calls-contig go with --calls FILE\n"); return 1; }
+    } else {
+        if (o.calls_files.size() != o.hap_files.size()) { fprintf(stderr, "[E::main] %zu --calls but %zu -o: one --calls per -o, paired in order (-r a.fq -o a.fa --calls a.vcf -r b.fq -o b.fa --calls b.vcf ...), or none at all\n", o.calls_files.size(), o.hap_files.size()); return 1; }
+        if (!o.from_vcf && o.calls_ref.empty()) { fprintf(stderr, "[E::main] --calls with -g needs --calls-ref NAME: the walk the calls are made against, named as the log names walks (SAMPLE.HAP)\n"); return 1; }
+        for (const std::string &f : o.calls_files) {
+            if (f.size() >= 3 && f.compare(f.size() - 3, 3, ".gz") == 0) { fprintf(stderr, "[E::main] --calls %s: the calls are written as plain text (there is no deflate writer); give a name that does not end in .gz\n", f.c_str()); return 1; }
+            if (o.cov.size() > 1 && f.find("{cov}") == std::string::npos) { fprintf(stderr, "[E::main] --coverage with several coverages: --calls must contain {cov} (got %s), e.g. --calls 'out.{cov}x.vcf'\n", f.c_str()); return 1; }
+            if (o.panel_sizes.size() > 1 && f.find("{panel}") == std::string::npos) { fprintf(stderr, "[E::main] --panels with several sizes: --calls must contain {panel} (got %s), e.g. --calls 'out.{panel}.vcf'\n", f.c_str()); return 1; }
+        }
     }
     o.argc = argc; o.argv = argv;
     t0_real = realtime();

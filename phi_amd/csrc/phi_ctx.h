@@ -306,6 +306,19 @@ struct phi_ctx {
     std::vector<int64_t> h_n_minimizers, h_n_anchors;
     phi_result result{};
     bool solved = false;
+    // the path of the last solve as stretches of walk entries (walk h, entries es .. ee of d_walk_vtx): what phi_calls_path
+    // expands on the device (calls.hip)
+    struct PhiPathSeg { int32_t h; int64_t es, ee; };
+    std::vector<PhiPathSeg> path_segs;
+    // ---- variant calls of the path or of a walk against a reference walk (calls.hip): the host copies phi_calls points into
+    struct PhiCalls {
+        bool have = false;
+        std::vector<int64_t> pos, ref_off, alt_off;
+        std::vector<int32_t> anchor;
+        std::vector<char> ref_bytes, alt_bytes;
+        int64_t span[4] = {0, 0, 0, 0};
+        phi_calls_info info{};
+    } calls;
 
     // ---- profiling of the sketch kernel
     bool prof = false;

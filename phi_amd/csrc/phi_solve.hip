@@ -1144,6 +1144,9 @@ int phi_solve_impl(phi_ctx *c)
     R.retained = spectrum - filtered;
     R.n_in_model = in_model;
     tm.lap("decode");
+    c->path_segs.clear();                                      // (phi_calls_path expands them on the device)
+    for (const Seg &s : best_segs) c->path_segs.push_back({s.h, s.es, s.ee});
+    c->calls.have = false;
     c->solved = true;
     return PHI_OK;
 }

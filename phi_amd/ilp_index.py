@@ -35,7 +35,7 @@ HOST_SYMBOLS = [
     "phi_vcf_rec_gt_index", "phi_vcf_rec_alt_off", "phi_vcf_alt_pos", "phi_vcf_alt_bytes", "phi_vcf_site_off", "phi_vcf_text", "phi_vcf_text_off",
     "phi_vcf_parse_gt", "phi_vcf_build", "phi_vcf_n_units", "phi_vcf_unit_first", "phi_vcf_n_real_sites", "phi_vcf_site_backbone",
     "phi_vcf_site_allele0", "phi_vcf_n_kept_haps", "phi_vcf_choice",
-    "phi_bam_header", "phi_panel_choose",
+    "phi_bam_header", "phi_panel_choose", "phi_write_calls_vcf",
 ]
 PHI_HOST_NEED_MORE = -6
 
@@ -122,6 +122,8 @@ def host_lib():
     L.phi_vcf_parse_gt.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, C.c_int32, vp, vp, C.c_char_p, C.c_int]
     L.phi_vcf_build.argtypes = [vp, vp, vp, C.c_int32, C.POINTER(vp), C.c_char_p, C.c_int]
     L.phi_write_fasta.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int64]
+    L.phi_write_calls_vcf.argtypes = [C.c_char_p, C.c_char_p, C.c_int64, C.c_char_p, C.c_int64, vp, vp, vp, vp, vp, vp,
+                                      C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_char_p, C.c_int]
     L.phi_bam_header.argtypes = [vp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_char_p, C.c_int]
     L.phi_panel_choose.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int32, vp, vp]
     for n in HOST_SYMBOLS:
