@@ -16,6 +16,7 @@
 #include "../../include/phi_amd.h"
 #include "phi_kernels.h"
 #include "phi_host_par.h"          // phi_host_threads, phi_parallel_chunks, PhiHostError (no HIP: shared with dp_steps.h)
+#include "solve_host.h"            // PhiAnchorHost, PhiAnchorSpan and the solve's host rules (no HIP: shared with its stand-alone check)
 
 // growable device buffer
 struct DevBuf {
@@ -23,11 +24,6 @@ struct DevBuf {
     size_t cap = 0;
     uint32_t gen = 0;        // bumped by phi_dev_ensure whenever the memory behind p changes hands (a new allocation, a buffer from the pool)
     template <class T> T *as() const { return reinterpret_cast<T *>(p); }
-};
-
-struct PhiAnchorHost {       // one dp anchor on the host (certificate / branch-and-bound)
-    uint32_t slot;           // minimiser identity: dense id (rank of first occurrence among the walk minimisers)
-    uint32_t e0, e1;         // first / last walk entry (phi_ent_t of phi_kernels.h: unsigned, below PHI_MAX_ENTRIES)
 };
 
 // host array that is NOT value-initialised on allocation: the threads that fill it touch its pages
@@ -49,16 +45,6 @@ template <class T> struct PhiRawBuf {
     size_t size() const { return n; }
     T *data() const { return p; }
     T &operator[](size_t i) const { return p[i]; }
-};
-
-// view of host anchors: the pinned download buffer, or an owned vector
-struct PhiAnchorSpan {
-    PhiAnchorHost *p = nullptr;
-    int64_t n = 0;
-    size_t size() const { return (size_t)n; }
-    PhiAnchorHost &operator[](int64_t i) const { return p[i]; }
-    PhiAnchorHost *begin() const { return p; }
-    PhiAnchorHost *end() const { return p + n; }
 };
 
 struct PhiComm;               // phi_comm.hip: the RCCL communicator of a multi-GPU job
@@ -363,7 +349,7 @@ static inline hipError_t phi_memset_sync(phi_ctx *c, void *dst, int v, size_t n)
 // walk of a walk entry
 static inline int32_t phi_entry_walk(const phi_ctx *c, int64_t e)
 {
-    return (int32_t)(std::upper_bound(c->h_walk_off.begin(), c->h_walk_off.end(), e) - c->h_walk_off.begin()) - 1;
+    return phi_walk_of_entry(c->h_walk_off.data(), (int32_t)c->h_walk_off.size() - 1, e);
 }
 
 // phi_solve.cpp: host orchestration of the exact solve on top of the DP kernel

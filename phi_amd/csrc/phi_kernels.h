@@ -27,7 +27,7 @@ static inline int phi_nov_shift(int w)
 }
 #define PHI_STRIPES 256          // counters are striped over 256 cache lines: one hot address
                                  // serialises at ~12 ns per atomic (MI355X_MICROARCH.md "fanin")
-#define PHI_RCAP 32            // DP run-length states 0..31 (an anchor spans <= k-1 <= 31 edges)
+// (PHI_RCAP, the DP's run-length states: phi_dp_flags.h)
 
 // A walk entry is an index into the concatenated walks (walk_off / walk_vtx of phi_set_graph).  Entries are held in
 // 32 bits, UNSIGNED, wherever they are stored (class representatives, record and anchor entries, events, path
@@ -304,8 +304,8 @@ struct PhiDpEventArgs {
     int32_t *row_out; int32_t *rowend_out;   // DP_ROW out: [n_blk * (n_walks + 1)][64] keys at the block's end; best value of a path ending inside
     int32_t *blk_keys_out; int32_t *blk_carry;   // DP_PATH out: [n_blk][64] keys at the block's end; start of the run that carries them (-1: before the block)
 };
-#define PHI_DP_BLOCK_MAX 2048        // steps of a block at most (= the larger ring of tops)
-#define PHI_DP_NEGK (-(1 << 30))      // "no run" in key space
+// (PHI_DP_BLOCK_MAX, the steps of a block at most, and PHI_DP_NEGK, "no run" in key space: phi_dp_flags.h,
+//  shared with the host code of solve_host.h)
 void phi_launch_dp_events(hipStream_t st, const PhiDpEventArgs &A);
 void phi_launch_dp_block_rows(hipStream_t st, const PhiDpEventArgs &A);
 void phi_launch_dp_block_paths(hipStream_t st, const PhiDpEventArgs &A);
