@@ -39,9 +39,6 @@
 #include "phi_wave.h"
 #include "bam_header.h"
 
-#define HIPCHK(call) do { int rc_ = phi_hip_check(c, (call), #call); if (rc_) return rc_; } while (0)
-#define PHICHK(call) do { int rc_ = (call); if (rc_) return rc_; } while (0)
-
 #define BAM_FIXED 36u            // block_size + the 32 fixed bytes: what a record's plausibility is read from
 #define BAM_MIN_STEP 37u         // 4 + 32 + l_read_name >= 1
 #define BAM_HALO 304u            // staged behind a tile: the fixed part and the longest name of a record that starts on its last byte
@@ -531,7 +528,7 @@ int phi_reads_bam_begin(phi_ctx *c, int64_t max_chunk_bytes, int64_t tile_bytes)
     if (tile_bytes < 64 || tile_bytes > BAM_TILE_MAX) return phi_fail(c, PHI_ERR_INVALID, "phi_reads_bam_begin: tile_bytes %lld outside [64, %d]", (long long)tile_bytes, BAM_TILE_MAX);
     HIPCHK(hipSetDevice(c->device));
     PHICHK(phi_sync_check(c));                                // (batches handed over without a wait: their overflow shows here)
-    c->async_batches = false;
+    c->rlog.async_batches = false;
     auto &T = c->bam;
     const uint32_t chunk = (uint32_t)std::min<int64_t>(std::max<int64_t>(max_chunk_bytes, 64), (int64_t)1 << 28);
     // the carry holds what a piece leaves unfinished: a record at most

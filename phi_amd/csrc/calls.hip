@@ -28,9 +28,6 @@
 #include <algorithm>
 #include "phi_ctx.h"
 
-#define HIPCHK(call) do { int rc_ = phi_hip_check(c, (call), #call); if (rc_) return rc_; } while (0)
-#define PHICHK(call) do { int rc_ = (call); if (rc_) return rc_; } while (0)
-
 #define CALLS_TPB 256
 #define CALLS_LANE_BYTES 4                              // output bytes per lane of the fill: one 32-bit store
 #define CALLS_FILL_TILE (CALLS_TPB * CALLS_LANE_BYTES)  // output bytes per workgroup

@@ -20,9 +20,6 @@
 #include "phi_ctx.h"
 #include "dp_steps.h"
 
-#define HIPCHK(call) do { int rc_ = phi_hip_check(c, (call), #call); if (rc_) return rc_; } while (0)
-#define PHICHK(call) do { int rc_ = (call); if (rc_) return rc_; } while (0)
-
 #define CHOP_TILE 4096
 #define CHOP_TPB 256
 

@@ -27,9 +27,6 @@
 #include <vector>
 #include "phi_ctx.h"
 
-#define HIPCHK(call) do { int rc_ = phi_hip_check(c, (call), #call); if (rc_) return rc_; } while (0)
-#define PHICHK(call) do { int rc_ = (call); if (rc_) return rc_; } while (0)
-
 namespace {
 
 #include "edit_band.inc"

@@ -22,9 +22,6 @@
 #include "phi_ctx.h"
 #include "phi_wave.h"
 
-#define HIPCHK(call) do { int rc_ = phi_hip_check(c, (call), #call); if (rc_) return rc_; } while (0)
-#define PHICHK(call) do { int rc_ = (call); if (rc_) return rc_; } while (0)
-
 #define GT_TILE ((int64_t)64 << 10)     // bytes per workgroup of the scan
 #define GT_CAP_DEFAULT (1 << 20)        // candidate W-lines at most (PHI_GFA_SPLIT_CAP)
 

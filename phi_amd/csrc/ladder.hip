@@ -27,9 +27,6 @@
 #include "phi_ctx.h"
 #include "phi_wave.h"
 
-#define HIPCHK(call) do { int rc_ = phi_hip_check(c, (call), #call); if (rc_) return rc_; } while (0)
-#define PHICHK(call) do { int rc_ = (call); if (rc_) return rc_; } while (0)
-
 #define LAD_TPB 256
 #define LAD_MAXL PHI_LADDER_MAX_LEVELS
 #define LAD_ALIGN 256

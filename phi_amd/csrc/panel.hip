@@ -24,9 +24,6 @@
 #include <chrono>
 #include "phi_ctx.h"
 
-#define HIPCHK(call) do { int rc_ = phi_hip_check(c, (call), #call); if (rc_) return rc_; } while (0)
-#define PHICHK(call) do { int rc_ = (call); if (rc_) return rc_; } while (0)
-
 #define PANEL_TILE 4096
 #define PANEL_TPB 256
 

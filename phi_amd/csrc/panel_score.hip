@@ -32,9 +32,6 @@
 #include "phi_wave.h"
 #include "host/panel_choose.h"
 
-#define HIPCHK(call) do { int rc_ = phi_hip_check(c, (call), #call); if (rc_) return rc_; } while (0)
-#define PHICHK(call) do { int rc_ = (call); if (rc_) return rc_; } while (0)
-
 #define SCORE_MAX_BLOCKS 65536
 
 namespace {

@@ -21,9 +21,6 @@
 #include "phi_ctx.h"
 #include "phi_dev.h"
 
-#define HIPCHK(call) do { int rc_ = phi_hip_check(c, (call), #call); if (rc_) return rc_; } while (0)
-#define PHICHK(call) do { int rc_ = (call); if (rc_) return rc_; } while (0)
-
 namespace {
 
 struct RcclApi {

@@ -17,6 +17,7 @@
 #include "phi_kernels.h"
 #include "phi_host_par.h"          // phi_host_threads, phi_parallel_chunks, PhiHostError (no HIP: shared with dp_steps.h)
 #include "solve_host.h"            // PhiAnchorHost, PhiAnchorSpan and the solve's host rules (no HIP: shared with its stand-alone check)
+#include "reads_host.h"            // the read path's host rules: log, overflow list, set, offsets, text sizes (no HIP: shared with its stand-alone check)
 
 // growable device buffer
 struct DevBuf {
@@ -137,7 +138,7 @@ struct phi_ctx {
     DevBuf d_u_keys, d_u_rep, d_u_uid, d_u_replist;   // walk-minimiser table: keys, first record, dense id; dense id -> first record
     DevBuf d_rt;                                      // the same keys with their ids as the read table of the read probes (phi_launch_read_table)
     uint64_t rt_buckets = 0, rt_mask = 0;             // its 32-byte buckets (a power of two) and the mask of the bucket index
-    void *h_stage[2] = {nullptr, nullptr};            // pinned staging buffers of large uploads from pageable memory (phi_abi.hip upload_staged)
+    void *h_stage[2] = {nullptr, nullptr};            // pinned staging buffers of large uploads from pageable memory (dev_mem.hip upload_staged)
     hipEvent_t stage_ev[2] = {nullptr, nullptr};
     DevBuf d_wpre;                                    // per DP run: prefix sums of the anchor weights (dp_events.hip)
     DevBuf d_rowdiag;                                 // class-lane blocks: the rows' own columns (dp_events.hip)
@@ -155,28 +156,43 @@ struct phi_ctx {
     // The reference's read spectrum Sp_R (ILP_index.cpp:622-635) = the hit flags (read hashes that are walk minimisers, d_hit)
     // + the NOVEL read hashes.  The read kernels only LOG the novel ones, coalesced: d_novlog holds 1 << nov_shift entries per
     // 512-window chunk of every batch since the last flush (d_novcnt of them valid), d_ovlist what those entries could not
-    // hold and what the byte-wise routine found.  sp_flush (phi_abi.hip) enters what has been logged into the set d_sp_keys
+    // hold and what the byte-wise routine found.  phi_sp_flush (read_batches.hip) enters what has been logged into the set d_sp_keys
     // when something asks for |Sp_R| or for the list (phi_reads_stats, phi_solve, phi_spectrum_export / _import): once per
     // read set, with every lane of the launch an insert, instead of a dependent atomic behind each probe of the scoring wave.
-    DevBuf d_sp_keys;                                 // the set (open addressing), valid for generation sp_set_gen
-    uint64_t sp_cap = 0;
-    DevBuf d_sp_cnt;                                  // [PHI_STRIPES][8] u64: keys in the set
-    int64_t sp_set_gen = -1;                          // the generation of reads whose hashes the set holds (another one: emptied before use)
-    DevBuf d_novlog, d_novcnt;
-    int32_t nov_shift = 6;
-    int64_t log_chunks = 0, log_done = 0;             // chunks in the log; of those, already in the set
-    int64_t logged_done = 0;                          // the n_logged stripes' sum at the last flush
-    DevBuf d_ovlist;
-    int64_t ov_cap = 0, ov_done = 0, ov_bound = 0;    // overflow list: capacity; entries already in the set; what the batches so far may have sent there at most
-    bool async_batches = false;                       // batches went in without a wait behind them (phi_add_reads_device): their overflow shows at the next check
-    int64_t last_log_chunks = 0;                      // log chunks of the last batch (a replay rewinds the log by them)
+    // The sizes of all three are rules of reads_host.h.
+    struct PhiSpectrumSet {
+        DevBuf d_sp_keys;                             // the set (open addressing), valid for generation sp_set_gen
+        uint64_t sp_cap = 0;
+        DevBuf d_sp_cnt;                              // [PHI_STRIPES][8] u64: keys in the set
+        DevBuf d_export;                              // the set's keys as a list (a set that grows, phi_spectrum_export)
+        int64_t sp_set_gen = -1;                      // the generation of reads whose hashes the set holds (another one: emptied before use)
+        int64_t sp_gen = 0;                           // the generation of reads the context is in
+        void new_generation() { sp_gen++; }           // (the set stays the ended generation's until the new one first needs it)
+        void new_graph() { sp_set_gen = -1; }         // no generation's: emptied before use
+    } spset;
+    struct PhiReadLog {
+        DevBuf d_novlog, d_novcnt;
+        int32_t nov_shift = 6;
+        int64_t log_chunks = 0, log_done = 0;         // chunks in the log; of those, already in the set
+        int64_t logged_done = 0;                      // the n_logged stripes' sum at the last flush
+        int64_t last_log_chunks = 0;                  // log chunks of the last batch (a replay rewinds the log by them)
+        DevBuf d_ovlist;
+        int64_t ov_cap = 0, ov_done = 0, ov_bound = 0;   // overflow list: capacity; entries already in the set; what the batches so far may have sent there at most
+        bool async_batches = false;                   // batches went in without a wait behind them (phi_add_reads_device): their overflow shows at the next check
+        bool next_flag_zeroed = false;                // a launch of this generation has zeroed the overflow counter of the next one
+        DevBuf d_roff_made;                           // offsets made for a batch of one length the kernel does not take without (below 32)
+        // what the log and the list held is in the set (phi_sp_flush): both start over within the generation.  The caller
+        // zeroes the generation's overflow counter on the device.
+        void flushed() { log_chunks = log_done = 0; ov_done = 0; ov_bound = 0; }
+        // a new generation of reads starts both over; its overflow counter is another one (zeroed by the caller unless a launch has)
+        void new_generation() { flushed(); logged_done = 0; last_log_chunks = 0; next_flag_zeroed = false; }
+    } rlog;
     int64_t reads_bases = 0, reads_count = 0;
     int64_t spectrum_override = -1;
-    DevBuf d_rbases, d_roff, d_roff_made, d_export, d_peer_send;
+    DevBuf d_rbases, d_roff, d_peer_send;
     // device scalars: [0] err(u32 in low half) [1] n_bad ... [8..10] three rotating overflow counters (generation g: g % 3)
     DevBuf d_scalars;
     DevBuf d_stripes;                                 // [2][PHI_STRIPES][8] u64: novel hashes logged (with duplicates), emitted records
-    int64_t sp_gen = 0;
     // Double buffers: what a generation of reads accumulates in place (d_hit, d_stripes) exists twice.  phi_reset_reads swaps
     // the two on the host; what the ended generation filled is zeroed by the waves of the next read launch (sketch.hip
     // clean_finish), ready for the generation after: no reset launch.  The log needs none of it: a generation starts it over.
@@ -184,7 +200,6 @@ struct phi_ctx {
         DevBuf hit, stripes;
         bool needs_clean = false;                     // filled by the ended generation, not zeroed yet
     } alt;
-    bool next_flag_zeroed = false;                    // a launch of this generation has zeroed the overflow counter of the next one
 
     uint32_t *h_err = nullptr;                        // pinned copy of the device error word, fetched behind a batch's last kernel
     // ---- reads as raw text (phi_add_reads_text, reads_text.hip): the device finds the records
@@ -356,9 +371,13 @@ static inline int32_t phi_entry_walk(const phi_ctx *c, int64_t e)
 int phi_solve_impl(phi_ctx *c);
 // one batch of reads the device can address; replay: the same batch again after the spectrum set was regrown
 int phi_add_reads_device_impl(phi_ctx *c, const void *d_bases, const void *d_read_off, int64_t n_reads, int64_t n_bases, bool replay);
-// helpers of phi_abi.hip shared with the files that keep a feature's host glue beside its kernels (set_graph.hip, chop.hip,
-// vcf.hip, ladder.hip) and with phi_solve.hip
+// replay of the batch at (d_bases, d_off) while the overflow list of novel hashes ran full under it (read_batches.hip; err = the
+// device error word read behind the batch, after the stream was waited for)
+int replay_if_full(phi_ctx *c, uint32_t err, const void *d_bases, const void *d_off, int64_t n_reads, int64_t n_bases);
+// helpers of phi_abi.hip (errors) and dev_mem.hip (device memory) shared with every unit of host glue
 int phi_fail(phi_ctx *c, int code, const char *fmt, ...);
+#define HIPCHK(call) do { int rc_ = phi_hip_check(c, (call), #call); if (rc_) return rc_; } while (0)
+#define PHICHK(call) do { int rc_ = (call); if (rc_) return rc_; } while (0)
 int phi_dev_ensure(phi_ctx *c, DevBuf &b, size_t bytes);
 int phi_dev_grow_keep(phi_ctx *c, DevBuf &b, size_t bytes, size_t keep);   // grows and KEEPS the first `keep` bytes
 void phi_dev_free(DevBuf &b);                          // to the pool of large buffers or back to the driver (waits for the device)
@@ -378,7 +397,6 @@ enum { S_ERR = 0, S_NBAD = 1, S_BATCHBAD = 2, S_NEMIT = 3, S_FILTERED = 4, S_INM
        S_OVCNT = 8 /* .. 10: three rotating counters of the overflow list, generation g uses g % 3 */, S_N = 11 };
 static inline uint64_t *scalar(phi_ctx *c, int i) { return c->d_scalars.as<uint64_t>() + i; }
 #define STRIPE_BYTES ((size_t)PHI_STRIPES * 8 * 8)
-static inline uint64_t pow2_at_least(uint64_t x) { uint64_t p = 1; while (p < x) p <<= 1; return p; }
 // n bytes from host memory into b (grown to hold them) on `st`, the context's stream if null; not waited for.  256 MB and more
 // from pageable memory go through the context's pinned staging buffers, given back by stage_release.
 int phi_upload_bytes(phi_ctx *c, DevBuf &b, const void *src, size_t bytes, hipStream_t st);
@@ -409,8 +427,8 @@ int phi_dev_poison_fill(void *p, size_t bytes);         // 0 = filled
 static inline int phi_dev_poison(void *p, size_t bytes) { return phi_device_poison < 0 ? 0 : phi_dev_poison_fill(p, bytes); }
 // bam.hip
 void phi_bam_drop(phi_ctx *c);                         // the stream's buffers let go (the context's end)
-// a parked piece's bytes on `device`, landed (phi_abi.hip owns the park): PHI_ERR_INVALID when there is no such piece there
-int phi_text_park_piece_dev(phi_text_park *p, int32_t index, int device, const void **d, int64_t *n);
+// a parked piece's bytes on `device`, landed (text_park.hip owns the park): PHI_ERR_INVALID when there is no such piece there
+int phi_text_park_piece_dev(phi_text_park *p, int32_t index, int device, const void **d, int64_t *n, char *first = nullptr);   // *first (optional): the piece's first byte
 // ladder.hip
 int phi_ladder_collect(phi_ctx *c, const void *d_bases, const void *d_read_off, int64_t n_reads, int64_t n_bases);   // the hook of phi_add_reads_device_impl
 void phi_ladder_drop(phi_ctx *c);                      // store and plan let go (a new graph, the context's end)
@@ -419,7 +437,8 @@ void phi_ladder_detach(phi_ctx *c, phi_ctx::PhiLadder &out);
 void phi_ladder_attach(phi_ctx *c, phi_ctx::PhiLadder &in);
 // a batch whose data stays where it is: scored, waited for, and replayed if the overflow list of novel hashes ran full
 int phi_score_resident_batch(phi_ctx *c, const void *d_bases, const void *d_read_off, int64_t n_reads, int64_t n_bases);
-void phi_pool_flush(int device);                    // the pool of large device buffers let go (phi_abi.hip) back to the driver
+void phi_pool_bypass(bool on);                         // dev_mem.hip: what this thread lets go from now on goes back to the driver, not to the pool (a context that ends)
+void phi_pool_flush(int device);                    // the pool of large device buffers let go (dev_mem.hip) back to the driver
 int phi_hip_check(phi_ctx *c, hipError_t e, const char *what);
 int phi_sync_check(phi_ctx *c);
 // PHI_ERR_STATE naming the scout when the context holds one (phi_scout_graph: an index without the DP), else PHI_OK

@@ -44,9 +44,6 @@
 #include "phi_ctx.h"
 #include "phi_dev.h"
 
-#define HIPCHK(call) do { int rc_ = phi_hip_check(c, (call), #call); if (rc_) return rc_; } while (0)
-#define PHICHK(call) do { int rc_ = (call); if (rc_) return rc_; } while (0)
-
 #define PHI_IPC_MAX 16
 #define PHI_IPC_MAGIC 0x50484969u
 #define PHI_IPC_FLAG_SLOTS 4                  // a peer is at most one step ahead: the flag of step s lives in slot s % 4
@@ -227,7 +224,7 @@ void ipc_release(phi_ctx *c, PhiIpc *g)
 
 }  // namespace
 
-// (phi_abi.hip) everything that looks at the hit vector comes through phi_flush_reset: the context's stream waits for the last gather
+// (read_batches.hip) everything that looks at the hit vector comes through phi_flush_reset: the context's stream waits for the last gather
 int phi_ipc_wait_pending(phi_ctx *c)
 {
     PhiIpc *g = c->ipc;
@@ -238,11 +235,11 @@ int phi_ipc_wait_pending(phi_ctx *c)
     return PHI_OK;
 }
 
-// (phi_abi.hip phi_reset_reads) two resets with no read launch in between: the hit vector that comes to the front is zeroed
+// (read_batches.hip phi_reset_reads) two resets with no read launch in between: the hit vector that comes to the front is zeroed
 // by a launch of its own, which has no wave to look at the flags -- everything issued so far is waited for instead
 int phi_ipc_before_generation(phi_ctx *c, int64_t) { return phi_ipc_wait_pending(c); }
 
-// (phi_abi.hip, every read launch of a context in a group) what the launch's waves publish and what they make sure of before
+// (read_batches.hip, every read launch of a context in a group) what the launch's waves publish and what they make sure of before
 // they zero the hit vector of read set gen - 3: this rank's last exchange of a read set <= gen - 2 has been gathered
 void phi_ipc_launch_args(phi_ctx *c, PhiSketchArgs &A)
 {
@@ -251,7 +248,7 @@ void phi_ipc_launch_args(phi_ctx *c, PhiSketchArgs &A)
     A.ipc_mb = g->mbox;
     A.ipc_scored = g->step;
     A.ipc_need = 0;
-    for (int64_t h = c->sp_gen - 2; h >= c->sp_gen - 3 && h >= 0; h--)
+    for (int64_t h = c->spset.sp_gen - 2; h >= c->spset.sp_gen - 3 && h >= 0; h--)
         if (g->gen_tag[h % PHI_HIT_RING] == h) { A.ipc_need = g->step_of_gen[h % PHI_HIT_RING]; break; }
     if (g->shared_device && A.q_clean && A.ipc_need) {
         // Ranks that SHARE a GPU (tests, rehearsals): scoring waves that wait inside the kernel would hold the very wave slots
@@ -376,7 +373,7 @@ int phi_ipc_allreduce_hits(phi_ctx *c)
     HIPCHK(hipSetDevice(c->device));
     const int64_t n_words = c->n_unique / 8 + 1;               // (the vectors are allocated in whole words)
     g->step++;
-    g->step_of_gen[c->sp_gen % PHI_HIT_RING] = g->step; g->gen_tag[c->sp_gen % PHI_HIT_RING] = c->sp_gen;
+    g->step_of_gen[c->spset.sp_gen % PHI_HIT_RING] = g->step; g->gen_tag[c->spset.sp_gen % PHI_HIT_RING] = c->spset.sp_gen;
     IpcPeerArgs P{};
     int np = 0;
     for (int r = 0; r < g->n; r++) {

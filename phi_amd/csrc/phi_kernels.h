@@ -1,4 +1,4 @@
-// phi_kernels.h -- launch interface between the C-ABI layer (phi_abi.hip, set_graph.hip, phi_solve.hip and the host glue kept
+// phi_kernels.h -- launch interface between the C-ABI layer (phi_abi.hip, read_batches.hip, text_stream.hip, set_graph.hip, phi_solve.hip and the host glue kept
 // beside the kernels of chop.hip, vcf.hip, ladder.hip) and the kernels.
 #pragma once
 #include <stdint.h>
@@ -77,7 +77,7 @@ struct PhiSketchArgs {
     // chunk log_base + i of the log, written in order by the wave that owns the chunk (coalesced); nov_cnt = how many.
     // What a chunk (pooled kernel: a wave) has beyond its entries, and what the byte-wise routine finds, goes to
     // ov_list[atomicAdd(ov_count)]; a full list raises PHI_KERR_TABLE_FULL (the host grows it and replays the batch).
-    // The read-spectrum set is made from these when |Sp_R| is asked for (phi_abi.hip sp_flush, table.hip).
+    // The read-spectrum set is made from these when |Sp_R| is asked for (read_batches.hip phi_sp_flush, table.hip).
     uint64_t *nov_log; uint16_t *nov_cnt; int64_t log_base; int32_t nov_shift;
     uint64_t *ov_list; unsigned long long *ov_count; int64_t ov_cap;
     // PHI_MODE_PROBE reads ASCII: the 2-bit pack, the bases outside ACGTacgt and the read-start bitmap of a chunk

@@ -37,9 +37,6 @@
 #include "phi_ctx.h"
 #include "phi_dev.h"
 
-#define HIPCHK(call) do { int rc_ = phi_hip_check(c, (call), #call); if (rc_) return rc_; } while (0)
-#define PHICHK(call) do { int rc_ = (call); if (rc_) return rc_; } while (0)
-
 // The walk entries as the solve's host code reads them: from the context's host copy, or -- a chromosome-scale graph keeps none
 // (phi_set_graph) -- from the device copy: single entries for the backtrack, whole stretches for the decoded path.
 static bool have_host_walks(const phi_ctx *c) { return (int64_t)c->h_walk_vtx.size() == c->n_entries; }

@@ -15,9 +15,6 @@
 #include "phi_kernels.h"
 #include "phi_wave.h"
 
-#define HIPCHK(call) do { int rc_ = phi_hip_check(c, (call), #call); if (rc_) return rc_; } while (0)
-#define PHICHK(call) do { int rc_ = (call); if (rc_) return rc_; } while (0)
-
 // ------------------------------------------------------------------ three phases, 1024 items per workgroup
 // block sums -> their scan in one workgroup (phi_scan_tiles_kernel) -> every workgroup again, from its offset.
 // Workgroup n / 1024 owns off[n], the total: one workgroup more than the items need when n is a multiple of 1024.

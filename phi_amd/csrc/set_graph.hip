@@ -11,9 +11,6 @@
 #include "phi_dev.h"
 #include "dp_steps.h"
 
-#define HIPCHK(call) do { int rc_ = phi_hip_check(c, (call), #call); if (rc_) return rc_; } while (0)
-#define PHICHK(call) do { int rc_ = (call); if (rc_) return rc_; } while (0)
-
 // The read table of the read probes (phi_launch_read_table) from the walk-minimiser table's keys and dense ids.  At most
 // 3/16 key per bucket: a read probe then takes a second trip when the key it looks for sits past its home bucket (0.25 %
 // of the keys at C2's 0.127 a bucket, 0.54 % at 3/16) or when a novel hash's home bucket has overflowed (3e-4 / 1e-3 of
@@ -633,12 +630,11 @@ static int late_uploads_and_events(SetGraph &S)
 static void reset_read_state(phi_ctx *c)
 {
     c->reads_bases = 0; c->reads_count = 0; c->spectrum_override = -1;
-    c->sp_set_gen = -1; c->log_chunks = c->log_done = 0; c->logged_done = 0; c->ov_done = 0; c->ov_bound = 0; c->async_batches = false;
+    c->spset.new_graph(); c->rlog.new_generation(); c->rlog.async_batches = false;   // (set_graph zeroed all scalars, the overflow counters among them)
     c->walks_on_device = false;                                // (consumed: a later phi_set_graph brings its own walks)
-    c->nov_shift = phi_nov_shift(c->w);
-    if (const char *e = getenv("PHI_NOV_SHIFT")) c->nov_shift = std::max(0, std::min(9, atoi(e)));   // tests: chunk logs of a few entries, so that ordinary reads spill into the overflow list
+    c->rlog.nov_shift = phi_nov_shift(c->w);
+    if (const char *e = getenv("PHI_NOV_SHIFT")) c->rlog.nov_shift = std::max(0, std::min(9, atoi(e)));   // tests: chunk logs of a few entries, so that ordinary reads spill into the overflow list
     c->alt.needs_clean = false;
-    c->next_flag_zeroed = false;                               // (set_graph zeroed all scalars, the overflow counters among them)
 }
 
 // the body of phi_set_graph, and of phi_set_graph_chopped once the graph is chopped: the schedule of the stages above

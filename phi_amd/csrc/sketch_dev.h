@@ -143,7 +143,7 @@ __device__ __forceinline__ MinEnt take_right(MinEnt a, MinEnt b) { return (b.v <
 // that derive from it (ILP_index.cpp:622-641, 738-743, 883).  They are not entered into a set here (round 3: an atomicCAS
 // per novel hash into a 64-MB table, a second dependent round trip behind the probe and ~100 bytes of write traffic per
 // 8-byte key: 45 % of the launch on long noisy reads): the wave appends them to its LOG, coalesced, and the set is made
-// from the log once, when somebody asks for |Sp_R| (phi_abi.hip sp_flush).
+// from the log once, when somebody asks for |Sp_R| (read_batches.hip phi_sp_flush).
 // The table is the read table of table.hip (phi_launch_read_table): aligned 32-byte buckets of two (key, id) slots, home
 // bucket h & bmask.  A lookup loads its whole home bucket -- both slots, keys and ids, issued before one wait -- and is done
 // unless the bucket's OVERFLOWED flag says that a key whose home it is lies in a later bucket (3e-4 of the buckets at

@@ -21,9 +21,6 @@
 #include <algorithm>
 #include "phi_ctx.h"
 
-#define HIPCHK(call) do { int rc_ = phi_hip_check(c, (call), #call); if (rc_) return rc_; } while (0)
-#define PHICHK(call) do { int rc_ = (call); if (rc_) return rc_; } while (0)
-
 #define VCF_TPB 256
 #define VCF_TILE (VCF_TPB * 16)
 #define VCF_MAX_WALK 4096

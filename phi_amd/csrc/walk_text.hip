@@ -23,9 +23,6 @@
 #include "phi_dev.h"
 #include "phi_wave.h"
 
-#define HIPCHK(call) do { int rc_ = phi_hip_check(c, (call), #call); if (rc_) return rc_; } while (0)
-#define PHICHK(call) do { int rc_ = (call); if (rc_) return rc_; } while (0)
-
 namespace {
 
 __device__ __forceinline__ bool is_step(unsigned c) { return c == '>' || c == '<'; }

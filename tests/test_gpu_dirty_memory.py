@@ -1,5 +1,5 @@
 """No result may depend on what device memory held before.  Every kernel test of the suite starts from a fresh context on
-memory the driver has cleared; in real use a buffer comes back from the pool of phi_abi.hip with an earlier owner's contents, or
+memory the driver has cleared; in real use a buffer comes back from the pool of dev_mem.hip with an earlier owner's contents, or
 stays with its context from a larger input to a smaller one.  Here the battery of tests/dirty_battery.py -- the smallest shapes
 that still reach every kernel family, each case asserted against its CPU reference inside the child -- runs
 
