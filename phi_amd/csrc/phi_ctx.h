@@ -138,6 +138,16 @@ struct phi_ctx {
     DevBuf d_u_keys, d_u_rep, d_u_uid, d_u_replist;   // walk-minimiser table: keys, first record, dense id; dense id -> first record
     DevBuf d_rt;                                      // the same keys with their ids as the read table of the read probes (phi_launch_read_table)
     uint64_t rt_buckets = 0, rt_mask = 0;             // its 32-byte buckets (a power of two) and the mask of the bucket index
+    // The k-mer table (set_graph.hip build_kmer_table; k <= 31): the same bucket format and dense ids under the keys
+    // phi_kmer_mix(canonical k-mer) of the walk minimisers, for the clean waves of the 150-bp read kernel (sketch_rounds_kmer.inc).
+    // kt_mask = 0: this graph has none (k = 32 and beyond, or two walk k-mers of one hash).
+    DevBuf d_kt;
+    uint64_t kt_buckets = 0, kt_mask = 0;
+    // The batches that take it: those whose waves are all resident at once (seven a SIMD).  Such a launch lasts as long as one
+    // wave's dependent chain, which the route shortens (C2: 10.9 -> 10.4 us); a launch of many rounds of waves is bound by the
+    // table's random loads, and there the route measured 3 - 9 % SLOWER in spite of 30 % fewer vector instructions (C3, C5s:
+    // profiles/kmer_keys_bench_ab.json).  PHI_SKETCH_KMER_KEYS=0: no batch; =2: every batch.
+    int64_t kt_max_chunks = 0;
     void *h_stage[2] = {nullptr, nullptr};            // pinned staging buffers of large uploads from pageable memory (dev_mem.hip upload_staged)
     hipEvent_t stage_ev[2] = {nullptr, nullptr};
     DevBuf d_wpre;                                    // per DP run: prefix sums of the anchor weights (dp_events.hip)

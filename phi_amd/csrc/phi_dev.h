@@ -218,3 +218,42 @@ PHI_HD uint64_t phi_kmer_hash(uint64_t val, int k)
     }
     return phi_murmur_lanes(e[0], e[1], e[2], e[3], k);
 }
+
+// ---- k-mer keys: the walk-minimiser lookup of a clean 150-bp wave needs an injective key, not MurmurHash3.
+// phi_kmer_mix is a bijection on 64 bits -- xor-shift, one multiply by an odd constant, xor-shift: ten vector instructions --
+// whose low bits (the home bucket is key & bmask) take in every bit of a value below 2^62: the first shift folds bits 31 .. 61
+// onto the low word, the multiply carries the low word upwards, the last shift folds the high word back down.  The value
+// that maps to PHI_EMPTY_KEY is 0x66c88cc3cd911987 >= 2^62: no k-mer of up to 31 bases maps to the sentinel.
+#define PHI_KMER_MIX_MUL 0x9E3779B97F4A7C15ull
+#define PHI_KMER_MIX_INV 0xF1DE83E19937733Dull       // its inverse modulo 2^64
+PHI_HD uint64_t phi_kmer_mix(uint64_t v)
+{
+    v ^= v >> 31;
+    v = phi_mul64(v, PHI_KMER_MIX_MUL);
+    return v ^ (v >> 32);
+}
+PHI_HD uint64_t phi_kmer_unmix(uint64_t y)
+{
+    y ^= y >> 32;
+    y = y * PHI_KMER_MIX_INV;
+    return y ^ (y >> 31) ^ (y >> 62);
+}
+
+// What the flush makes of one logged novel k-mer v with h = phi_kmer_hash(v, k): 0 = h enters the set, otherwise the bits
+// of the device error word to raise.  Only a MurmurHash3 collision between different k-mers can make the k-mer route differ
+// from the reference's result, and every such case is reported:
+//  - h is the table sentinel (the hash route raises the same);
+//  - in_walks: h is a walk minimiser's hash, yet the k-mer is none (it would have hit);
+//  - have_prev: the entry before it in its chunk's log is another k-mer (vp) of the same hash (hp) -- the reference drops a
+//    window whose hash equals the window's before it.
+// (the same bits as in phi_kernels.h's list)
+#define PHI_KERR_SENTINEL 1u
+#define PHI_KERR_HASH_COLLISION 128u
+PHI_HD uint32_t phi_kmer_flush_rule(uint64_t h, uint64_t v, bool have_prev, uint64_t hp, uint64_t vp, bool in_walks)
+{
+    if (h == PHI_EMPTY_KEY) return PHI_KERR_SENTINEL;
+    uint32_t e = 0;
+    if (in_walks) e |= PHI_KERR_HASH_COLLISION;
+    if (have_prev && hp == h && vp != v) e |= PHI_KERR_HASH_COLLISION;
+    return e;
+}

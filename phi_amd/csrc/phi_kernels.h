@@ -51,6 +51,7 @@ enum { PHI_MODE_COUNT = 0, PHI_MODE_WRITE = 1, PHI_MODE_PROBE = 2 };
 #define PHI_KERR_CSR_ID 32u      // a minimiser id outside the table (internal error)
 #define PHI_KERR_DP_QUEUE 16u    // event DP: more live young runs on a lane than its queue holds
 #define PHI_KERR_DP_CLASSES 64u  // block DP on class lanes: a block holds more than 64 classes of walks
+#define PHI_KERR_HASH_COLLISION 128u   // k-mer keys: two different k-mers of one MurmurHash3 value met (phi_dev.h phi_kmer_flush_rule)
 
 struct PhiSketchArgs {
     const uint64_t *words;                 // packed bases (+2 padding words)
@@ -100,7 +101,12 @@ struct PhiSketchArgs {
     // gather ipc_need has ended (by then every peer has read that vector; true long before, except when a peer lags)
     unsigned long long *ipc_mb; unsigned long long ipc_scored, ipc_need;
     uint64_t *q_hit_words; int64_t q_n_hit_words; uint64_t *q_stripes; int64_t q_n_stripe_words;
+    // the k-mer table (null: none): the read table's bucket format, keys phi_kmer_mix(canonical k-mer) of the walk minimisers,
+    // the same dense ids.  A clean wave of phi_sketch_winfix_kernel probes it by k-mer, logs novel K-MERS and tags its
+    // chunk by PHI_NOV_KMERS in nov_cnt; the flush hashes them (sketch_rounds_kmer.inc, table.hip)
+    const uint64_t *k_rt; uint64_t k_bmask;
 };
+#define PHI_NOV_KMERS 0x8000u    // nov_cnt: the chunk's entries are k-mers, not hashes (counts are at most 512)
 
 // sketch.hip
 void phi_launch_pack_ascii(hipStream_t st, const uint8_t *bases, int64_t n, uint64_t *words, int64_t n_words,
@@ -143,9 +149,21 @@ void phi_launch_iota_i64(hipStream_t st, int64_t *p, int64_t n, int64_t step);  
 void phi_launch_spectrum_insert(hipStream_t st, const uint64_t *hashes, int64_t n, uint64_t *sp_keys,
                                 uint64_t sp_mask, unsigned long long *sp_count, const uint64_t *u_keys, uint64_t u_mask,
                                 const uint32_t *u_uid, uint8_t *hit, uint32_t *err);
-// the logged novel hashes of chunks [c_lo, c_hi) (1 << shift entries each, cnt[c] of them valid) into the spectrum set
+// the logged novel hashes of chunks [c_lo, c_hi) (1 << shift entries each, cnt[c] of them valid) into the spectrum set.  A
+// chunk tagged PHI_NOV_KMERS holds k-mers: hashed here (k), checked by phi_kmer_flush_rule against the walk-minimiser table
+// (u_keys, u_mask) and the entry before
 void phi_launch_spectrum_flush(hipStream_t st, const uint64_t *nov_log, const uint16_t *nov_cnt, int64_t c_lo, int64_t c_hi, int32_t shift,
-                               uint64_t *sp_keys, uint64_t sp_mask, unsigned long long *sp_count, uint32_t *err);
+                               uint64_t *sp_keys, uint64_t sp_mask, unsigned long long *sp_count, int32_t k, const uint64_t *u_keys,
+                               uint64_t u_mask, uint32_t *err);
+// k-mer keys of the walk minimisers: kkeys[slot] (slots of the walk-minimiser table, PHI_EMPTY_KEY before) = phi_kmer_mix of
+// the canonical k-mer under class record i at class-space base cls_base[rec_cls[i]] + cls_left + rec_rel[i], for EVERY class
+// record.  ctr[0] += records whose k-mer holds a base outside ACGTacgt (skipped), ctr[1] += records whose k-mer does not
+// hash to rec_hash[i] (internal error), ctr[2] += records that met another k-mer in their slot (a hash collision)
+void phi_launch_kmer_keys(hipStream_t st, const int32_t *rec_cls, const int32_t *rec_rel, const uint64_t *rec_hash, const uint32_t *rec_slot,
+                          int64_t n_rec, const int64_t *cls_base, const uint8_t *cls_left, const uint64_t *words, const uint32_t *badbits,
+                          int32_t k, uint64_t *kkeys, unsigned long long *ctr);
+// *n_out += buckets of a read table flagged PHI_RT_OVERFLOWED
+void phi_launch_rt_overflowed(hipStream_t st, const uint64_t *rt, int64_t n_buckets, unsigned long long *n_out);
 // *n_out += number of non-zero bytes of flags[0..n)
 void phi_launch_count_flags(hipStream_t st, const uint8_t *flags, int64_t n, unsigned long long *n_out);
 // compact the occupied slots of the spectrum set into a list; *n_out receives the count

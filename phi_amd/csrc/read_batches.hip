@@ -119,7 +119,8 @@ int phi_sp_flush(phi_ctx *c, uint64_t *n_in_set)
         PHICHK(sp_reserve(c, in_set, more));
         if (L.log_chunks > L.log_done)
             phi_launch_spectrum_flush(c->stream, L.d_novlog.as<uint64_t>(), L.d_novcnt.as<uint16_t>(), L.log_done, L.log_chunks, L.nov_shift,
-                                      S.d_sp_keys.as<uint64_t>(), S.sp_cap - 1, S.d_sp_cnt.as<unsigned long long>(), (uint32_t *)scalar(c, S_ERR));
+                                      S.d_sp_keys.as<uint64_t>(), S.sp_cap - 1, S.d_sp_cnt.as<unsigned long long>(), c->k, c->d_u_keys.as<uint64_t>(),
+                                      c->u_cap - 1, (uint32_t *)scalar(c, S_ERR));
         if ((int64_t)ov_now > L.ov_done)
             phi_launch_spectrum_insert(c->stream, L.d_ovlist.as<uint64_t>() + L.ov_done, (int64_t)ov_now - L.ov_done, S.d_sp_keys.as<uint64_t>(),
                                        S.sp_cap - 1, S.d_sp_cnt.as<unsigned long long>(), nullptr, 0, nullptr, nullptr, (uint32_t *)scalar(c, S_ERR));
@@ -157,6 +158,7 @@ int phi_sync_check(phi_ctx *c)
     const uint32_t err = (uint32_t)s[S_ERR];
     if (err & PHI_KERR_TABLE_FULL) return phi_fail(c, PHI_ERR_OVERFLOW, "open-addressed table overflow (probe bound %d), or the overflow list of novel read hashes ran full under a batch handed over with phi_add_reads_device", PHI_MAX_PROBE);
     if (err & PHI_KERR_SENTINEL) return phi_fail(c, PHI_ERR_UNSUPPORTED, "a minimiser hashes to UINT64_MAX (table sentinel)");
+    if (err & PHI_KERR_HASH_COLLISION) return phi_fail(c, PHI_ERR_UNSUPPORTED, "two different k-mers of the reads and walks share a MurmurHash3 value: the k-mer route cannot reproduce the reference's result for this read set (set PHI_SKETCH_KMER_KEYS=0 and run again)");
     return PHI_OK;
 }
 
@@ -244,6 +246,13 @@ int phi_add_reads_device_impl(phi_ctx *c, const void *d_bases, const void *d_rea
     A.u_rt = c->d_rt.as<uint64_t>(); A.u_bmask = c->rt_mask;
     A.hit = c->d_hit.as<uint8_t>();
     A.err = (uint32_t *)scalar(c, S_ERR);
+    if (c->kt_mask) {
+        // the k-mer route of the clean 150-bp waves, for a batch whose waves are resident at once (phi_ctx.h kt_max_chunks;
+        // PHI_SKETCH_KMER_KEYS=0: the hash route for every batch, =2: the k-mer route for every batch)
+        const char *e = getenv("PHI_SKETCH_KMER_KEYS");
+        const int mode = e ? atoi(e) : 1;
+        if (mode >= 2 || (mode == 1 && n_log_chunks <= c->kt_max_chunks)) { A.k_rt = c->d_kt.as<uint64_t>(); A.k_bmask = c->kt_mask; }
+    }
     A.nov_log = L.d_novlog.as<uint64_t>(); A.nov_cnt = L.d_novcnt.as<uint16_t>(); A.log_base = L.log_chunks; A.nov_shift = L.nov_shift;
     A.ov_list = L.d_ovlist.as<uint64_t>(); A.ov_cap = L.ov_cap;
     A.ov_count = (unsigned long long *)scalar(c, S_OVCNT + (int)(c->spset.sp_gen % 3));

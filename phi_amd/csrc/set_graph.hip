@@ -41,6 +41,65 @@ static int build_read_table(phi_ctx *c)
     return PHI_OK;
 }
 
+// The k-mer table beside it (phi_ctx.h d_kt): for every class record the canonical k-mer under it, from the class-space
+// text, checked against the record's hash; its phi_kmer_mix under the record's slot of the walk-minimiser table; then the
+// read table's build over those keys and the same dense ids, at the read table's buckets.  A record whose k-mer holds a base
+// outside ACGTacgt has no 2-bit value and is skipped: no clean read carries its k-mer.  Two records of one hash and
+// different k-mers -- a MurmurHash3 collision inside the graph -- leave the graph without a k-mer table: the reads then take
+// the hash route, which treats the two as the reference does.  k <= 31: a 32-mer has no value to spare for the sentinel.
+static int build_kmer_table(phi_ctx *c)
+{
+    c->kt_buckets = 0; c->kt_mask = 0;
+    if (c->k > 31 || c->n_rec <= 0 || c->n_unique <= 0) return PHI_OK;
+    PhiStageTimer tg("set_graph");
+    DevBuf kkeys, ctr;
+    PhiDevGuard guard{{&kkeys, &ctr}};
+    PHICHK(phi_dev_ensure(c, kkeys, c->u_cap * 8));
+    PHICHK(phi_dev_ensure(c, ctr, 5 * 8));
+    phi_launch_fill_u64(c->stream, kkeys.as<uint64_t>(), (int64_t)c->u_cap, PHI_EMPTY_KEY);
+    HIPCHK(hipMemsetAsync(ctr.p, 0, 5 * 8, c->stream));
+    phi_launch_kmer_keys(c->stream, c->d_rec_cls.as<int32_t>(), c->d_rec_rel.as<int32_t>(), c->d_rec_hash.as<uint64_t>(), c->d_rec_slot.as<uint32_t>(),
+                         c->n_rec, c->d_cls_base.as<int64_t>(), c->d_cls_left.as<uint8_t>(), c->d_wwords.as<uint64_t>(), c->d_wbad.as<uint32_t>(),
+                         c->k, kkeys.as<uint64_t>(), ctr.as<unsigned long long>());
+    uint64_t n[5] = {0, 0, 0, 0, 0};
+    HIPCHK(phi_copy_sync(c, n, ctr.p, 3 * 8, hipMemcpyDeviceToHost));
+    if (n[1]) return phi_fail(c, PHI_ERR_DEVICE, "k-mer table: %llu class records whose k-mer in class space does not hash to the record's hash (internal error)", (unsigned long long)n[1]);
+    if (n[2]) {
+        if (tg.on) fprintf(stderr, "[phi timing] set_graph: %llu walk minimisers share a hash with another k-mer: no k-mer table for this graph\n", (unsigned long long)n[2]);
+        return PHI_OK;
+    }
+    uint64_t nb = c->rt_buckets;
+    uint32_t err0 = 0;                                  // (a table overflow raised before this one: reported by phi_sync_check)
+    HIPCHK(phi_copy_sync(c, &err0, scalar(c, S_ERR), 4, hipMemcpyDeviceToHost));
+    if (err0 & PHI_KERR_TABLE_FULL) return PHI_OK;
+    for (int attempt = 0;; attempt++) {
+        PHICHK(phi_dev_ensure(c, c->d_kt, nb * 32));
+        phi_launch_read_table(c->stream, kkeys.as<uint64_t>(), c->d_u_uid.as<uint32_t>(), (int64_t)c->u_cap, c->d_kt.as<uint64_t>(), (int64_t)nb,
+                              (uint32_t *)scalar(c, S_ERR));
+        uint32_t err = 0;
+        HIPCHK(phi_copy_sync(c, &err, scalar(c, S_ERR), 4, hipMemcpyDeviceToHost));
+        if (!(err & PHI_KERR_TABLE_FULL)) break;
+        if (attempt >= 40) return phi_fail(c, PHI_ERR_OVERFLOW, "k-mer table overflow at %llu buckets (internal error)", (unsigned long long)nb);
+        err &= ~PHI_KERR_TABLE_FULL;
+        HIPCHK(phi_copy_sync(c, scalar(c, S_ERR), &err, 4, hipMemcpyHostToDevice));
+        nb *= 2;
+    }
+    c->kt_buckets = nb; c->kt_mask = nb - 1;
+    int n_cu = 0;
+    HIPCHK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->device));
+    c->kt_max_chunks = (int64_t)n_cu * 4 * 7;           // (waves resident at once: four SIMDs a CU, seven waves of the read kernel each)
+    if (tg.on) {
+        phi_launch_rt_overflowed(c->stream, c->d_rt.as<uint64_t>(), (int64_t)c->rt_buckets, ctr.as<unsigned long long>() + 3);
+        phi_launch_rt_overflowed(c->stream, c->d_kt.as<uint64_t>(), (int64_t)nb, ctr.as<unsigned long long>() + 4);
+        HIPCHK(phi_copy_sync(c, n + 3, ctr.as<uint64_t>() + 3, 2 * 8, hipMemcpyDeviceToHost));
+        fprintf(stderr, "[phi timing] set_graph: k-mer table of %llu buckets (%.1f MB) beside the read table's %llu; %llu class records with a base outside ACGT skipped; "
+                        "OVERFLOWED buckets: read table %.2e, k-mer table %.2e\n", (unsigned long long)nb, (double)nb * 32 / 1e6, (unsigned long long)c->rt_buckets,
+                (unsigned long long)n[0], (double)n[3] / (double)c->rt_buckets, (double)n[4] / (double)nb);
+        tg.lap("[gpu thread]   k-mer table");
+    }
+    return PHI_OK;
+}
+
 // Classes of walk entries with equal context, their sketch in class space and the class records
 // (contexts.hip).  Leaves d_vlen, d_ent_cls, d_cls_*, d_rec_{hash,cls,rel,e0,e1}, n_cls, n_rec,
 // h_walk_base / walk_bases.  Runs on the context's stream; called by the GPU thread of phi_set_graph.
@@ -496,6 +555,7 @@ static int gpu_thread(SetGraph &S)
     tg.lap("[gpu thread] classes + class sketch");
     PHICHK(build_minimizer_table(c));
     PHICHK(build_read_table(c));
+    PHICHK(build_kmer_table(c));
     // records of each walk ("Number of Minimizers", ILP_index.cpp:563) = sum over its entries of their class's records
     PHICHK(phi_dev_ensure(c, c->d_list2, (size_t)(S.n_walks + 1) * 8));
     HIPCHK(hipMemsetAsync(c->d_list2.p, 0, (size_t)(S.n_walks + 1) * 8, c->stream));

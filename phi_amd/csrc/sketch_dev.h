@@ -160,9 +160,11 @@ __device__ __forceinline__ void rt_bucket(const uint64_t *rt, uint64_t b, ulongl
     s1 = *reinterpret_cast<const uint3 *>(p + 2);                // key 1 (x, y), id 1 (z): the word after it carries nothing
     asm volatile("" : "+v"(s0.x), "+v"(s0.y), "+v"(s1.x), "+v"(s1.y), "+v"(s1.z));
 }
+// (SENT = false: the key cannot be the sentinel -- phi_kmer_mix of a k-mer, phi_dev.h)
+template <bool SENT = true>
 __device__ __forceinline__ bool probe_table(const ProbeArgs &A, uint64_t h)
 {
-    if (h == PHI_EMPTY_KEY) { atomicOr(A.err, PHI_KERR_SENTINEL); return false; }
+    if (SENT && h == PHI_EMPTY_KEY) { atomicOr(A.err, PHI_KERR_SENTINEL); return false; }
     uint64_t b = h & A.u_bmask;
     ulonglong2 s0;
     uint3 s1;

@@ -11,7 +11,8 @@
 //    one v_min_f64, stored at constant offsets from one of four addresses;
 //  - every window of a lane exists (V = 96 = 8 G): phase 3 has no `imax`.
 // Phases 2 - 5, the byte-wise routine for bases outside ACGTacgt, the log, clean_finish and the epilogue are those of
-// phi_sketch_win_kernel, and so are its outputs.
+// phi_sketch_win_kernel, and so are its outputs -- except that a clean wave (every base ACGTacgt) of a graph with a k-mer table
+// (A.k_rt) probes by k-mer and logs novel k-mers, without MurmurHash3: sketch_rounds_kmer.inc.
 #include "sketch_dev.h"
 
 // reverse complement of 16 bases in 2 bits (first base in the top bits)
@@ -97,6 +98,7 @@ __global__ void __launch_bounds__(TPB, 7) phi_sketch_winfix_kernel(PhiSketchArgs
         s_code[lane] = code;
         chunk_bad = __ballot(lane < 62 && bad != 0) != 0ull;   // wave-uniform
     }
+    const bool kmer_keys = !chunk_bad && A.k_rt != nullptr;   // wave-uniform: the rounds of sketch_rounds_kmer.inc
     wave_sync();
 
     // ---- phase 1: k-mers P j .. P j + P - 1 of the lane's read (bases P j .. P j + P + k - 2), canonical, to slots
@@ -191,7 +193,7 @@ __global__ void __launch_bounds__(TPB, 7) phi_sketch_winfix_kernel(PhiSketchArgs
                 }
             }
         }
-        if (coff == 0 && cflag) s_meta[0] = (MetaT)((uint32_t)(lane * Q + __ffs((int)cflag) - 2) | ITEM_NOEMIT);
+        if (coff == 0 && cflag && !kmer_keys) s_meta[0] = (MetaT)((uint32_t)(lane * Q + __ffs((int)cflag) - 2) | ITEM_NOEMIT);
     }
     wave_sync();
 #undef SQ
@@ -199,7 +201,13 @@ __global__ void __launch_bounds__(TPB, 7) phi_sketch_winfix_kernel(PhiSketchArgs
     // ---- phases 4 + 5, as in base space
     int n_emit = 0, n_log = 0, n_nov_slow = 0;
     const int64_t out_base = 0;
+    bool hashed = !kmer_keys;                            // wave-uniform: the chunk's log holds hashes
+    if (!hashed) {
+#include "sketch_rounds_kmer.inc"
+    }
+    if (hashed) {
 #include "sketch_rounds.inc"
+    }
 
     if (chunk_bad) {
         // (the wave's region from a scalar: its vector address would be one register too many around the byte-wise routine)
@@ -217,7 +225,7 @@ __global__ void __launch_bounds__(TPB, 7) phi_sketch_winfix_kernel(PhiSketchArgs
         if (PA->q_clean) clean_finish(*PA, chunk, (int64_t)gridDim.x * (TPB / 64), lane);
         if (lane == 0) {
             const int cap = 1 << PA->nov_shift;
-            PA->nov_cnt[PA->log_base + chunk] = (uint16_t)(n_log < cap ? n_log : cap);
+            PA->nov_cnt[PA->log_base + chunk] = (uint16_t)((uint32_t)(n_log < cap ? n_log : cap) | (hashed ? 0u : PHI_NOV_KMERS));
             const int n_nov_wave = n_log + n_nov_slow;
             const int stripe = (int)(chunk & (PHI_STRIPES - 1)) * 8;
             if (n_nov_wave && PA->n_logged) atomicAdd(PA->n_logged + stripe, (unsigned long long)n_nov_wave);

@@ -272,17 +272,54 @@ void phi_launch_spectrum_insert(hipStream_t st, const uint64_t *hashes, int64_t 
 // The read-spectrum set from the log of novel hashes (sketch.hip): thread -> entry (chunk, i); every lane of a wave
 // that holds a logged hash inserts it, the wave adds its new entries to a striped counter.  All lanes of the launch are
 // inserts (in the sketch kernel an insert was a lane's second dependent round trip behind its table probe).
+// A chunk tagged PHI_NOV_KMERS (a clean wave of phi_sketch_winfix_kernel, sketch_rounds_kmer.inc) holds the novel K-MERS:
+// their MurmurHash3 is taken here, once per read set, and phi_kmer_flush_rule (phi_dev.h) decides: the hash enters the set
+// unless it is the sentinel, a walk minimiser's hash (u_keys: the walk-minimiser table) or the hash of another k-mer in
+// the entry before (the lane below: entry i - 1 of the chunk, i > 0; lane 0 loads and hashes it).
 __global__ void __launch_bounds__(256) phi_spectrum_flush_kernel(const uint64_t *__restrict__ nov_log, const uint16_t *__restrict__ nov_cnt,
                                                                  int64_t c_lo, int64_t n_ent, int32_t shift,
                                                                  uint64_t *__restrict__ sp_keys, uint64_t sp_mask,
-                                                                 unsigned long long *__restrict__ sp_count, uint32_t *__restrict__ err)
+                                                                 unsigned long long *__restrict__ sp_count, int32_t k,
+                                                                 const uint64_t *__restrict__ u_keys, uint64_t u_mask, uint32_t *__restrict__ err)
 {
     int n_new = 0;
-    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n_ent; t += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t c = c_lo + (t >> shift);
-        const int i = (int)(t & ((1 << shift) - 1));
-        if (i >= (int)nov_cnt[c]) continue;
-        const uint64_t h = __builtin_nontemporal_load(&nov_log[(c << shift) + i]);
+    const int lane = threadIdx.x & 63;
+    // (whole waves take every turn: the lanes past n_ent hold nothing, the shuffle below needs them there)
+    for (int64_t t0 = (int64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63); t0 < n_ent; t0 += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t t = t0 + lane;
+        bool have = false, kmers = false;
+        int i = 0;
+        int64_t c = 0;
+        uint64_t h = 0, v = 0;
+        if (t < n_ent) {
+            c = c_lo + (t >> shift);
+            i = (int)(t & ((1 << shift) - 1));
+            const uint32_t cnt = nov_cnt[c];
+            kmers = (cnt & PHI_NOV_KMERS) != 0;
+            have = i < (int)(cnt & (PHI_NOV_KMERS - 1));
+            if (have) {
+                h = __builtin_nontemporal_load(&nov_log[(c << shift) + i]);
+                if (kmers) { v = h; h = phi_kmer_hash(v, k); }
+            }
+        }
+        // entry i - 1 of the same chunk is the lane below (a chunk's entries are consecutive threads; i > 0 and lane > 0)
+        uint64_t hp = __shfl_up(h, 1, 64), vp = __shfl_up(v, 1, 64);
+        if (have && kmers) {
+            if (lane == 0 && i > 0) { vp = nov_log[(c << shift) + i - 1]; hp = phi_kmer_hash(vp, k); }
+            bool in_walks = false;
+            if (h != PHI_EMPTY_KEY) {
+                uint64_t su = h & u_mask;
+                for (int probes = 0; probes <= PHI_MAX_PROBE; probes++) {
+                    const uint64_t key = u_keys[su];
+                    if (key == h) { in_walks = true; break; }
+                    if (key == PHI_EMPTY_KEY) break;
+                    su = (su + 1) & u_mask;
+                }
+            }
+            const uint32_t e = phi_kmer_flush_rule(h, v, i > 0, hp, vp, in_walks);
+            if (e) { atomicOr(err, e); have = false; }
+        }
+        if (!have) continue;
         uint64_t slot = h & sp_mask;
         int probes = 0;
         for (;;) {
@@ -299,12 +336,64 @@ __global__ void __launch_bounds__(256) phi_spectrum_flush_kernel(const uint64_t 
 }
 
 void phi_launch_spectrum_flush(hipStream_t st, const uint64_t *nov_log, const uint16_t *nov_cnt, int64_t c_lo, int64_t c_hi, int32_t shift,
-                               uint64_t *sp_keys, uint64_t sp_mask, unsigned long long *sp_count, uint32_t *err)
+                               uint64_t *sp_keys, uint64_t sp_mask, unsigned long long *sp_count, int32_t k, const uint64_t *u_keys,
+                               uint64_t u_mask, uint32_t *err)
 {
     const int64_t n_ent = (c_hi - c_lo) << shift;
     if (n_ent > 0)
         hipLaunchKernelGGL(phi_spectrum_flush_kernel, dim3(grid_for(n_ent, 256)), dim3(256), 0, st, nov_log, nov_cnt, c_lo, n_ent, shift,
-                           sp_keys, sp_mask, sp_count, err);
+                           sp_keys, sp_mask, sp_count, k, u_keys, u_mask, err);
+}
+
+// The k-mer keys of the walk minimisers (phi_kernels.h phi_launch_kmer_keys): one lane per class record.  The record's
+// k-mer from the class-space text -- 32 bases from its first one, the k-mer's strand by value as the sketch takes it --,
+// checked against the hash the sketch gave the record, then entered under the record's table slot: every record of a slot
+// must bring the same k-mer.
+__global__ void __launch_bounds__(256) phi_kmer_keys_kernel(const int32_t *__restrict__ rec_cls, const int32_t *__restrict__ rec_rel,
+                                                            const uint64_t *__restrict__ rec_hash, const uint32_t *__restrict__ rec_slot,
+                                                            int64_t n_rec, const int64_t *__restrict__ cls_base, const uint8_t *__restrict__ cls_left,
+                                                            const uint64_t *__restrict__ words, const uint32_t *__restrict__ badbits, int32_t k,
+                                                            uint64_t *__restrict__ kkeys, unsigned long long *__restrict__ ctr)
+{
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_rec; i += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t c = rec_cls[i];
+        const int64_t p = cls_base[c] + cls_left[c] + rec_rel[i];
+        const int64_t wi = p >> 5;
+        const int s = (int)(p & 31);
+        const uint64_t bad = (((uint64_t)badbits[wi + 1] << 32) | badbits[wi]) >> s;      // bit j: base p + j (s + k <= 62)
+        if (bad & ((1ull << k) - 1)) { atomicAdd(&ctr[0], 1ull); continue; }
+        const uint64_t f = phi_extract64(words, p) >> (64 - 2 * k), r = phi_revcomp(f, k);
+        const uint64_t v = f < r ? f : r;
+        if (phi_kmer_hash(v, k) != rec_hash[i]) { atomicAdd(&ctr[1], 1ull); continue; }
+        const uint64_t key = phi_kmer_mix(v);
+        unsigned long long *slot = (unsigned long long *)&kkeys[rec_slot[i]];
+        unsigned long long prev = __builtin_nontemporal_load(slot);
+        if (prev == PHI_EMPTY_KEY) prev = atomicCAS(slot, PHI_EMPTY_KEY, key);
+        if (prev != PHI_EMPTY_KEY && prev != key) atomicAdd(&ctr[2], 1ull);
+    }
+}
+void phi_launch_kmer_keys(hipStream_t st, const int32_t *rec_cls, const int32_t *rec_rel, const uint64_t *rec_hash, const uint32_t *rec_slot,
+                          int64_t n_rec, const int64_t *cls_base, const uint8_t *cls_left, const uint64_t *words, const uint32_t *badbits,
+                          int32_t k, uint64_t *kkeys, unsigned long long *ctr)
+{
+    if (n_rec > 0)
+        hipLaunchKernelGGL(phi_kmer_keys_kernel, dim3(grid_for(n_rec, 256)), dim3(256), 0, st, rec_cls, rec_rel, rec_hash, rec_slot, n_rec,
+                           cls_base, cls_left, words, badbits, k, kkeys, ctr);
+}
+
+__global__ void __launch_bounds__(256) phi_rt_overflowed_kernel(const uint64_t *__restrict__ rt, int64_t n_buckets,
+                                                                unsigned long long *__restrict__ n_out)
+{
+    int cnt = 0;
+    for (int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; b < n_buckets; b += (int64_t)gridDim.x * blockDim.x)
+        cnt += (int)((rt[4 * b + 1] >> 32) & PHI_RT_OVERFLOWED);
+    cnt = phi_wave_sum(cnt);
+    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(n_out, (unsigned long long)cnt);
+}
+void phi_launch_rt_overflowed(hipStream_t st, const uint64_t *rt, int64_t n_buckets, unsigned long long *n_out)
+{
+    if (n_buckets > 0)
+        hipLaunchKernelGGL(phi_rt_overflowed_kernel, dim3(grid_for(n_buckets, 256)), dim3(256), 0, st, rt, n_buckets, n_out);
 }
 
 // number of set hit flags (bytes != 0), added to *n_out
