@@ -33,8 +33,8 @@
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include "phi_kernels.h"
+#include "dp_dev.h"
 
-#define NEG (-(1 << 28))
 #define CHK PHI_DP_CHUNK
 #define RING PHI_DP_RING
 
@@ -72,32 +72,7 @@ void phi_launch_dp_words(hipStream_t st, const uint8_t *e_out, const int64_t *g_
 }
 
 // ------------------------------------------------------------------ the DP
-__device__ __forceinline__ unsigned long long pack_vh(int32_t val, int32_t h)
-{
-    // larger value wins, then the smaller walk id
-    return ((unsigned long long)(uint32_t)(val - NEG) << 32) | (uint32_t)(0x7FFFFFFF - h);
-}
-
-// max over the 64 lanes on the VALU: DPP rotations inside each row of 16 lanes, then the four row
-// results through v_readlane.  (__shfl_xor is ds_bpermute: six LDS round trips per reduction.)
-__device__ __forceinline__ int32_t wave_max_i32(int32_t v)
-{
-    v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x121, 0xF, 0xF, false));     // row_ror:1
-    v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x122, 0xF, 0xF, false));     // row_ror:2
-    v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x124, 0xF, 0xF, false));     // row_ror:4
-    v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x128, 0xF, 0xF, false));     // row_ror:8
-    const int32_t a = __builtin_amdgcn_readlane(v, 0), b = __builtin_amdgcn_readlane(v, 16);
-    const int32_t c = __builtin_amdgcn_readlane(v, 32), d = __builtin_amdgcn_readlane(v, 48);
-    return max(max(a, b), max(c, d));
-}
-
-// tops of a step packed in 16 bytes: x = top1 value, y = top2 value,
-// z = (top1 walk + 1) | (top1 out-edge + 1) << 10 | (top2 walk + 1) << 20
-__device__ __forceinline__ int4 pack_tops(int32_t t1v, int32_t t1h, int32_t t1n, int32_t t2v, int32_t t2h)
-{
-    return make_int4(t1v, t2v, (t1h + 1) | ((t1n + 1) << 10) | ((t2h + 1) << 20), 0);
-}
-
+// (the entry rule, the tops and their selection: dp_dev.h, shared with the event kernels)
 template <int NW>   // waves in the workgroup
 __global__ void __launch_bounds__(NW * 64) phi_dp_kernel(PhiDpArgs A)
 {
@@ -194,34 +169,7 @@ __global__ void __launch_bounds__(NW * 64) phi_dp_kernel(PhiDpArgs A)
             // ---- recombination entry into this vertex (uniform over the workgroup)
             int32_t E = NEG, Eh = -1, Esrc = -1;
             if (flags & PHI_DP_NEED_ENTRY) {
-                const int n_in = (flags >> 8) & 0xFF;
-                auto consider = [&](const int4 q, int32_t oj, int32_t src) {
-                    const int32_t t1h = (q.z & 0x3FF) - 1, t1n = ((q.z >> 10) & 0x3FF) - 1, t2h = ((q.z >> 20) & 0x3FF) - 1;
-                    const bool cont = t1n == oj;             // top1 continues along this edge: use top2
-                    const int32_t val = cont ? q.y : q.x, hh = cont ? t2h : t1h;
-                    if (hh < 0) return;
-                    if (val > E || (val == E && (hh < Eh || (hh == Eh && src < Esrc)))) { E = val; Eh = hh; Esrc = src; }
-                };
-                const uint32_t b0 = (uint32_t)ra.z >> 8, b1 = (uint32_t)ra.w >> 8, b2 = (uint32_t)rb.x >> 8;
-                if (n_in <= 3 && (b0 | b1 | b2) < RG) {
-                    // usual case: all sources in the LDS ring, the three look-ups in flight together
-                    const int4 q0 = s_top[(step - b0) & (RG - 1)];
-                    const int4 q1 = s_top[(step - b1) & (RG - 1)];
-                    const int4 q2 = s_top[(step - b2) & (RG - 1)];
-                    consider(q0, ra.z & 0xFF, step - (int32_t)b0);
-                    if (n_in > 1) consider(q1, ra.w & 0xFF, step - (int32_t)b1);
-                    if (n_in > 2) consider(q2, rb.x & 0xFF, step - (int32_t)b2);
-                } else {
-                    for (int j = 0; j < n_in; j++) {
-                        const int32_t p = j == 0 ? ra.z : j == 1 ? ra.w : j == 2 ? rb.x : A.in_packed[ra.y + j - 3];
-                        const int32_t back = (int32_t)((uint32_t)p >> 8);
-                        const int32_t src = step - back;
-                        const int4 q = back < RG ? s_top[src & (RG - 1)]
-                                                   : reinterpret_cast<const int4 *>(A.tops)[src];
-                        consider(q, p & 0xFF, src);
-                    }
-                }
-                if (Eh >= 0) E -= A.cost;
+                dp_eval_entry<RG, true>(ra, rb, step, s_top, A.in_packed, reinterpret_cast<const int4 *>(A.tops), A.cost, E, Eh, Esrc);
                 if (h == 0) { A.ent_src[step] = Esrc; A.ent_h[step] = Eh; }
             }
 
@@ -291,49 +239,11 @@ __global__ void __launch_bounds__(NW * 64) phi_dp_kernel(PhiDpArgs A)
             //      another out-edge.  Walks that end here do not leave.
             if (flags & PHI_DP_NEED_TOPS) {
                 const bool leaving = active && oidx != 255 && dmax > NEG / 2;
-                int32_t t1v = NEG, t1h = -1, t1n = -1, t2v = NEG, t2h = -1;
-                if (NW == 1) {
-                    const int32_t m1 = wave_max_i32(leaving ? dmax : NEG);
-                    if (m1 > NEG / 2) {
-                        const int l1 = __ffsll((long long)__ballot(leaving && dmax == m1)) - 1;   // lowest walk id
-                        t1v = m1; t1h = l1;
-                        t1n = __builtin_amdgcn_readlane(oidx, l1);
-                        const bool other = leaving && oidx != t1n;
-                        const int32_t m2 = wave_max_i32(other ? dmax : NEG);
-                        if (m2 > NEG / 2) { t2v = m2; t2h = __ffsll((long long)__ballot(other && dmax == m2)) - 1; }
-                    }
-                } else {
-                    s_oidx[h] = oidx;
-                    const int32_t m1 = wave_max_i32(leaving ? dmax : NEG);
-                    unsigned long long k1 = 0;
-                    if (m1 > NEG / 2) k1 = pack_vh(m1, wid * 64 + __ffsll((long long)__ballot(leaving && dmax == m1)) - 1);
-                    if (lane == 0) s_red[wid] = k1;
-                    __syncthreads();
-                    k1 = s_red[0];
-#pragma unroll
-                    for (int x = 1; x < NW; x++) k1 = s_red[x] > k1 ? s_red[x] : k1;
-                    if (k1) {
-                        t1v = (int32_t)(uint32_t)(k1 >> 32) + NEG;
-                        t1h = 0x7FFFFFFF - (int32_t)(uint32_t)k1;
-                        t1n = s_oidx[t1h];
-                    }
-                    __syncthreads();
-                    const bool other = leaving && oidx != t1n;
-                    const int32_t m2 = wave_max_i32(other ? dmax : NEG);
-                    unsigned long long k2 = 0;
-                    if (m2 > NEG / 2) k2 = pack_vh(m2, wid * 64 + __ffsll((long long)__ballot(other && dmax == m2)) - 1);
-                    if (lane == 0) s_red[wid] = k2;
-                    __syncthreads();
-                    k2 = s_red[0];
-#pragma unroll
-                    for (int x = 1; x < NW; x++) k2 = s_red[x] > k2 ? s_red[x] : k2;
-                    if (k2) {
-                        t2v = (int32_t)(uint32_t)(k2 >> 32) + NEG;
-                        t2h = 0x7FFFFFFF - (int32_t)(uint32_t)k2;
-                    }
-                }
+                DpTops t;
+                if constexpr (NW == 1) t = dp_tops_wave(leaving, dmax, oidx);
+                else t = dp_tops_waves<NW>(leaving, dmax, oidx, s_red, s_oidx);
                 if (h == 0) {
-                    const int4 q = pack_tops(t1v, t1h, t1n, t2v, t2h);
+                    const int4 q = pack_tops(t);
                     s_top[step & (RG - 1)] = q;
                     reinterpret_cast<int4 *>(A.tops)[step] = q;
                 }

@@ -203,7 +203,7 @@ static inline int phi_dp_steps_compact(const PhiDpGraph &g, PhiDpSteps &out, Phi
     return PHI_OK;
 }
 
-// where the chain of compact steps may be cut (dp_events.hip, blocks in parallel): not between the two steps of a pair,
+// where the chain of compact steps may be cut (dp_blocks.hip, blocks in parallel): not between the two steps of a pair,
 // and only where no recombination edge of this or a later step comes from before the cut.  After phi_dp_steps_compact.
 static inline void phi_dp_steps_cuts(PhiDpSteps &out)
 {

@@ -114,12 +114,13 @@ int phi_ctx_create(int device_id, phi_ctx **out)
         phi_warm_contexts(c->stream); (void)hipStreamSynchronize(c->stream); tm.lap("  code object: contexts");
         phi_warm_dp(c->stream); (void)hipStreamSynchronize(c->stream); tm.lap("  code object: dp");
         phi_warm_dp_events(c->stream); (void)hipStreamSynchronize(c->stream); tm.lap("  code object: dp_events");
+        phi_warm_dp_blocks(c->stream); (void)hipStreamSynchronize(c->stream); tm.lap("  code object: dp_blocks");
         phi_warm_solve_dev(c->stream); (void)hipStreamSynchronize(c->stream); tm.lap("  code object: solve_dev");
         phi_warm_reads_text(c->stream); (void)hipStreamSynchronize(c->stream); tm.lap("  code object: reads_text");
         phi_warm_scan(c->stream); (void)hipStreamSynchronize(c->stream); tm.lap("  code object: scan");
     }
     phi_warm_sketch(c->stream); phi_warm_table(c->stream); phi_warm_anchors(c->stream); phi_warm_contexts(c->stream);
-    phi_warm_dp(c->stream); phi_warm_dp_events(c->stream); phi_warm_solve_dev(c->stream); phi_warm_reads_text(c->stream);
+    phi_warm_dp(c->stream); phi_warm_dp_events(c->stream); phi_warm_dp_blocks(c->stream); phi_warm_solve_dev(c->stream); phi_warm_reads_text(c->stream);
     phi_warm_walk_text(c->stream); phi_warm_scan(c->stream);
     if (hipStreamSynchronize(c->stream) != hipSuccess) return bail(PHI_ERR_DEVICE);
     tm.lap("scalars + code objects");

@@ -282,12 +282,15 @@ struct PhiDpArgs {
     // outputs
     int32_t *dmax;                       // per entry (only where a path can end or leave): best score
     int32_t *bstart;                     // per entry: walk index where the run attaining it began (ties: the longest run)
-    int32_t *tops;                       // [n_vtx][5] by step: top1 value/walk/out-edge, top2 value/walk
+    int32_t *tops;                       // [n_vtx] by step: packed 16-byte tops (layout: dp_dev.h)
     int32_t *ent_src, *ent_h;            // per step: source step and walk of the best recombination entry
 };
 void phi_launch_dp(hipStream_t st, const PhiDpArgs &A);
+int phi_dp_num_waves(int n_walks);
+void phi_launch_dp_words(hipStream_t st, const uint8_t *e_out, const int64_t *g_off, const uint8_t *g_span,
+                         const uint8_t *a_weight, int64_t n_entries, uint64_t *word);
 
-// event-driven DP (dp_events.hip): up to PHI_DP_EVENT_MAX_WALKS walks
+// dp_events.hip: the event-driven DP, up to PHI_DP_EVENT_MAX_WALKS walks -- event records and the step kernels
 #define PHI_DP_EVENT_MAX_WALKS 256
 #define PHI_DP_EVENT_SAFE_WALKS 128  // beyond: per-lane queues of 16 runs; a deeper one makes the caller fall back to dp.hip
 struct PhiDpEventArgs {
@@ -305,7 +308,7 @@ struct PhiDpEventArgs {
     int32_t cost;
     // outputs
     int32_t *dmax, *bstart;              // per entry, written at query events
-    int32_t *tops;                       // [n_k] packed 16-byte tops
+    int32_t *tops;                       // [n_k] packed 16-byte tops (layout: dp_dev.h)
     int32_t *ent_src, *ent_h;            // per compact step
     uint32_t *err;                       // PHI_KERR_DP_QUEUE
     int32_t q_limit;                     // 0 = the kernel's queue depth; tests lower it to provoke the fallback
@@ -327,6 +330,13 @@ struct PhiDpEventArgs {
 void phi_launch_dp_events(hipStream_t st, const PhiDpEventArgs &A);
 void phi_launch_dp_block_rows(hipStream_t st, const PhiDpEventArgs &A);
 void phi_launch_dp_block_paths(hipStream_t st, const PhiDpEventArgs &A);
+// DP_PATH on walk lanes, more than 64 walks
+void phi_launch_dp_block_paths_wide(hipStream_t st, const PhiDpEventArgs &A);
+void phi_launch_event_flags(hipStream_t st, const int32_t *walk_vtx, int64_t n_entries, const int32_t *cvtx, uint8_t *flags);
+void phi_launch_event_off(hipStream_t st, const phi_ent_t *ev_e, int64_t n_ev, const int64_t *walk_off, int32_t n_walks,
+                          int64_t *ev_off);
+void phi_launch_dp_event_fill(hipStream_t st, const PhiDpEventArgs &A, const uint8_t *e_out, const int32_t *walk_vtx,
+                              const int32_t *cvtx, const phi_ent_t *a_e1, const int32_t *wpre, int64_t n_entries);
 // the solve's bookkeeping on the device copy of the anchors (solve_dev.hip)
 void phi_launch_anchor_prep(hipStream_t st, const uint32_t *tri, int64_t n, const int64_t *walk_off, int32_t n_walks, phi_ent_t *a_e1, uint8_t *a_span,
                             unsigned long long *walk_cnt, unsigned long long *out);
@@ -337,7 +347,8 @@ void phi_launch_weights(hipStream_t st, const uint32_t *tri, int64_t n, const ui
 void phi_launch_path_cover(hipStream_t st, bool clear, const phi_ent_t *segs, int32_t n_seg, const int64_t *g_off, const uint32_t *tri, const uint8_t *wgt,
                            int32_t *cov_all, int32_t *cov_w, unsigned long long *ctr, uint32_t *twice, int64_t twice_cap);
 void phi_launch_uncovered_slots(hipStream_t st, const uint32_t *slots, int64_t n, const int32_t *cov_all, unsigned long long *ctr, uint32_t *out);
-// more than 64 walks: the blocks' rows on class lanes (dp_events.hip)
+// dp_blocks.hip: where the chain may be cut; more than 64 walks: the classes of walks per block and the chain over the
+// blocks on class lanes (their rows are made by phi_launch_dp_block_rows)
 struct PhiBlkClassArgs {
     int32_t n_blk, n_walks, lane_stride;
     const int32_t *blk_lo, *blk_ev;      // [n_blk + 1], [n_blk][lane_stride]
@@ -355,7 +366,6 @@ void phi_launch_blk_chain_segments(hipStream_t st, const PhiBlkClassArgs &G, con
                                    int32_t n_seg, const int32_t *d_seg_lo, int32_t *seg_row, int32_t *seg_S);
 void phi_launch_blk_check(hipStream_t st, const int32_t *keys, const int32_t *S, int32_t n_blk, int32_t LS, int32_t n_walks, int32_t *bad);
 void phi_launch_carry_resolve(hipStream_t st, const int32_t *carry, int32_t LS, int32_t b_from, int32_t h, int32_t *out);
-void phi_launch_dp_block_paths_wide(hipStream_t st, const PhiDpEventArgs &A);
 void phi_launch_cut_cov(hipStream_t st, const phi_ent_t *a_e1, const uint8_t *a_span, int64_t n_a, int32_t *diff);
 void phi_launch_cut_clean(hipStream_t st, const int32_t *cov_excl, int64_t n_entries, int32_t *clean);
 void phi_launch_cut_clean_direct(hipStream_t st, const int64_t *g_off, const uint8_t *g_span, int64_t n_entries, int32_t *clean);
@@ -363,14 +373,6 @@ void phi_launch_cut_events(hipStream_t st, const phi_ent_t *ev_e, int64_t n_ev, 
                            const int32_t *walk_vtx, const int32_t *cvtx, const int32_t *ncl_excl, int32_t *stepdiff);
 void phi_launch_blk_ev(hipStream_t st, const int32_t *blk_lo, int32_t n_blk, const phi_ent_t *ev_e, const int64_t *ev_off, int32_t n_walks,
                        const int32_t *walk_vtx, const int32_t *cvtx, int32_t *blk_ev);
-void phi_launch_event_flags(hipStream_t st, const int32_t *walk_vtx, int64_t n_entries, const int32_t *cvtx, uint8_t *flags);
-void phi_launch_event_off(hipStream_t st, const phi_ent_t *ev_e, int64_t n_ev, const int64_t *walk_off, int32_t n_walks,
-                          int64_t *ev_off);
-void phi_launch_dp_event_fill(hipStream_t st, const PhiDpEventArgs &A, const uint8_t *e_out, const int32_t *walk_vtx,
-                              const int32_t *cvtx, const phi_ent_t *a_e1, const int32_t *wpre, int64_t n_entries);
-int phi_dp_num_waves(int n_walks);
-void phi_launch_dp_words(hipStream_t st, const uint8_t *e_out, const int64_t *g_off, const uint8_t *g_span,
-                         const uint8_t *a_weight, int64_t n_entries, uint64_t *word);
 
 // reads_text.hip: the records of a FASTA / FASTQ text found on the device
 #define PHI_TEXT_IRREGULAR_CR 1u       // a carriage return in the chunk
@@ -426,6 +428,7 @@ void phi_warm_anchors(hipStream_t st);
 void phi_warm_contexts(hipStream_t st);
 void phi_warm_dp(hipStream_t st);
 void phi_warm_dp_events(hipStream_t st);
+void phi_warm_dp_blocks(hipStream_t st);
 void phi_warm_solve_dev(hipStream_t st);
 void phi_warm_reads_text(hipStream_t st);
 void phi_warm_walk_text(hipStream_t st);

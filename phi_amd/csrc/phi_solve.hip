@@ -259,7 +259,7 @@ static int dp_blocks_fallback(phi_ctx *c, uint32_t kerr, uint32_t bit, DpRetry *
 }
 
 // the chain over the class-lane blocks: one workgroup, 1.1 us per block -- or, from a few thousand blocks on, cut into segments
-// whose matrices are made in parallel, chained, and replayed in parallel (dp_events.hip; PHI_DP_CHAIN_SEGMENTS: tests)
+// whose matrices are made in parallel, chained, and replayed in parallel (dp_blocks.hip; PHI_DP_CHAIN_SEGMENTS: tests)
 static int dp_chain_class_rows(phi_ctx *c, const PhiBlkClassArgs &G, const PhiDpEventArgs &A)
 {
     const int32_t nb = c->n_blk;

@@ -1,7 +1,7 @@
 // Sums across the 64 lanes of a wave and across the waves of a workgroup: the one copy of the two idioms every scan,
 // compaction and counter of the device code is made of.  Device code only; workgroups are one-dimensional (the lane is
 // threadIdx.x & 63).  Integer sums only: the order of the additions is not part of the result.
-// (The sketch and DP kernels keep their own DPP scans and reductions, tuned to a register count: sketch.hip, dp.hip.)
+// (The sketch and DP kernels keep their own DPP scans and reductions, tuned to a register count: sketch_dev.h, dp_dev.h.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -131,3 +131,46 @@ def test_scan_kernels_compile_for_gfx950_without_scratch(tmp_path):
         m = _meta(asm, kernel)
         print(kernel, m)
         assert m["vgpr_spill_count"] == 0 and m["sgpr_spill_count"] == 0 and m["private_segment_fixed_size"] == 0, (kernel, m)
+
+
+def test_event_dp_kernels_fit_the_tasks_per_cu_their_launchers_state(tmp_path):
+    """dp_events.hip: the consumer + producers kernel uses no scratch in any instance (its consumer wave is the serial chain
+    of the solve), and the static LDS of an instance leaves room for the workgroups per CU (160 KB of LDS) that the comments
+    at its launchers count on: six for the rows of blocks of at most 64 steps (CK = 32), four / three for the rows / paths on
+    a ring of 256 tops, two on a ring of 1 024.  Every instance, and the two- and four-wave kernel, fits one CU."""
+    if not os.path.exists(HIPCC):
+        pytest.skip("hipcc not found")
+    out = tmp_path / "dp_events.s"
+    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-o", str(out),
+                           os.path.join(ROOT, "phi_amd", "csrc", "dp_events.hip")], stderr=subprocess.DEVNULL)
+    asm = out.read_text()
+    kernels = sorted(set(re.findall(r"^\s+\.name:\s+(\S+)$", asm.split("amdhsa.kernels:")[1], flags=re.M)))
+    LDS = 160 * 1024
+    DP_ROW, DP_PATH = 1, 2
+    pc = [k for k in kernels if "phi_dp_events_pc_kernel" in k]
+    assert len(pc) == 8, pc
+    seen = set()
+    for kernel in pc:
+        npw, mode, p, ringt, qd, ck = map(int, re.search(r"pc_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)EE", kernel).groups())
+        m = _meta(asm, kernel)
+        print(kernel, m)
+        assert m["vgpr_spill_count"] == 0 and m["private_segment_fixed_size"] == 0, (kernel, m)
+        lds = m["group_segment_fixed_size"]
+        assert lds <= LDS, (kernel, m)
+        if ck == 32:
+            seen.add("ck32")
+            assert mode == DP_ROW and lds * 6 <= LDS, (kernel, m)
+        elif ringt == 256 and mode == DP_ROW:
+            seen.add("row256")
+            assert lds * 4 <= LDS, (kernel, m)
+        elif ringt == 256 and mode == DP_PATH:
+            seen.add("path256")
+            assert lds * 3 <= LDS, (kernel, m)
+        elif ringt == 1024:
+            seen.add(("ring1024", mode))
+            assert lds * 2 <= LDS, (kernel, m)
+    assert seen == {"ck32", "row256", "path256", ("ring1024", DP_ROW), ("ring1024", DP_PATH)}, seen
+    wide = [k for k in kernels if "phi_dp_events_kernelILi" in k]
+    assert len(wide) == 4 and all(re.search(r"kernelILi[24]ELi[02]EE", k) for k in wide), wide      # two or four waves, DP_SEQ or DP_PATH
+    for kernel in wide:
+        assert _meta(asm, kernel)["group_segment_fixed_size"] <= LDS, kernel

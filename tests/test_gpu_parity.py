@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import DATA, GOLDEN
-from graphgen import mosaic_reads, random_graph
+from graphgen import mosaic_reads, random_graph, walk_sequence
 
 pytestmark = pytest.mark.gpu
 
@@ -1671,15 +1671,39 @@ def test_novel_hash_log_spills_grows_and_starts_over(oracle, ctx_factory, monkey
     assert ctx.reads_stats()["n_distinct"] == want and ctx.solve()["spectrum_size"] == want
 
 
-@pytest.mark.parametrize("block_steps", ["1", "3", "16", None])
-def test_dp_blocks_in_parallel_equal_the_whole_chain(oracle, ctx_factory, monkeypatch, block_steps):
+def _closed_stretch_case(seed, n_sites, n_walks, k, frac):
+    """A chain of short bubbles (a site every ~4 bases, k-mers span two or more of them, w = 1: every k-mer an anchor that
+    no filter drops) with reads tiling the first `frac` of every walk: no entry there is clean of anchors, so no cut may
+    split that stretch of ~3 * n_sites * frac compact steps; behind it no anchor is matched and cuts abound."""
+    rng = np.random.default_rng(seed)
+    g = random_graph(rng, n_sites=n_sites, n_walks=n_walks, seg_len=(1, 3), alt_len=(1, 3), p_del=0.0)
+    reads = []
+    for h in range(g.n_walks):
+        s = walk_sequence(g, h)
+        reads += [s[a:a + 60] for a in range(0, int(len(s) * frac) - 60, 20)]
+    return g, reads, k
+
+
+@pytest.mark.parametrize("block_steps", ["1", "3", "16", None, "ring2048"])
+def test_dp_blocks_in_parallel_equal_the_whole_chain(oracle, ctx_factory, monkeypatch, capfd, block_steps):
     """Up to 64 walks the chain of compact steps is cut at clean cuts and the blocks are solved in parallel (transfer-matrix
     rows, host chain, second pass from the true entry vectors).  PHI_DP_BLOCK_STEPS forces blocks of a few steps so that
     small graphs have many cuts; PHI_DP_NOBLOCKS=1 keeps the chain whole.  Same objective, bound, proof and counters, a
-    feasible path of that value, over graphs with repeats, walks ending inside the graph, R = 0 .. 100."""
+    feasible path of that value, over graphs with repeats, walks ending inside the graph, R = 0 .. 100.
+    ring2048: graphs whose longest stretch without a cut has more than 1 024 compact steps (1 201 of 1 336; 1 301 of 1 501,
+    solved by branch and bound) -- the rows and paths on a ring of 2 048 tops, which the solve's timing line confirms."""
     from oracle import solve_oracle as S
     cases = []
-    for seed in range(10):
+    if block_steps == "ring2048":
+        for n_sites, n_walks, k, w, frac in ((450, 6, 11, 1, 0.9), (500, 12, 9, 2, 0.85)):
+            g, reads, k = _closed_stretch_case(7800, n_sites, n_walks, k, frac)
+            cases.append((g, reads, k, w, 3))
+        monkeypatch.setenv("PHI_TIMING", "1")
+        block_steps = None
+        want_ring = "(rings of 2048 steps)"
+    else:
+        want_ring = None
+    for seed in (range(10) if want_ring is None else ()):
         rng = np.random.default_rng(7700 + seed)
         k, w = int(rng.integers(5, 12)), int(rng.integers(1, 7))
         rep = bytes(rng.choice(list(b"ACGT"), size=k + 4).tolist()) if seed % 2 else None
@@ -1701,7 +1725,10 @@ def test_dp_blocks_in_parallel_equal_the_whole_chain(oracle, ctx_factory, monkey
             ctx.set_solve_budget(64)
             _set_graph(ctx, g)
             ctx.add_reads(reads)
+            capfd.readouterr()
             res = ctx.solve()
+            if want_ring and mode == "blocks":
+                assert want_ring in capfd.readouterr().err and ctx.solve_stats()["dp_mode"] == 2
             monkeypatch.delenv("PHI_DP_NOBLOCKS", raising=False)
             monkeypatch.delenv("PHI_DP_BLOCK_STEPS", raising=False)
             out[mode] = res
