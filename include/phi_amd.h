@@ -534,6 +534,37 @@ typedef struct {
 } phi_solve_info;
 int phi_solve_stats(phi_ctx *ctx, phi_solve_info *out);
 
+/*
+ * Test introspection: ONE run of the solve's DP with anchor weights the caller gives (no reference counterpart; the
+ * search calls the same function once per relaxation).  Valid after phi_solve, on the state that solve left: the strategy
+ * (dp_mode and the blocks phi_solve_stats reports), including what its fallbacks changed.  The run is the solve's own,
+ * fallbacks included, and may change that state as a run inside a solve would; the next phi_solve starts over as ever.
+ *
+ * weights: one byte, 0 or 1, per dp anchor = per kept anchor that spans an edge (t1 > t0 in phi_kept_anchors), in kept
+ * order; n_weights must be their number (phi_solve_info.n_dp_anchors).  NULL: every weight 1 (n_weights is not read).
+ * The run maximises, over the walks-and-switches paths of the model, the weights of the anchors traversed whole minus
+ * 2 * (recombination / 2) per switch.
+ *
+ * out_ends[h], h < n_walks: the best value of a path that ends at the last vertex of walk h (INT32_MIN: none).
+ * *out_value, *out_end_walk: the largest of them and the lowest walk that has it.  The argmax path as segments in path
+ * order -- walk, first and last position within the walk -- *n_seg of them; with seg_cap < *n_seg none is written.
+ * info: the strategy of the attempt that finished (dp_mode, n_blocks, max_classes as in phi_solve_info; blk_ring = ring of
+ * tops the blocks were placed for, blk_max_len = steps of the longest block; both 0 without blocks) and the fallbacks
+ * taken on the way, PHI_DP_RETRY_* or-ed; retries_since_solve: those of every run since the last phi_solve began, its own
+ * runs included (a solve whose first run falls back leaves nothing for a later run to fall back from).
+ */
+#define PHI_DP_RETRY_HALVE_CLASS_TARGET 1u   /* a block with more than 64 classes: shorter class-lane blocks */
+#define PHI_DP_RETRY_NO_SMALL_BLOCKS 2u      /* a 256-step block task's queue overflowed: longer blocks */
+#define PHI_DP_RETRY_GIVE_UP_BLOCKS 4u       /* the whole event chain from now on */
+#define PHI_DP_RETRY_DENSE 8u                /* the event kernel's queue overflowed: every vertex a step from now on */
+typedef struct {
+    int32_t dp_mode, n_blocks, blk_ring, blk_max_len, max_classes;
+    uint32_t retries, retries_since_solve;
+} phi_dp_probe_info;
+int phi_dp_probe(phi_ctx *ctx, const uint8_t *weights, int64_t n_weights, int32_t *out_ends, int64_t *out_value,
+                 int32_t *out_end_walk, int32_t *out_seg_walk, int64_t *out_seg_first, int64_t *out_seg_last,
+                 int64_t seg_cap, int64_t *n_seg, phi_dp_probe_info *info);
+
 /* Minimisers of walk h found by phi_set_graph, sorted by position. */
 int phi_walk_minimizers(phi_ctx *ctx, int32_t walk, uint64_t *out_hash, int64_t *out_pos,
                         int64_t cap, int64_t *n_out);

@@ -22,7 +22,7 @@ SYMBOLS = [
     "phi_spectrum_export", "phi_spectrum_import", "phi_spectrum_set_size", "phi_solve", "phi_path_sequence",
     "phi_sketch", "phi_walk_minimizers", "phi_walk_sharing", "phi_kept_anchors", "phi_prof_enable", "phi_prof_read",
     "phi_host_register", "phi_host_unregister", "phi_set_solve_budget", "phi_device_synchronize", "phi_walk_text_upload", "phi_walk_text_resolve", "phi_walk_entries",
-    "phi_index_stats", "phi_solve_stats", "phi_comm_unique_id", "phi_comm_init", "phi_comm_info", "phi_comm_allreduce_hits", "phi_comm_exchange", "phi_comm_destroy",
+    "phi_index_stats", "phi_solve_stats", "phi_dp_probe", "phi_comm_unique_id", "phi_comm_init", "phi_comm_info", "phi_comm_allreduce_hits", "phi_comm_exchange", "phi_comm_destroy",
     "phi_reads_text_begin", "phi_add_reads_text", "phi_reads_text_end", "phi_reads_text_detach_carry", "phi_reads_text_last_batch",
     "phi_text_park_create", "phi_text_park_pin", "phi_text_park_add", "phi_text_park_add_async", "phi_text_park_wait", "phi_text_park_bytes", "phi_text_park_fetch", "phi_text_park_release", "phi_text_park_destroy",
     "phi_add_reads_text_parked",
@@ -57,6 +57,14 @@ class PhiIndexInfo(C.Structure):
 class PhiSolveInfo(C.Structure):
     _fields_ = [("n_dp_anchors", C.c_int64), ("n_events", C.c_int64), ("n_steps", C.c_int32), ("n_blocks", C.c_int32),
                 ("dp_mode", C.c_int32), ("max_classes", C.c_int32), ("mean_classes", C.c_double)]
+
+
+class PhiDpProbeInfo(C.Structure):
+    _fields_ = [("dp_mode", C.c_int32), ("n_blocks", C.c_int32), ("blk_ring", C.c_int32), ("blk_max_len", C.c_int32),
+                ("max_classes", C.c_int32), ("retries", C.c_uint32), ("retries_since_solve", C.c_uint32)]
+
+
+PHI_DP_RETRY_HALVE_CLASS_TARGET, PHI_DP_RETRY_NO_SMALL_BLOCKS, PHI_DP_RETRY_GIVE_UP_BLOCKS, PHI_DP_RETRY_DENSE = 1, 2, 4, 8
 
 
 class PhiChopInfo(C.Structure):
@@ -211,6 +219,7 @@ def load():
     L.phi_set_solve_budget.argtypes = [vp, i64]
     L.phi_index_stats.argtypes = [vp, C.POINTER(PhiIndexInfo)]
     L.phi_solve_stats.argtypes = [vp, C.POINTER(PhiSolveInfo)]
+    L.phi_dp_probe.argtypes = [vp, vp, i64, vp, C.POINTER(i64), C.POINTER(i32), vp, vp, vp, i64, C.POINTER(i64), C.POINTER(PhiDpProbeInfo)]
     L.phi_comm_unique_id.argtypes = [vp, C.c_size_t]
     L.phi_comm_init.argtypes = [vp, vp, i32, i32]
     L.phi_comm_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]

@@ -326,6 +326,33 @@ class Context:
         self._chk(self._L.phi_solve_stats(self._h, C.byref(r)))
         return {n: getattr(r, n) for n, _ in _capi.PhiSolveInfo._fields_}
 
+    def dp_probe(self, weights=None):
+        """(tests) One run of the solve's DP, after solve(), with one 0/1 weight per dp anchor (the kept anchors with
+        t1 > t0, in kept order; None: all ones).  ends: per walk the best value of a path ending at its last vertex (None: no
+        such path); value, end_walk: the best of them, the lowest walk that has it; segs: the argmax path as (walk, first,
+        last position in the walk); dp_mode, n_blocks, blk_ring, blk_max_len, max_classes: the strategy of the attempt that
+        finished; retries: the fallbacks taken on the way (PHI_DP_RETRY_* or-ed); retries_since_solve: those of every run since
+        the last solve began, its own included."""
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, np.uint8)
+        ends = np.zeros(max(self.n_walks, 1), np.int32)
+        value, end_walk, n_seg = C.c_int64(), C.c_int32(), C.c_int64()
+        info = _capi.PhiDpProbeInfo()
+        cap = self.n_vtx + 1                                   # (one segment per vertex at most; a chopped graph has more vertices)
+        while True:
+            sw, s0, s1 = np.zeros(cap, np.int32), np.zeros(cap, np.int64), np.zeros(cap, np.int64)
+            self._chk(self._L.phi_dp_probe(self._h, None if w is None else w.ctypes.data, 0 if w is None else len(w), _ptr(ends),
+                                           C.byref(value), C.byref(end_walk), _ptr(sw), _ptr(s0), _ptr(s1), cap, C.byref(n_seg), C.byref(info)))
+            if n_seg.value <= cap:
+                break
+            cap = n_seg.value                                  # (the run again, with room for its path)
+        n = n_seg.value
+        out = {"ends": [None if e == -2 ** 31 else int(e) for e in ends[:self.n_walks].tolist()], "value": value.value,
+               "end_walk": end_walk.value, "segs": list(zip(sw[:n].tolist(), s0[:n].tolist(), s1[:n].tolist()))}
+        out.update({name: getattr(info, name) for name, _ in _capi.PhiDpProbeInfo._fields_})
+        return out
+
     # ------------------------------------------------------------------ reads
     def add_reads(self, seqs):
         """seqs: list of bytes, or (concat bytes/uint8 array, int64 offsets)."""

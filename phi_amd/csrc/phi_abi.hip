@@ -406,6 +406,29 @@ int phi_solve_stats(phi_ctx *c, phi_solve_info *out)
     return PHI_OK;
 }
 
+int phi_dp_probe(phi_ctx *c, const uint8_t *weights, int64_t n_weights, int32_t *out_ends, int64_t *out_value, int32_t *out_end_walk,
+                 int32_t *out_seg_walk, int64_t *out_seg_first, int64_t *out_seg_last, int64_t seg_cap, int64_t *n_seg, phi_dp_probe_info *info)
+{
+    if (!c || !out_ends || !out_value || !out_end_walk || !n_seg || !info) return PHI_ERR_INVALID;
+    if (seg_cap > 0 && (!out_seg_walk || !out_seg_first || !out_seg_last)) return PHI_ERR_INVALID;
+    PHICHK(phi_refuse_scout(c, "phi_dp_probe"));
+    if (!c->solved) return phi_fail(c, PHI_ERR_STATE, "phi_dp_probe before phi_solve");
+    if (weights) {
+        if (n_weights != c->n_dp) return phi_fail(c, PHI_ERR_INVALID, "phi_dp_probe: %lld weights for %lld dp anchors", (long long)n_weights, (long long)c->n_dp);
+        for (int64_t a = 0; a < n_weights; a++)
+            if (weights[a] > 1) return phi_fail(c, PHI_ERR_INVALID, "phi_dp_probe: weight %lld is %d, not 0 or 1", (long long)a, (int)weights[a]);
+    }
+    HIPCHK(hipSetDevice(c->device));
+    memset(info, 0, sizeof *info);
+    PHICHK(phi_dp_probe_impl(c, weights, out_ends, out_value, out_end_walk, out_seg_walk, out_seg_first, out_seg_last, seg_cap, n_seg, &info->retries));
+    phi_solve_info st;
+    PHICHK(phi_solve_stats(c, &st));                             // (the strategy as the run left it: the attempt that finished)
+    info->dp_mode = st.dp_mode; info->n_blocks = st.n_blocks; info->max_classes = st.max_classes;
+    if (st.dp_mode >= 2) { info->blk_ring = c->blk_ring; info->blk_max_len = c->blk_max_len; }
+    info->retries_since_solve = c->dp_retries;
+    return PHI_OK;
+}
+
 int phi_walk_sharing(phi_ctx *c, int64_t *hist, int32_t cap, int64_t *n_distinct)
 {
     if (!c || !hist) return PHI_ERR_INVALID;

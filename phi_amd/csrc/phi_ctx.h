@@ -297,6 +297,7 @@ struct phi_ctx {
     int32_t blk_cls_target = 16;        // class-lane blocks: steps per block aimed at (halved when a block holds more than 64 classes)
     bool blk_no_small = false;          // this solve met a block task with more than 8 live runs on a lane: no 256-step blocks
     int32_t blk_ls = 64;                // row length of the per-(block, walk) tables
+    uint32_t dp_retries = 0;            // the fallbacks DP runs have taken since the last solve began (PHI_DP_RETRY_*: phi_dp_probe reports them)
     DevBuf d_lane_walk, d_walk_lane, d_coff, d_blk_ncls, d_rownew, d_blk_bad;
     DevBuf d_seg_lo, d_seg_row, d_seg_S;  // the chain over the blocks cut into segments (dp_blocks.hip)
     DevBuf d_k_rec, d_k_in, d_cvtx, d_ev_e, d_ev_off, d_ev, d_off_end, d_off_start, d_scan_blk, d_scan_blk64, d_scan_blkoff;
@@ -458,6 +459,8 @@ static inline int phi_refuse_scout(phi_ctx *c, const char *what)
 }
 // pinned host buffer of at least `bytes` (contents are not kept)
 int phi_pin_ensure(phi_ctx *c, size_t bytes);
+int phi_dp_probe_impl(phi_ctx *c, const uint8_t *weights, int32_t *out_ends, int64_t *out_value, int32_t *out_end_walk,   // phi_solve.hip
+                      int32_t *out_seg_walk, int64_t *out_seg_first, int64_t *out_seg_last, int64_t seg_cap, int64_t *n_seg, uint32_t *retries);
 int phi_host_anchors(phi_ctx *c);                      // the host copy of the kept anchors, fetched if it is not there
 // phi_ipc.hip
 int phi_ipc_wait_pending(phi_ctx *c);                  // the context's stream waits for the last gather (every observer of the hit vector: phi_flush_reset)

@@ -497,11 +497,23 @@ static int dp_backtrack(phi_ctx *c, const DpOut &O, bool events, DpHost &H, int3
     return PHI_OK;
 }
 
+// what a caller that looks into a run (phi_dp_probe) learns besides its value and path
+struct DpTrace {
+    uint32_t retries = 0;                                      // bit (r - 1): DpRetry r was taken on the way
+    int32_t end_walk = -1;                                     // dp_pick_end's walk
+};
+static_assert((1u << (DP_HALVE_CLASS_TARGET - 1)) == PHI_DP_RETRY_HALVE_CLASS_TARGET && (1u << (DP_NO_SMALL_BLOCKS - 1)) == PHI_DP_RETRY_NO_SMALL_BLOCKS &&
+              (1u << (DP_GIVE_UP_BLOCKS - 1)) == PHI_DP_RETRY_GIVE_UP_BLOCKS && (1u << (DP_DENSE - 1)) == PHI_DP_RETRY_DENSE, "phi_dp_probe_info.retries (phi_amd.h)");
+
 // One DP run with the given anchor weights (wgt == nullptr: the weights are on the device already): its value and the
 // argmax path.  An attempt that names a DpRetry has left the error word clean; the next one starts over, weights included.
-static int run_dp(phi_ctx *c, const std::vector<uint8_t> *wgt, DpHost &H, int64_t *value, std::vector<Seg> *segs)
+static int run_dp(phi_ctx *c, const std::vector<uint8_t> *wgt, DpHost &H, int64_t *value, std::vector<Seg> *segs, DpTrace *trace = nullptr)
 {
     for (DpRetry want = DP_DONE;;) {
+        if (want != DP_DONE) {
+            c->dp_retries |= 1u << (want - 1);
+            if (trace) trace->retries |= 1u << (want - 1);
+        }
         switch (want) {
         case DP_DONE: break;
         case DP_HALVE_CLASS_TARGET: c->blk_cls_target /= 2; PHICHK(dp_prepare_blocks(c, c->n_dp)); break;
@@ -529,10 +541,37 @@ static int run_dp(phi_ctx *c, const std::vector<uint8_t> *wgt, DpHost &H, int64_
         if (want != DP_DONE) continue;
         int32_t bh = -1;
         PHICHK(dp_pick_end(c, H, &bh, value));
+        if (trace) trace->end_walk = bh;
         PHICHK(dp_backtrack(c, O, events, H, bh, segs));
         tr.lap("backtrack");
         return PHI_OK;
     }
+}
+
+// phi_dp_probe: run_dp itself, once, on the state the last solve left, with the caller's weights -- what a relaxation of
+// the search does between its weights and its path cover.  The ends are dp_fetch_ends' (a walk without a state: INT32_MIN),
+// value and end walk dp_pick_end's, the segments run_dp's with positions inside their walk.  Test introspection.
+int phi_dp_probe_impl(phi_ctx *c, const uint8_t *weights, int32_t *out_ends, int64_t *out_value, int32_t *out_end_walk,
+                      int32_t *out_seg_walk, int64_t *out_seg_first, int64_t *out_seg_last, int64_t seg_cap, int64_t *n_seg, uint32_t *retries)
+{
+    std::vector<uint8_t> wgt((size_t)c->n_dp, 1);
+    if (weights) wgt.assign(weights, weights + c->n_dp);
+    DpHost H;
+    DpTrace T;
+    std::vector<Seg> segs;
+    int64_t value = 0;
+    PHICHK(run_dp(c, &wgt, H, &value, &segs, &T));
+    for (int32_t h = 0; h < c->n_walks; h++) out_ends[h] = H.ends[(size_t)h] > -(1 << 28) ? H.ends[(size_t)h] : INT32_MIN;
+    *out_value = value;
+    *out_end_walk = T.end_walk;
+    *retries = T.retries;
+    *n_seg = (int64_t)segs.size();
+    if ((int64_t)segs.size() > seg_cap) return PHI_OK;
+    for (size_t i = 0; i < segs.size(); i++) {
+        const int64_t w0 = c->h_walk_off[(size_t)segs[i].h];
+        out_seg_walk[i] = segs[i].h; out_seg_first[i] = segs[i].es - w0; out_seg_last[i] = segs[i].ee - w0;
+    }
+    return PHI_OK;
 }
 
 // dp anchors traversed by a path: calls f(anchor index)
@@ -861,6 +900,7 @@ static int dp_inputs(Solve &S)
     PHICHK(phi_dev_ensure(c, c->d_ent, (size_t)c->n_vtx * 2 * 4));
     c->blk_no_small = false;
     c->blk_cls_target = 16;
+    c->dp_retries = 0;
     PHICHK(dp_prepare_blocks(c, S.n_dp));
     S.tm.lap("DP inputs");
     return PHI_OK;

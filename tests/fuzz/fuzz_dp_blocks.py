@@ -2,7 +2,8 @@
 class lanes for 65-256 walks, with block lengths forced to 1 .. 12 steps or left to the solve, dense graphs (few cuts,
 many classes: the fallbacks) and sparse ones (k ~ 5, w ~ 20: many cuts), the solve's bookkeeping on the device copy of
 the anchors or on the host copy.  Objective, bound, proof flag and counters must agree; the path is evaluated on the
-restated model.
+restated model.  On every graph and in both modes one DP run with all weights 1 and one with Bernoulli 1/2 weights
+(Context.dp_probe) equal the plain reference of tests/dp_ref.py at the end of every walk.
 Usage (GPU box): python tests/fuzz/fuzz_dp_blocks.py SEED SECONDS [MIN_WALKS MAX_WALKS]  (default 2 257)"""
 import os, sys, time, numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -11,6 +12,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import phi_amd
 from graphgen import random_graph, mosaic_reads
 import test_gpu_parity as T
+import dp_ref
 from oracle import oracle as O, solve_oracle as S
 seed0 = int(sys.argv[1]); t_end = time.time() + float(sys.argv[2])
 lo_w, hi_w = (int(sys.argv[3]), int(sys.argv[4])) if len(sys.argv) > 4 else (2, 257)
@@ -39,6 +41,7 @@ while time.time() < t_end:
         T._set_graph(ctx, g); ctx.add_reads(reads)
         res = ctx.solve()
         info = ctx.solve_stats()
+        dp_ref.check_probes(ctx, g, R, np.random.default_rng(s), (s, nw, k, w, R, Tt, steps, dev, mode, info))
         out[mode] = (res, info)
         ctx.close()
         for name in ("PHI_DP_NOBLOCKS", "PHI_DP_BLOCK_STEPS", "PHI_SOLVE_DEVICE"): os.environ.pop(name, None)

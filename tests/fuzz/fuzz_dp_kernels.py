@@ -1,5 +1,6 @@
 """Randomised agreement of the DP kernels: event-driven (1 consumer wave / 2 waves / 4 waves, by walk count)
-against the every-vertex kernel (PHI_DP_DENSE=1) on random graphs.
+against the every-vertex kernel (PHI_DP_DENSE=1) on random graphs; on every graph and with either kernel one DP run with all
+weights 1 and one with Bernoulli 1/2 weights (Context.dp_probe) against the plain reference of tests/dp_ref.py.
 Usage (GPU box): python tests/fuzz/fuzz_dp_kernels.py SEED SECONDS [MIN_WALKS MAX_WALKS]  (default 2 257: all three kernels)"""
 import os, sys, time, numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -8,6 +9,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import phi_amd
 from graphgen import random_graph, mosaic_reads
 import test_gpu_parity as T
+import dp_ref
 seed0 = int(sys.argv[1]); t_end = time.time() + float(sys.argv[2])
 lo_w, hi_w = (int(sys.argv[3]), int(sys.argv[4])) if len(sys.argv) > 4 else (2, 257)
 s = seed0 * 100000; n = 0
@@ -26,6 +28,7 @@ while time.time() < t_end:
         ctx = phi_amd.Context(0); ctx.set_params(k=k, w=w, threshold=Tt, recombination=R)
         T._set_graph(ctx, g); ctx.add_reads(reads)
         res = ctx.solve()
+        dp_ref.check_probes(ctx, g, R, np.random.default_rng(s), (s, nw, k, w, R, Tt, mode))
         out[mode] = (res["objective"], res["upper_bound"], res["optimal"], res["n_in_model"], res["spectrum_size"])
         ctx.close()
     os.environ.pop("PHI_DP_DENSE", None)

@@ -87,3 +87,44 @@ def mosaic_reads(rng, g, n_reads=30, read_len=24, n_seg=2, err=0.0):
             r = r.translate(comp)[::-1]
         reads.append(r)
     return reads
+
+
+def closed_stretch_case(seed, n_sites, n_walks, k, frac):
+    """A chain of short bubbles (a site every ~4 bases, k-mers span two or more of them, w = 1: every k-mer an anchor that
+    no filter drops) with reads tiling the first `frac` of every walk: no entry there is clean of anchors, so no cut may
+    split that stretch of ~3 * n_sites * frac compact steps; behind it no anchor is matched and cuts abound."""
+    rng = np.random.default_rng(seed)
+    g = random_graph(rng, n_sites=n_sites, n_walks=n_walks, seg_len=(1, 3), alt_len=(1, 3), p_del=0.0)
+    reads = []
+    for h in range(g.n_walks):
+        s = walk_sequence(g, h)
+        reads += [s[a:a + 60] for a in range(0, int(len(s) * frac) - 60, 20)]
+    return g, reads, k
+
+
+def braided_graph(rng, n_sites=20, n_walks=6, allele_len=(4, 12)):
+    """Two alleles per site and no backbone between the sites: both alleles of a site lead to both alleles of the next, so
+    every vertex has two in-edges and a recombination can enter it over either (in random_graph a vertex is entered by
+    recombination over one in-edge only).  Every walk takes one allele per site, from a common first vertex to a common last."""
+    def rseq(n):
+        return bytes(rng.choice(list(b"ACGT"), size=n).tolist())
+    node_seq, adj = [rseq(int(rng.integers(allele_len[0], allele_len[1] + 1)))], [[]]
+    layers = [[0]]
+    for _ in range(n_sites):
+        layer = []
+        for _ in range(2):
+            node_seq.append(rseq(int(rng.integers(allele_len[0], allele_len[1] + 1))))
+            adj.append([])
+            layer.append(len(node_seq) - 1)
+        layers.append(layer)
+    node_seq.append(rseq(int(rng.integers(allele_len[0], allele_len[1] + 1))))
+    adj.append([])
+    layers.append([len(node_seq) - 1])
+    for a, b in zip(layers, layers[1:]):
+        for u in a:
+            adj[u] = list(b)
+    paths = [[int(layer[int(rng.integers(0, len(layer)))]) for layer in layers] for _ in range(n_walks)]
+    g = O.Graph(seg_names=[f"s{i + 1}" for i in range(len(node_seq))], node_seq=node_seq, adj=[sorted(a) for a in adj], paths=paths,
+                hap_names=[f"hap{h}.{h}" for h in range(n_walks)])
+    O.kahn(g)
+    return g

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import DATA, GOLDEN
-from graphgen import mosaic_reads, random_graph, walk_sequence
+from graphgen import closed_stretch_case as _closed_stretch_case, mosaic_reads, random_graph, walk_sequence
 
 pytestmark = pytest.mark.gpu
 
@@ -1669,19 +1669,6 @@ def test_novel_hash_log_spills_grows_and_starts_over(oracle, ctx_factory, monkey
     ctx.add_reads(reads[8000:])
     want = len(np.unique(np.concatenate(sk[8000:])))
     assert ctx.reads_stats()["n_distinct"] == want and ctx.solve()["spectrum_size"] == want
-
-
-def _closed_stretch_case(seed, n_sites, n_walks, k, frac):
-    """A chain of short bubbles (a site every ~4 bases, k-mers span two or more of them, w = 1: every k-mer an anchor that
-    no filter drops) with reads tiling the first `frac` of every walk: no entry there is clean of anchors, so no cut may
-    split that stretch of ~3 * n_sites * frac compact steps; behind it no anchor is matched and cuts abound."""
-    rng = np.random.default_rng(seed)
-    g = random_graph(rng, n_sites=n_sites, n_walks=n_walks, seg_len=(1, 3), alt_len=(1, 3), p_del=0.0)
-    reads = []
-    for h in range(g.n_walks):
-        s = walk_sequence(g, h)
-        reads += [s[a:a + 60] for a in range(0, int(len(s) * frac) - 60, 20)]
-    return g, reads, k
 
 
 @pytest.mark.parametrize("block_steps", ["1", "3", "16", None, "ring2048"])
