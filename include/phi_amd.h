@@ -686,6 +686,34 @@ int phi_gzip_header(const void *data, int64_t n, int64_t pos, int64_t *deflate_s
 /* CRC32 (the gzip one) of A followed by B, from crc(A), crc(B) and |B| */
 uint32_t phi_crc32_combine(uint32_t crc_a, uint32_t crc_b, int64_t len_b);
 
+/* BGZF written on a device, DESIGN.md 4.17: in[0, n) cut into runs of PHI_BGZF_BLOCK bytes (the last may be shorter), each
+ * compressed by one workgroup into one gzip member with the BGZF extra field (1f 8b 08 04, MTIME 0, XFL 0, OS ff, XLEN 6,
+ * "BC" 02 00, BSIZE = member size - 1; one raw DEFLATE stream; CRC32, ISIZE), then the 28-byte EOF block.  A block holds
+ * LZ77 copies (lengths up to 258, distances up to 32768, none reaching before the block's first byte) under a dynamic
+ * Huffman code built on the device from the block's own histogram, or is a stored block where that would not be smaller.
+ * The output is a function of the input and the flags alone.  cap, *out_size and "nothing copied when it does not fit" as
+ * for phi_inflate; phi_deflate_bgzf_bound(n) always fits.  n == 0 is valid (the EOF block alone, or nothing with
+ * PHI_DEFLATE_NO_EOF).  PHI_ERR_INVALID, with nothing launched, for n < 0, in == NULL with n > 0, or unknown flags.  Inputs
+ * beyond a batch of blocks (PHI_DEFLATE_BATCH from the environment, else PHI_DEFLATE_BATCH_DEFAULT) go through the device in
+ * batches, so device memory stays bounded.  info (may be NULL) is filled, its detail text on any error.  Needs no phi_ctx. */
+#define PHI_BGZF_BLOCK 65280           /* input bytes per block, as htslib cuts them */
+#define PHI_DEFLATE_NO_MATCH 1         /* literals only (tests: isolates the Huffman side) */
+#define PHI_DEFLATE_NO_EOF   2         /* leave out the 28-byte EOF block (outputs that are concatenated) */
+#define PHI_DEFLATE_BATCH_DEFAULT 512  /* blocks per batch */
+typedef struct {
+    int64_t in_bytes, out_bytes, blocks;
+    int64_t stored_blocks;             /* blocks written as stored because the Huffman form was not smaller */
+    int64_t matches, match_bytes;      /* LZ77 copies and the input bytes they cover (of the blocks not stored) */
+    double  device_ms;                 /* uploaded input -> finished output, as phi_inflate_info.device_ms, summed over the batches */
+    char    detail[192];
+} phi_deflate_info;
+int64_t phi_deflate_bgzf_bound(int64_t n);        /* the output never exceeds this */
+int phi_deflate_bgzf(int32_t device, const void *in, int64_t n, void *out, int64_t cap, int32_t flags,
+                     int64_t *out_size, phi_deflate_info *info);
+int phi_deflate_bgzf_alloc(int32_t device, const void *in, int64_t n, int32_t flags, void **out, int64_t *out_size,
+                           phi_deflate_info *info);   /* freed with phi_deflate_free */
+void phi_deflate_free(void *p);
+
 /* A gzip GFA split on the device: the file (RFC 1952, any number of members) is inflated on the context's
  * device, the walk field of every W-line -- everything after its 6th tab, tags included, by the host reader's line rules
  * (include/phi_host.h) -- stays there, laid out as phi_walk_text_upload lays it out (phi_walk_text_resolve follows as after

@@ -11,6 +11,7 @@
  *   phi_vcf_*        vcf2gfa.py (VCF + FASTA -> graph)              vcf2gfa.py:27-64, without vg / gfa2gbwt
  *   phi_hap_name     get_hap_name()                       src/misc.cpp:58-87
  *   phi_write_fasta  the FASTA writer                     src/ILP_index.cpp:1590-1598
+ *   phi_format_*     the FASTA and the calls as text in memory (for phi_deflate_bgzf of phi_amd.h)
  * The arrays phi_gfa_read returns are exactly the arguments of phi_set_graph (phi_amd.h).
  * All functions return 0 or a negative code and never call exit(); *err receives a message.
  */
@@ -211,11 +212,22 @@ int phi_write_fasta(const char *path, const char *name, const char *seq, int64_t
  *     contig  pos + 1  .  REF  ALT  .  PASS  PH=<ph[k]>  GT  1
  * (tabs; INFO is "." where ph is NULL or ph[k] is NULL or empty; the bytes of REF and ALT as they are, case kept).  A call
  * whose REF and ALT are the same bytes is not written and counted in *n_dropped; *n_written = the records written (either
- * may be NULL).  PHI_HOST_ERR_INVALID, with a message, for a path that ends in ".gz" (the project has no deflate writer:
- * nothing is written) and for a call with an empty allele; PHI_HOST_ERR_IO when the file cannot be written. */
+ * may be NULL).  PHI_HOST_ERR_INVALID, with a message, for a path that ends in ".gz" (this writer writes plain text and has no
+ * deflate of its own: nothing is written; compressed calls are the text of phi_format_calls_vcf through phi_deflate_bgzf of
+ * phi_amd.h, which is what PHI --bgzf and write_vcf(bgzf=True) do) and for a call with an empty allele; PHI_HOST_ERR_IO when
+ * the file cannot be written. */
 int phi_write_calls_vcf(const char *path, const char *contig, int64_t contig_len, const char *sample, int64_t n_calls, const int64_t *pos,
                         const int64_t *ref_off, const char *ref_bytes, const int64_t *alt_off, const char *alt_bytes, const char *const *ph,
                         int64_t *n_written, int64_t *n_dropped, char *err, int err_cap);
+
+/* The same two texts in memory, for the BGZF writer on the device (phi_deflate_bgzf, phi_amd.h): *out[0, *n) holds exactly the
+ * bytes phi_write_fasta / phi_write_calls_vcf write to their file; free it with phi_host_free_text.  phi_format_calls_vcf has
+ * phi_write_calls_vcf's refusals (the file name's aside) and its count of dropped REF = ALT calls. */
+int phi_format_fasta(const char *name, const char *seq, int64_t len, char **out, int64_t *n);
+int phi_format_calls_vcf(const char *contig, int64_t contig_len, const char *sample, int64_t n_calls, const int64_t *pos, const int64_t *ref_off,
+                         const char *ref_bytes, const int64_t *alt_off, const char *alt_bytes, const char *const *ph, char **out, int64_t *n,
+                         int64_t *n_written, int64_t *n_dropped, char *err, int err_cap);
+void phi_host_free_text(char *p);
 
 #ifdef __cplusplus
 }

@@ -40,6 +40,7 @@ SYMBOLS = [
     "phi_prefix_sums",
     "phi_reads_bam_begin", "phi_add_reads_bam", "phi_add_reads_bam_parked", "phi_reads_bam_end", "phi_reads_bam_last_batch",
     "phi_calls_path", "phi_calls_walk", "phi_calls_stats",
+    "phi_deflate_bgzf_bound", "phi_deflate_bgzf", "phi_deflate_bgzf_alloc", "phi_deflate_free",
 ]
 PHI_PANEL_RETAIN = 1
 PHI_PANEL_KEEP_READS = 2
@@ -47,6 +48,10 @@ PHI_SCOUT_MAX_WALKS = 65535
 PHI_LADDER_MAX_LEVELS = 16
 PHI_INFLATE_NO_FINDER = 1
 PHI_INFLATE_CHUNK_DEFAULT = 64 << 10          # include/phi_amd.h
+PHI_BGZF_BLOCK = 65280
+PHI_DEFLATE_NO_MATCH = 1
+PHI_DEFLATE_NO_EOF = 2
+PHI_DEFLATE_BATCH_DEFAULT = 512
 
 
 class PhiIndexInfo(C.Structure):
@@ -128,6 +133,11 @@ class PhiResult(C.Structure):
 
 class PhiInflateInfo(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("in_bytes", "out_bytes", "members", "chunks", "confirmed", "redecoded", "marker_bytes")] + [
+        ("device_ms", C.c_double), ("detail", C.c_char * 192)]
+
+
+class PhiDeflateInfo(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("in_bytes", "out_bytes", "blocks", "stored_blocks", "matches", "match_bytes")] + [
         ("device_ms", C.c_double), ("detail", C.c_char * 192)]
 
 
@@ -259,6 +269,12 @@ def load():
     L.phi_inflate_alloc.argtypes = [i32, vp, i64, i64, i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(PhiInflateInfo)]
     L.phi_inflate_free.argtypes = [vp]
     L.phi_inflate_free.restype = None
+    L.phi_deflate_bgzf_bound.argtypes = [i64]
+    L.phi_deflate_bgzf_bound.restype = i64
+    L.phi_deflate_bgzf.argtypes = [i32, vp, i64, vp, i64, i32, C.POINTER(i64), C.POINTER(PhiDeflateInfo)]
+    L.phi_deflate_bgzf_alloc.argtypes = [i32, vp, i64, i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(PhiDeflateInfo)]
+    L.phi_deflate_free.argtypes = [vp]
+    L.phi_deflate_free.restype = None
     L.phi_text_park_gzip_begin.argtypes = [vp, i64]
     L.phi_text_park_gzip_add.argtypes = [vp, vp, i64]
     L.phi_text_park_gzip_end.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(PhiInflateInfo)]
@@ -270,7 +286,7 @@ def load():
     L.phi_gfa_gzip_free.restype = None
     for name in SYMBOLS:
         f = getattr(L, name)          # AttributeError here = the library does not export the ABI
-        if f.restype is C.c_int and name not in ("phi_strerror", "phi_last_error", "phi_ctx_destroy", "phi_crc32_combine", "phi_inflate_free", "phi_gfa_gzip_free"):
+        if f.restype is C.c_int and name not in ("phi_strerror", "phi_last_error", "phi_ctx_destroy", "phi_crc32_combine", "phi_inflate_free", "phi_gfa_gzip_free", "phi_deflate_bgzf_bound", "phi_deflate_free"):
             f.restype = C.c_int
     _lib = L
     return L

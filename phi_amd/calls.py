@@ -39,11 +39,12 @@ def ph_names(calls, path_hap, hap_names):
     return [hap_names[int(path_hap[int(i) + 1])] for i in calls["anchor"]]
 
 
-def write_vcf(path, calls, contig, contig_len, sample, ph=None):
+def write_vcf(path, calls, contig, contig_len, sample, ph=None, bgzf=False, device=0):
     """The calls as plain-text VCFv4.2 (phi_write_calls_vcf of include/phi_host.h): one haploid sample with genotype 1, POS
     1-based, PH=<ph[k]> in INFO where ph (a list of names, one per call) is given.  Calls whose REF and ALT are the same bytes
-    are dropped.  Returns (records written, calls dropped).  A name ending in .gz is refused (HostError): there is no
-    deflate writer."""
+    are dropped.  Returns (records written, calls dropped).  A name ending in .gz is refused (HostError: this writer has no
+    deflate of its own) unless bgzf is set: then the same text (phi_format_calls_vcf) is compressed into BGZF blocks on
+    `device` (deflate_bgzf) and written under the name as given."""
     from .ilp_index import HostError, host_lib
     L = host_lib()
     n = int(len(calls["pos"]))
@@ -58,6 +59,20 @@ def write_vcf(path, calls, contig, contig_len, sample, ph=None):
         names = (C.c_char_p * max(n, 1))(*[s.encode() if isinstance(s, str) else s for s in ph])
     nw, nd = C.c_int64(), C.c_int64()
     err = C.create_string_buffer(512)
+    if bgzf:
+        text, size = C.c_void_p(), C.c_int64()
+        rc = L.phi_format_calls_vcf(contig.encode(), int(contig_len), sample.encode(), n, pos.ctypes.data, ro.ctypes.data, rb, ao.ctypes.data, ab,
+                                    names, C.byref(text), C.byref(size), C.byref(nw), C.byref(nd), err, 512)
+        if rc:
+            raise HostError(rc, err.value.decode())
+        try:
+            plain = C.string_at(text, size.value)
+        finally:
+            L.phi_host_free_text(text)
+        from .context import deflate_bgzf
+        with open(path, "wb") as f:
+            f.write(deflate_bgzf(plain, device=device))
+        return nw.value, nd.value
     rc = L.phi_write_calls_vcf(os.fsencode(path), contig.encode(), int(contig_len), sample.encode(), n, pos.ctypes.data, ro.ctypes.data, rb,
                                ao.ctypes.data, ab, names, C.byref(nw), C.byref(nd), err, 512)
     if rc:

@@ -872,6 +872,27 @@ def inflate(data, device=0, chunk_bytes=0, finder=True, as_array=False):
     return (out if as_array else out.tobytes()), _info(info)
 
 
+def deflate_bgzf(data, device=0, match=True, eof=True, with_info=False):
+    """data (bytes or a uint8 array) as a BGZF file written on `device` (include/phi_amd.h phi_deflate_bgzf_alloc): one gzip
+    member per 65 280 input bytes, then the 28-byte EOF block (eof=False leaves it out, for outputs that are concatenated).
+    match=False writes literals only (a test knob).  Returns the file as bytes, or (bytes, info) with with_info: info a
+    dict of phi_deflate_info.  The bytes are a function of data and the two flags alone."""
+    L = _capi.load()
+    buf = np.frombuffer(data, np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, np.uint8)
+    flags = (0 if match else _capi.PHI_DEFLATE_NO_MATCH) | (0 if eof else _capi.PHI_DEFLATE_NO_EOF)
+    p, size, info = C.c_void_p(), C.c_int64(), _capi.PhiDeflateInfo()
+    rc = L.phi_deflate_bgzf_alloc(device, _ptr(buf) if len(buf) else None, len(buf), flags, C.byref(p), C.byref(size), C.byref(info))
+    if rc:
+        raise PhiError(rc, info.detail.decode())
+    try:
+        out = C.string_at(p, size.value) if size.value else b""
+    finally:
+        L.phi_deflate_free(p)
+    if not with_info:
+        return out
+    return out, {n: getattr(info, n) for n, _ in _capi.PhiDeflateInfo._fields_ if n != "detail"}
+
+
 def gzip_header(data, pos=0):
     """The offset of the deflate data of the gzip member header at data[pos:] (PhiError when there is none)."""
     L = _capi.load()

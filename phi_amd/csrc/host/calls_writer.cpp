@@ -1,7 +1,9 @@
 // calls_writer.cpp -- the variant calls of phi_calls_path / phi_calls_walk (include/phi_amd.h) written as plain-text VCFv4.2.
 // The reference writes no VCF (its one product is the FASTA of ILP_index.cpp:1590-1598); the file serves the comparison it
-// makes the other way round with `bcftools consensus` (data/run_PG.py:54-60).  Plain host code: no deflate writer.
+// makes the other way round with `bcftools consensus` (data/run_PG.py:54-60).  Plain host code.  The text
+// is also handed out in memory (phi_format_calls_vcf, phi_format_fasta) for the device's BGZF writer (phi_deflate_bgzf, phi_amd.h).
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 #include <string>
 #include "../../../include/phi_host.h"
@@ -14,9 +16,78 @@ int fail(char *err, int err_cap, int code, const std::string &msg)
     return code;
 }
 
+// the file's text; the arguments are checked by the callers
+int format_calls(std::string &out, const char *contig, int64_t contig_len, const char *sample, int64_t n_calls, const int64_t *pos, const int64_t *ref_off,
+                 const char *ref_bytes, const int64_t *alt_off, const char *alt_bytes, const char *const *ph, int64_t *n_written, int64_t *n_dropped,
+                 char *err, int err_cap, const char *who)
+{
+    if (!contig || !sample || n_calls < 0 || (n_calls > 0 && (!pos || !ref_off || !alt_off || !ref_bytes || !alt_bytes)))
+        return fail(err, err_cap, PHI_HOST_ERR_INVALID, std::string(who) + ": null argument");
+    for (int64_t k = 0; k < n_calls; k++)
+        if (ref_off[k + 1] <= ref_off[k] || alt_off[k + 1] <= alt_off[k] || pos[k] < 0)
+            return fail(err, err_cap, PHI_HOST_ERR_INVALID, std::string(who) + ": call " + std::to_string(k) + " has an empty allele or a negative position");
+    out += "##fileformat=VCFv4.2\n##source=phi_amd\n##contig=<ID=";
+    out += contig;
+    out += ",length=" + std::to_string((long long)contig_len) + ">\n";
+    out += "##INFO=<ID=PH,Number=1,Type=String,Description=\"Panel haplotype the inferred path follows through the call\">\n";
+    out += "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n";
+    out += "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t";
+    out += sample;
+    out += '\n';
+    int64_t nw = 0, nd = 0;
+    for (int64_t k = 0; k < n_calls; k++) {
+        const size_t rn = (size_t)(ref_off[k + 1] - ref_off[k]), an = (size_t)(alt_off[k + 1] - alt_off[k]);
+        const char *r = ref_bytes + ref_off[k], *a = alt_bytes + alt_off[k];
+        if (rn == an && memcmp(r, a, rn) == 0) { nd++; continue; }      // other vertices, the same sequence: no variant
+        out += contig;
+        out += '\t';
+        out += std::to_string((long long)pos[k] + 1);
+        out += "\t.\t";
+        out.append(r, rn);
+        out += '\t';
+        out.append(a, an);
+        const char *name = ph ? ph[k] : nullptr;
+        if (name && *name) { out += "\t.\tPASS\tPH="; out += name; out += "\tGT\t1\n"; }
+        else out += "\t.\tPASS\t.\tGT\t1\n";
+        nw++;
+    }
+    if (n_written) *n_written = nw;
+    if (n_dropped) *n_dropped = nd;
+    return PHI_HOST_OK;
+}
+
+int hand_over(const std::string &text, char **out, int64_t *n)
+{
+    char *p = (char *)malloc(text.size() ? text.size() : 1);
+    if (!p) return PHI_HOST_ERR_IO;
+    memcpy(p, text.data(), text.size());
+    *out = p;
+    *n = (int64_t)text.size();
+    return PHI_HOST_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int phi_format_calls_vcf(const char *contig, int64_t contig_len, const char *sample, int64_t n_calls, const int64_t *pos, const int64_t *ref_off,
+                         const char *ref_bytes, const int64_t *alt_off, const char *alt_bytes, const char *const *ph, char **out, int64_t *n,
+                         int64_t *n_written, int64_t *n_dropped, char *err, int err_cap)
+{
+    if (n_written) *n_written = 0;
+    if (n_dropped) *n_dropped = 0;
+    if (!out || !n) return fail(err, err_cap, PHI_HOST_ERR_INVALID, "phi_format_calls_vcf: null argument");
+    *out = nullptr;
+    *n = 0;
+    std::string text;
+    int64_t nw = 0, nd = 0;
+    const int rc = format_calls(text, contig, contig_len, sample, n_calls, pos, ref_off, ref_bytes, alt_off, alt_bytes, ph, &nw, &nd, err, err_cap, "phi_format_calls_vcf");
+    if (rc) return rc;
+    if (hand_over(text, out, n)) return fail(err, err_cap, PHI_HOST_ERR_IO, "phi_format_calls_vcf: out of memory");
+    if (n_written) *n_written = nw;
+    if (n_dropped) *n_dropped = nd;
+    return PHI_HOST_OK;
+}
 
 int phi_write_calls_vcf(const char *path, const char *contig, int64_t contig_len, const char *sample, int64_t n_calls, const int64_t *pos,
                         const int64_t *ref_off, const char *ref_bytes, const int64_t *alt_off, const char *alt_bytes, const char *const *ph,
@@ -24,37 +95,44 @@ int phi_write_calls_vcf(const char *path, const char *contig, int64_t contig_len
 {
     if (n_written) *n_written = 0;
     if (n_dropped) *n_dropped = 0;
-    if (!path || !contig || !sample || n_calls < 0 || (n_calls > 0 && (!pos || !ref_off || !alt_off || !ref_bytes || !alt_bytes)))
-        return fail(err, err_cap, PHI_HOST_ERR_INVALID, "phi_write_calls_vcf: null argument");
+    if (!path) return fail(err, err_cap, PHI_HOST_ERR_INVALID, "phi_write_calls_vcf: null argument");
     const size_t pn = strlen(path);
     if (pn >= 3 && strcmp(path + pn - 3, ".gz") == 0)
-        return fail(err, err_cap, PHI_HOST_ERR_INVALID, std::string("cannot write ") + path + ": the calls are written as plain text (there is no deflate writer); give a name that does not end in .gz");
-    for (int64_t k = 0; k < n_calls; k++)
-        if (ref_off[k + 1] <= ref_off[k] || alt_off[k + 1] <= alt_off[k] || pos[k] < 0)
-            return fail(err, err_cap, PHI_HOST_ERR_INVALID, "phi_write_calls_vcf: call " + std::to_string(k) + " has an empty allele or a negative position");
+        return fail(err, err_cap, PHI_HOST_ERR_INVALID, std::string("cannot write ") + path + ": this writer writes plain text and has no deflate of its own; give a name that does not end in .gz, or compress the text of phi_format_calls_vcf with phi_deflate_bgzf (PHI --bgzf, write_vcf(bgzf=True))");
+    std::string text;
+    int64_t nw = 0, nd = 0;
+    const int rc = format_calls(text, contig, contig_len, sample, n_calls, pos, ref_off, ref_bytes, alt_off, alt_bytes, ph, &nw, &nd, err, err_cap, "phi_write_calls_vcf");
+    if (rc) return rc;
     FILE *fp = fopen(path, "w");
     if (!fp) return fail(err, err_cap, PHI_HOST_ERR_IO, std::string("cannot write ") + path);
-    fprintf(fp, "##fileformat=VCFv4.2\n##source=phi_amd\n##contig=<ID=%s,length=%lld>\n", contig, (long long)contig_len);
-    fputs("##INFO=<ID=PH,Number=1,Type=String,Description=\"Panel haplotype the inferred path follows through the call\">\n", fp);
-    fputs("##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n", fp);
-    fprintf(fp, "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t%s\n", sample);
-    int64_t nw = 0, nd = 0;
-    bool ok = true;
-    for (int64_t k = 0; k < n_calls && ok; k++) {
-        const size_t rn = (size_t)(ref_off[k + 1] - ref_off[k]), an = (size_t)(alt_off[k + 1] - alt_off[k]);
-        const char *r = ref_bytes + ref_off[k], *a = alt_bytes + alt_off[k];
-        if (rn == an && memcmp(r, a, rn) == 0) { nd++; continue; }      // other vertices, the same sequence: no variant
-        fprintf(fp, "%s\t%lld\t.\t", contig, (long long)pos[k] + 1);
-        ok = fwrite(r, 1, rn, fp) == rn && fputc('\t', fp) != EOF && fwrite(a, 1, an, fp) == an;
-        const char *name = ph ? ph[k] : nullptr;
-        if (name && *name) fprintf(fp, "\t.\tPASS\tPH=%s\tGT\t1\n", name);
-        else fputs("\t.\tPASS\t.\tGT\t1\n", fp);
-        nw++;
-    }
+    const bool ok = fwrite(text.data(), 1, text.size(), fp) == text.size();
     if (fclose(fp) != 0 || !ok) return fail(err, err_cap, PHI_HOST_ERR_IO, std::string("cannot write ") + path);
     if (n_written) *n_written = nw;
     if (n_dropped) *n_dropped = nd;
     return PHI_HOST_OK;
 }
+
+// exactly the bytes phi_write_fasta (reads_reader.cpp) writes: ">" name " LN:" len, then 80-column lines
+int phi_format_fasta(const char *name, const char *seq, int64_t len, char **out, int64_t *n)
+{
+    if (!name || !out || !n || len < 0 || (len > 0 && !seq)) return PHI_HOST_ERR_INVALID;
+    const std::string head = std::string(">") + name + " LN:" + std::to_string((long long)len) + "\n";
+    const int64_t lines = (len + 79) / 80, total = (int64_t)head.size() + len + lines;
+    char *p = (char *)malloc((size_t)(total > 0 ? total : 1));
+    if (!p) return PHI_HOST_ERR_IO;
+    memcpy(p, head.data(), head.size());
+    char *o = p + head.size();
+    for (int64_t j = 0; j < len; j += 80) {
+        const int64_t k = len - j < 80 ? len - j : 80;
+        memcpy(o, seq + j, (size_t)k);
+        o[k] = '\n';
+        o += k + 1;
+    }
+    *out = p;
+    *n = total;
+    return PHI_HOST_OK;
+}
+
+void phi_host_free_text(char *p) { free(p); }
 
 }  // extern "C"

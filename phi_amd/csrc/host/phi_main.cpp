@@ -11,6 +11,7 @@
 //                                                             (data/chop_graph.sh:46-66); -o 'out.{panel}.fa': one FASTA per panel
 //         [--calls FILE [--calls-ref NAME] [--calls-contig NAME]]   the inferred haplotype as variant calls against a reference walk
 //                                                             (plain-text VCF; one --calls per -o, in order, same placeholder)
+//         [--bgzf]                                            every -o and --calls file as BGZF, compressed on the device
 //   ./PHI -g <target.gfa> -r a.fq -o a.fa -r b.fq -o b.fa ...      several read sets against ONE graph: the graph is parsed and
 //         indexed once (the reference's harness runs PHI once per sample x coverage on the same graph,
 //         data/run_batch_4_miqp.py:31-46), every job prints the log of a run of its own and writes its own FASTA
@@ -141,7 +142,8 @@ static void usage(FILE *fp, int k, int w, int R, int q, int m, float T, int t, c
     fprintf(fp, "    -r INT       Read [%s]\n", r);
     fprintf(fp, "    -o INT       Output haplotype [%s]\n", o);
     fprintf(fp, "    -d bool      Debug mode [%d]\n", d);
-    fprintf(fp, "    --calls FILE           the inferred haplotype as variant calls (plain-text VCFv4.2, no .gz) against a reference walk of\n");
+    fprintf(fp, "    --bgzf                 every -o and --calls file compressed into BGZF blocks on the GPU; names are taken as given\n");
+    fprintf(fp, "    --calls FILE           the inferred haplotype as variant calls (plain-text VCFv4.2; .gz only with --bgzf) against a reference walk of\n");
     fprintf(fp, "                           the graph; one per -o, in order, with the same {cov} / {panel} placeholder where -o takes one.\n");
     fprintf(fp, "                           The rule is this program's own (not vg deconstruct's): nothing is trimmed or left-aligned\n");
     fprintf(fp, "    --calls-ref NAME       the reference walk, named as the log names walks (SAMPLE.HAP); required with -g, REF.0 with --vcf;\n");
@@ -184,6 +186,7 @@ struct Options {
     // (phi_calls_path, phi_write_calls_vcf; no reference counterpart: for the comparison of data/run_PG.py:54-60); one per -o
     std::vector<std::string> calls_files;
     std::string calls_ref, calls_contig;
+    bool bgzf = false;                                        // --bgzf: every -o and --calls file compressed into BGZF blocks on the device
     bool panel() const { return have_keep || have_drop || !panel_sizes.empty() || panel_auto > 0; }
     int argc = 0;
     char **argv = nullptr;
@@ -1109,7 +1112,15 @@ struct Driver {
             Stage st("FASTA write");
             std::unique_ptr<char[]> seq(new char[(size_t)(res.hap_len > 0 ? res.hap_len : 1)]);      // (not zero-filled: every byte is written)
             if ((rc = phi_path_sequence(ctx, seq.get(), res.hap_len))) return fail_on(ctx, "sequence", rc);
-            if (phi_write_fasta(hap_file.c_str(), hap_name, seq.get(), res.hap_len) != PHI_HOST_OK) return fail("[E::main] cannot write %s\n", hap_file.c_str());
+            if (o.bgzf) {
+                char *text = nullptr;
+                int64_t n_text = 0;
+                if (phi_format_fasta(hap_name, seq.get(), res.hap_len, &text, &n_text) != PHI_HOST_OK) return fail("[E::main] cannot format %s\n", hap_file.c_str());
+                seq.reset();
+                const int wrc = write_bgzf(hap_file, text, n_text);
+                phi_host_free_text(text);
+                if (wrc) return 1;
+            } else if (phi_write_fasta(hap_file.c_str(), hap_name, seq.get(), res.hap_len) != PHI_HOST_OK) return fail("[E::main] cannot write %s\n", hap_file.c_str());
         }
         stamp("ILP_function"); fprintf(stderr, "Haplotype of size: %d written to: %s\n", (int)res.hap_len, hap_file.c_str());
         if (!o.calls_files.empty() && write_calls(res)) return 1;
@@ -1144,6 +1155,24 @@ struct Driver {
         return fail("[E::main] --calls-ref %s: the panel does not keep this walk, and calls are made against no other; keep it with --panel-always %s (or --keep-samples)\n",
                     want.c_str(), sample_of(want.c_str()).c_str());
     }
+    // --bgzf: text[0, n) compressed into BGZF blocks on the command's device (phi_deflate_bgzf), written under the name as given
+    int write_bgzf(const std::string &file, const char *text, int64_t n)
+    {
+        void *z = nullptr;
+        int64_t zn = 0;
+        phi_deflate_info di;
+        const int rc = phi_deflate_bgzf_alloc(devices[0], text, n, 0, &z, &zn, &di);
+        if (rc) return fail("[E::main] --bgzf %s: %s: %s\n", file.c_str(), phi_strerror(rc), di.detail);
+        FILE *fp = fopen(file.c_str(), "wb");
+        bool ok = fp && fwrite(z, 1, (size_t)zn, fp) == (size_t)zn;
+        if (fp && fclose(fp) != 0) ok = false;
+        phi_deflate_free(z);
+        if (!ok) return fail("[E::main] cannot write %s\n", file.c_str());
+        stamp("main");
+        fprintf(stderr, "BGZF: %lld bytes written to %s, %lld bytes of text in %lld blocks (%lld stored); %.3f ms on device %d\n", (long long)zn, file.c_str(),
+                (long long)di.in_bytes, (long long)di.blocks, (long long)di.stored_blocks, di.device_ms, devices[0]);
+        return 0;
+    }
     // the path of the solve just reported as calls against the reference walk, written beside the FASTA
     int write_calls(const phi_result &res)
     {
@@ -1165,8 +1194,17 @@ struct Driver {
         for (int64_t k = 0; k < cl.n_calls; k++) ph[(size_t)k] = walk_name(res.path_hap[cl.anchor[k] + 1]);
         int64_t n_written = 0, n_dropped = 0;
         char werr[512] = "";
-        if (phi_write_calls_vcf(file.c_str(), contig.c_str(), contig_len, hap_name, cl.n_calls, cl.pos, cl.ref_off, cl.ref_bytes, cl.alt_off, cl.alt_bytes,
-                                ph.data(), &n_written, &n_dropped, werr, sizeof werr) != PHI_HOST_OK)
+        if (o.bgzf) {
+            char *text = nullptr;
+            int64_t n_text = 0;
+            if (phi_format_calls_vcf(contig.c_str(), contig_len, hap_name, cl.n_calls, cl.pos, cl.ref_off, cl.ref_bytes, cl.alt_off, cl.alt_bytes, ph.data(), &text, &n_text,
+                                     &n_written, &n_dropped, werr, sizeof werr) != PHI_HOST_OK)
+                return fail("[E::main] %s\n", werr[0] ? werr : "cannot format the calls");
+            const int wrc = write_bgzf(file, text, n_text);
+            phi_host_free_text(text);
+            if (wrc) return 1;
+        } else if (phi_write_calls_vcf(file.c_str(), contig.c_str(), contig_len, hap_name, cl.n_calls, cl.pos, cl.ref_off, cl.ref_bytes, cl.alt_off, cl.alt_bytes,
+                                       ph.data(), &n_written, &n_dropped, werr, sizeof werr) != PHI_HOST_OK)
             return fail("[E::main] %s\n", werr[0] ? werr : "cannot write the calls");
         stamp("main");
         fprintf(stderr, "Calls: %lld written to %s, %lld dropped as REF = ALT; called span [%lld,%lld) of %s (%lld bases), [%lld,%lld) of the haplotype\n",
@@ -1395,7 +1433,7 @@ int main(int argc, char *argv[])
                                            {"keep-samples", required_argument, 0, 311}, {"drop-samples", required_argument, 0, 312}, {"panels", required_argument, 0, 313},
                                            {"panel-seed", required_argument, 0, 314}, {"panel-always", required_argument, 0, 315},
                                            {"panel-auto", required_argument, 0, 316}, {"panel-blocks", required_argument, 0, 317},
-                                           {"calls", required_argument, 0, 318}, {"calls-ref", required_argument, 0, 319}, {"calls-contig", required_argument, 0, 320}, {0, 0, 0, 0}};
+                                           {"calls", required_argument, 0, 318}, {"calls-ref", required_argument, 0, 319}, {"calls-contig", required_argument, 0, 320}, {"bgzf", no_argument, 0, 321}, {0, 0, 0, 0}};
     int c;
     std::string gfa_arg, vcf_arg;
     // main.cpp:38 declares -h with an argument; a bare -h falls into the usage branch either way
@@ -1460,6 +1498,7 @@ int main(int argc, char *argv[])
         else if (c == 318) o.calls_files.push_back(optarg);
         else if (c == 319) o.calls_ref = optarg;
         else if (c == 320) o.calls_contig = optarg;
+        else if (c == 321) o.bgzf = true;
         else if (c == 304) o.shard_min_bases = std::max<long long>(1, atoll(optarg));
         else if (c == 303) {                                   // --devices 0,1,2,...: shard the reads over these GPUs
             o.devices.clear();
@@ -1516,7 +1555,7 @@ int main(int argc, char *argv[])
         if (o.calls_files.size() != o.hap_files.size()) { fprintf(stderr, "[E::main] %zu --calls but %zu -o: one --calls per -o, paired in order (-r a.fq -o a.fa --calls a.vcf -r b.fq -o b.fa --calls b.vcf ...), or none at all\n", o.calls_files.size(), o.hap_files.size()); return 1; }
         if (!o.from_vcf && o.calls_ref.empty()) { fprintf(stderr, "[E::main] --calls with -g needs --calls-ref NAME: the walk the calls are made against, named as the log names walks (SAMPLE.HAP)\n"); return 1; }
         for (const std::string &f : o.calls_files) {
-            if (f.size() >= 3 && f.compare(f.size() - 3, 3, ".gz") == 0) { fprintf(stderr, "[E::main] --calls %s: the calls are written as plain text (there is no deflate writer); give a name that does not end in .gz\n", f.c_str()); return 1; }
+            if (!o.bgzf && f.size() >= 3 && f.compare(f.size() - 3, 3, ".gz") == 0) { fprintf(stderr, "[E::main] --calls %s: without --bgzf the calls are written as plain text (no deflate); give a name that does not end in .gz, or add --bgzf\n", f.c_str()); return 1; }
             if (o.cov.size() > 1 && f.find("{cov}") == std::string::npos) { fprintf(stderr, "[E::main] --coverage with several coverages: --calls must contain {cov} (got %s), e.g. --calls 'out.{cov}x.vcf'\n", f.c_str()); return 1; }
             if (o.panel_sizes.size() > 1 && f.find("{panel}") == std::string::npos) { fprintf(stderr, "[E::main] --panels with several sizes: --calls must contain {panel} (got %s), e.g. --calls 'out.{panel}.vcf'\n", f.c_str()); return 1; }
         }

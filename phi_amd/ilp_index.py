@@ -36,6 +36,7 @@ HOST_SYMBOLS = [
     "phi_vcf_parse_gt", "phi_vcf_build", "phi_vcf_n_units", "phi_vcf_unit_first", "phi_vcf_n_real_sites", "phi_vcf_site_backbone",
     "phi_vcf_site_allele0", "phi_vcf_n_kept_haps", "phi_vcf_choice",
     "phi_bam_header", "phi_panel_choose", "phi_write_calls_vcf",
+    "phi_format_fasta", "phi_format_calls_vcf", "phi_host_free_text",
 ]
 PHI_HOST_NEED_MORE = -6
 
@@ -124,6 +125,11 @@ def host_lib():
     L.phi_write_fasta.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int64]
     L.phi_write_calls_vcf.argtypes = [C.c_char_p, C.c_char_p, C.c_int64, C.c_char_p, C.c_int64, vp, vp, vp, vp, vp, vp,
                                       C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_char_p, C.c_int]
+    L.phi_format_fasta.argtypes = [C.c_char_p, C.c_char_p, C.c_int64, C.POINTER(vp), C.POINTER(C.c_int64)]
+    L.phi_format_calls_vcf.argtypes = [C.c_char_p, C.c_int64, C.c_char_p, C.c_int64, vp, vp, vp, vp, vp, vp, C.POINTER(vp), C.POINTER(C.c_int64),
+                                       C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_char_p, C.c_int]
+    L.phi_host_free_text.restype = None
+    L.phi_host_free_text.argtypes = [vp]
     L.phi_bam_header.argtypes = [vp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_char_p, C.c_int]
     L.phi_panel_choose.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int32, vp, vp]
     for n in HOST_SYMBOLS:
@@ -594,6 +600,7 @@ class ILP_index:
         self.threshold = 1.0
         self.is_mixed = True
         self.max_occ = 5000
+        self.bgzf = False               # the FASTA compressed into BGZF blocks on the device (the command line's --bgzf), the name as given
         self.chop = None                # N: segments are cut into pieces of at most N bases first (data/chop_graph.sh:3 `hal2vg --chop 30`)
         self.graph = None
         self.result = None
@@ -685,9 +692,22 @@ class ILP_index:
         print(f"Recombination count: {res['recombination_count']}", file=self.log)
         print("Recombined haplotypes: " + self.recombined_segments(res), file=self.log)
         L = host_lib()
-        rc = L.phi_write_fasta(os.fsencode(self.hap_file), self.hap_name.encode(), hap, len(hap))
-        if rc:
-            raise HostError(rc, f"cannot write {self.hap_file}")
+        if self.bgzf:
+            text, size = C.c_void_p(), C.c_int64()
+            rc = L.phi_format_fasta(self.hap_name.encode(), hap, len(hap), C.byref(text), C.byref(size))
+            if rc:
+                raise HostError(rc, f"cannot format {self.hap_file}")
+            try:
+                from .context import deflate_bgzf
+                packed = deflate_bgzf(np.ctypeslib.as_array(C.cast(text, C.POINTER(C.c_uint8)), shape=(size.value,)), device=self.device)
+            finally:
+                L.phi_host_free_text(text)
+            with open(self.hap_file, "wb") as f:
+                f.write(packed)
+        else:
+            rc = L.phi_write_fasta(os.fsencode(self.hap_file), self.hap_name.encode(), hap, len(hap))
+            if rc:
+                raise HostError(rc, f"cannot write {self.hap_file}")
         self._stamp(f"Haplotype of size: {len(hap)} written to: {self.hap_file}")
         return res
 
@@ -730,6 +750,7 @@ def main(argv=None):
     ap.add_argument("-t", type=int, default=4)
     ap.add_argument("-d", type=int, default=0)
     ap.add_argument("--chop", type=int, default=None)
+    ap.add_argument("--bgzf", action="store_true")
     a = ap.parse_args(argv)
     idx = ILP_index(a.g)
     idx.read_gfa()
@@ -738,6 +759,7 @@ def main(argv=None):
     idx.k_mer, idx.window, idx.recombination = a.k, a.w, a.R
     idx.is_qclp, idx.threshold, idx.is_mixed = a.q, a.T, bool(a.m)
     idx.chop = a.chop
+    idx.bgzf = a.bgzf
     reads = []
     idx.read_ip_reads(reads, a.r)
     idx.ILP_function(reads)
