@@ -26,14 +26,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
-#include <stdarg.h>
-#include <stdio.h>
 #include <stdlib.h>
 #include <algorithm>
 #include <vector>
 #include "../../include/phi_amd.h"
 #include "phi_ctx.h"
 #include "phi_wave.h"
+#include "dev_run.h"
 #include "deflate_codes.h"
 
 #define DFL_T 256                       // threads per workgroup = positions per tile = segments per block
@@ -162,8 +161,8 @@ __global__ void __launch_bounds__(DFL_T) phi_deflate_block_kernel(const uint8_t 
         L.hist_pre[tid] = 0;
         if (tid < 32) L.hist_dist[tid] = 0;
         {
-            uint32_t c = (uint32_t)tid;
-            for (int k = 0; k < 8; k++) c = (c >> 1) ^ (0xEDB88320u & (0u - (c & 1u)));
+            uint32_t c = (uint32_t)tid;                         // dfl_crc_byte, written out: the call compiles to other code
+            for (int k = 0; k < 8; k++) c = (c >> 1) ^ (DFL_CRC_POLY & (0u - (c & 1u)));
             L.crc_tab[tid] = c;
         }
         if (tid == 0) { L.matches = 0; L.match_bytes = 0; L.crc = 0; }
@@ -392,40 +391,6 @@ __global__ void __launch_bounds__(256) phi_deflate_gather_kernel(const uint8_t *
 
 const uint8_t BGZF_EOF[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 
-struct Dev {
-    std::vector<void *> bufs;
-    hipStream_t st = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ~Dev()
-    {
-        if (st) (void)hipStreamSynchronize(st);
-        for (void *p : bufs) (void)hipFree(p);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-        if (st) (void)hipStreamDestroy(st);
-    }
-    template <class T> T *alloc(size_t bytes)
-    {
-        void *p = nullptr;
-        if (hipMalloc(&p, std::max<size_t>(bytes, 16)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-        bufs.push_back(p);
-        if (phi_dev_poison(p, std::max<size_t>(bytes, 16))) return nullptr;
-        return (T *)p;
-    }
-};
-
-int fail(phi_deflate_info *info, int code, const char *fmt, ...) __attribute__((format(printf, 3, 4)));
-int fail(phi_deflate_info *info, int code, const char *fmt, ...)
-{
-    if (info) {
-        va_list ap;
-        va_start(ap, fmt);
-        vsnprintf(info->detail, sizeof(info->detail), fmt, ap);
-        va_end(ap);
-    }
-    return code;
-}
-
 int64_t batch_blocks()
 {
     const char *e = getenv("PHI_DEFLATE_BATCH");
@@ -434,9 +399,6 @@ int64_t batch_blocks()
 }
 
 int64_t n_blocks(int64_t n) { return (n + PHI_BGZF_BLOCK - 1) / PHI_BGZF_BLOCK; }
-
-#define DCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(info, PHI_ERR_DEVICE, "%s: %s", #call, hipGetErrorString(e_)); } while (0)
-#define DALLOC(var, T, bytes) T *var = dev.alloc<T>(bytes); if (!var) return fail(info, PHI_ERR_NOMEM, "device allocation of %zu bytes failed", (size_t)(bytes))
 
 int check_args(const void *in, int64_t n, int32_t flags, int64_t *out_size, phi_deflate_info *info)
 {

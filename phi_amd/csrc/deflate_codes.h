@@ -1,15 +1,10 @@
 // deflate_codes.h -- the parts of a DEFLATE writer (RFC 1951) that are plain code: length-limited prefix codes from a histogram,
-// the run-length coding of code lengths (symbols 16 / 17 / 18), canonical codes, the length and distance symbols, and the CRC32
-// shift.  __host__ __device__: the compressor's kernel (deflate.hip) calls them from single lanes, host/deflate_codes_selftest.cpp
-// calls them on the CPU.  Every loop is bounded by the alphabet size (at most DFL_MAX_SYMS) or by a constant.
+// the run-length coding of code lengths (symbols 16 / 17 / 18), canonical codes, the length and distance symbols; the CRC32
+// shift comes with them, from crc32_shift.h.  __host__ __device__: the compressor's kernel (deflate.hip) calls them from single
+// lanes, host/deflate_codes_selftest.cpp calls them on the CPU.  Every loop is bounded by the alphabet size (at most DFL_MAX_SYMS) or by a constant.
 #pragma once
 #include <stdint.h>
-
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define DFL_HD __host__ __device__ inline
-#else
-#define DFL_HD inline
-#endif
+#include "crc32_shift.h"        // DFL_HD, dfl_crc_mul, dfl_crc_shift
 
 #define DFL_NLIT 286            // literal/length symbols that may be coded
 #define DFL_NDIST 30
@@ -185,28 +180,3 @@ DFL_HD int dfl_rle_lengths(const uint8_t *seq, int n, uint8_t *sym, uint8_t *ext
 }
 
 DFL_HD int dfl_cl_extra_bits(int sym) { return sym == 16 ? 2 : sym == 17 ? 3 : sym == 18 ? 7 : 0; }
-
-// ------------------------------------------------------------------------------------------------ CRC32
-
-// CRC32 registers as polynomials over GF(2) modulo the CRC's polynomial, in its reflected form: bit 31 is x^0.
-// a * b mod P
-DFL_HD uint32_t dfl_crc_mul(uint32_t a, uint32_t b)
-{
-    uint32_t p = 0;
-    for (int k = 31; k >= 0; k--) {
-        if ((a >> k) & 1u) p ^= b;
-        b = (b >> 1) ^ (0xEDB88320u & (0u - (b & 1u)));        // b * x
-    }
-    return p;
-}
-
-// the register c (zero initial value, no final inversion) after nbytes more zero bytes: c * x^(8 nbytes) mod P
-DFL_HD uint32_t dfl_crc_shift(uint32_t c, uint32_t nbytes)
-{
-    uint32_t sq = 0x00800000u;                                  // x^8
-    for (int k = 0; k < 32 && nbytes; k++, nbytes >>= 1) {
-        if (nbytes & 1u) c = dfl_crc_mul(c, sq);
-        sq = dfl_crc_mul(sq, sq);
-    }
-    return c;
-}

@@ -20,63 +20,27 @@
 //     on.  A distance reaching before the member's first byte is an error, inside a piece on the device and across
 //     pieces at resolution.  CRC32 per 4 KB segment on the device, combined per member on the host by the GF(2) shift.
 //
+// This file: the kernels, and the host side as stages over one InfRun (upload, find, decode, redecode, layout and resolve,
+// CRC and check, info) that hold launches and copies only.  What both sides share -- records, status values, the gzip
+// header parser -- and every host rule between the launches is plain code in inflate_host.h, checked on the CPU by
+// host/inflate_host_selftest.cpp; the stream, events and buffers of a run are dev_run.h's.
+//
 // Mapping: one decoder per wave (64-thread workgroup), its state wave-uniform; the Huffman tables of the block in LDS
 // (10-bit first level, canonical decoding beyond); literals written by lane 0, match copies and stored blocks by all lanes.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
-#include <stdarg.h>
-#include <stdio.h>
 #include <stdlib.h>
 #include <algorithm>
 #include <vector>
 #include "../../include/phi_amd.h"
 #include "phi_ctx.h"
+#include "dev_run.h"
+#include "inflate_host.h"
 
 #define INF_TB 10               // first-level table bits of the literal/length and distance codes
-#define INF_SEG 4096            // CRC segment
-#define INF_WIN 32768
 
 namespace {
-
-// ------------------------------------------------------------------------------------------------ shared host/device
-
-__host__ __device__ inline uint32_t inf_crc_bitwise(uint32_t c, const uint8_t *p, int64_t n)
-{
-    c = ~c;
-    for (int64_t i = 0; i < n; i++) {
-        c ^= p[i];
-        for (int k = 0; k < 8; k++) c = (c >> 1) ^ (0xEDB88320u & (0u - (c & 1u)));
-    }
-    return ~c;
-}
-
-// a gzip member header at byte p of b[0, n): the byte offset of its deflate data, -1 when invalid, -2 when truncated
-__host__ __device__ inline int64_t inf_gz_header(const uint8_t *b, int64_t n, int64_t p)
-{
-    if (p + 10 > n) return -2;
-    if (b[p] != 0x1f || b[p + 1] != 0x8b || b[p + 2] != 8) return -1;
-    const uint32_t flg = b[p + 3];
-    if (flg & 0xe0) return -1;
-    int64_t q = p + 10;
-    if (flg & 4) {                                              // FEXTRA
-        if (q + 2 > n) return -2;
-        q += 2 + (b[q] | (b[q + 1] << 8));
-        if (q > n) return -2;
-    }
-    for (uint32_t f = 8; f <= 16; f <<= 1)                      // FNAME, FCOMMENT: zero-terminated
-        if (flg & f) {
-            while (q < n && b[q]) q++;
-            if (q >= n) return -2;
-            q++;
-        }
-    if (flg & 2) {                                              // FHCRC: low 16 bits of the header's CRC32
-        if (q + 2 > n) return -2;
-        if ((inf_crc_bitwise(0, b + p, q - p) & 0xffffu) != (uint32_t)(b[q] | (b[q + 1] << 8))) return -1;
-        q += 2;
-    }
-    return q;
-}
 
 // ------------------------------------------------------------------------------------------------ device
 
@@ -88,22 +52,6 @@ __constant__ uint16_t c_dbase[30] = {1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65
 __constant__ uint8_t c_dext[30] = {0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13};
 __constant__ uint8_t c_clord[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
 
-enum : int {
-    INF_STOP = 0,               // stood on another decoder's start
-    INF_END = 1,                // the stream's last trailer
-    INF_E_CODE = -1,            // invalid Huffman code / symbol
-    INF_E_TRUNC = -2,           // ran past the input
-    INF_E_DIST = -3,            // distance before the member's first byte
-    INF_E_HEADER = -4,          // bad gzip member header
-    INF_E_BLOCK = -5,           // bad block type, bad dynamic header, LEN != ~NLEN
-};
-
-struct InfJob { int64_t start; int64_t cap; uint16_t *sym; int32_t chunk; int32_t pad; };
-struct InfResult { int64_t out_len; int64_t end_bit; int32_t end_chunk; int32_t status; int32_t ovf; int32_t pad; };
-struct InfMember { int32_t job; int32_t pad; int64_t pos; uint32_t crc; uint32_t isize; };
-struct InfPiece { int64_t abs; int64_t len; int64_t lo; const uint16_t *sym; };
-struct InfSlab { int32_t piece; int32_t pad; int64_t k0; int64_t k1; };
-struct InfSeg { int64_t off; int64_t len; };
 
 struct InfTables {
     uint16_t lit[1 << INF_TB], dst[1 << INF_TB];    // (symbol << 4) | length; 0: longer than INF_TB bits, or no code
@@ -553,8 +501,8 @@ __global__ void __launch_bounds__(256) phi_inflate_crc_kernel(const uint8_t *__r
 {
     __shared__ uint32_t tab[256];
     {
-        uint32_t c = threadIdx.x;
-        for (int k = 0; k < 8; k++) c = (c >> 1) ^ (0xEDB88320u & (0u - (c & 1u)));
+        uint32_t c = threadIdx.x;                               // dfl_crc_byte, written out: the call compiles to other code
+        for (int k = 0; k < 8; k++) c = (c >> 1) ^ (DFL_CRC_POLY & (0u - (c & 1u)));
         tab[threadIdx.x] = c;
     }
     __syncthreads();
@@ -568,98 +516,212 @@ __global__ void __launch_bounds__(256) phi_inflate_crc_kernel(const uint8_t *__r
 
 // ------------------------------------------------------------------------------------------------ host
 
-// CRC32 shift operators: ops[k] maps a (zero-initialised, uninverted) CRC register to its value after 2^k zero bytes
-struct CrcOps {
-    uint32_t ops[48][32];
-    static uint32_t times(const uint32_t *m, uint32_t v)
-    {
-        uint32_t s = 0;
-        for (int i = 0; v; i++, v >>= 1)
-            if (v & 1) s ^= m[i];
-        return s;
-    }
-    CrcOps()
-    {
-        uint32_t bit[32], a[32], b[32];
-        bit[0] = 0xEDB88320u;                               // one zero bit: c -> (c >> 1) ^ (c & 1 ? P : 0)
-        for (int i = 1; i < 32; i++) bit[i] = 1u << (i - 1);
-        for (int i = 0; i < 32; i++) a[i] = times(bit, bit[i]);           // 2 bits
-        for (int i = 0; i < 32; i++) b[i] = times(a, a[i]);               // 4 bits
-        for (int i = 0; i < 32; i++) ops[0][i] = times(b, b[i]);          // 8 bits
-        for (int k = 1; k < 48; k++)
-            for (int i = 0; i < 32; i++) ops[k][i] = times(ops[k - 1], ops[k - 1][i]);
-    }
-    uint32_t shift(uint32_t c, uint64_t nbytes) const
-    {
-        for (int k = 0; nbytes && c; k++, nbytes >>= 1)
-            if (nbytes & 1) c = times(ops[k], c);
-        return c;
-    }
-};
-
-const CrcOps &crc_ops()
-{
-    static CrcOps *ops = new CrcOps();
-    return *ops;
-}
-
-struct Dev {
-    std::vector<void *> bufs;
+// One inflate, from the compressed bytes on the host to the checked text in one of dev's buffers, as stages: each is
+// launches and copies, and between them the rules of inflate_host.h.  Every host vector a copy reads or fills lives here,
+// for the whole run.
+struct InfRun {
+    Dev &dev;
+    phi_inflate_info *info;
+    const uint8_t *src;
+    int64_t n;
+    int32_t flags;
+    int64_t hdr = 0;                                            // byte offset of the first member's deflate data
+    InfChunks ck{};
     hipStream_t st = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ~Dev()
-    {
-        if (st) (void)hipStreamSynchronize(st);
-        for (void *p : bufs) (void)hipFree(p);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-        if (st) (void)hipStreamDestroy(st);
-    }
-    template <class T> T *alloc(size_t bytes)
-    {
-        void *p = nullptr;
-        if (hipMalloc(&p, std::max<size_t>(bytes, 16)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-        bufs.push_back(p);
-        if (phi_dev_poison(p, std::max<size_t>(bytes, 16))) return nullptr;
-        return (T *)p;
-    }
+    uint32_t *d_in = nullptr;
+    int64_t *d_starts = nullptr;
+    InfMember *d_mem = nullptr;
+    uint8_t *d_out = nullptr;
+    unsigned long long *d_stat = nullptr, stat[2] = {0, 0};     // [0] marker bytes, [1] a distance reached before its member
+    std::vector<int64_t> starts;
+    std::vector<int> job_of, chunk_of, chain;
+    std::vector<InfJob> jobs, jobs2;                            // (2: the second run)
+    std::vector<InfResult> res, res2;
+    int32_t nmem = 0;
+    std::vector<InfMember> mem;
+    std::vector<InfPiece> pieces;
+    std::vector<InfEnd> ends;
+    int64_t total = 0;
+    std::vector<InfSlab> slabs;
+    std::vector<InfSeg> segs;
+    std::vector<uint32_t> crcs;
+    InfErr err;
+
+    int refused() { return fail(info, err.code, "%s", err.text); }
+    int upload(int32_t device);
+    int find();
+    int run_decoders(const std::vector<InfJob> &js, InfMember *d_m, int32_t *d_nm, int32_t mem_cap, std::vector<InfResult> &out);
+    int decode();
+    int redecode();
+    int layout_resolve();
+    int crc_check();
+    void fill_info();
 };
 
-int fail(phi_inflate_info *info, int code, const char *fmt, ...) __attribute__((format(printf, 3, 4)));
-int fail(phi_inflate_info *info, int code, const char *fmt, ...)
+int InfRun::upload(int32_t device)
 {
-    if (info) {
-        va_list ap;
-        va_start(ap, fmt);
-        vsnprintf(info->detail, sizeof(info->detail), fmt, ap);
-        va_end(ap);
-    }
-    return code;
+    if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return fail(info, PHI_ERR_DEVICE, "phi_inflate: no device %d", device); }
+    DCHK(hipStreamCreateWithFlags(&dev.st, hipStreamNonBlocking));
+    DCHK(hipEventCreate(&dev.ev[0]));
+    DCHK(hipEventCreate(&dev.ev[1]));
+    st = dev.st;
+    const size_t in_pad = (((size_t)n + 3) & ~(size_t)3) + 256;
+    DALLOC(p, uint32_t, in_pad);
+    d_in = p;
+    DCHK(hipMemsetAsync(d_in, 0, in_pad, st));
+    DCHK(hipMemcpyAsync(d_in, src, (size_t)n, hipMemcpyHostToDevice, st));
+    DCHK(hipEventRecord(dev.ev[0], st));
+    return PHI_OK;
 }
 
-const char *status_text(int s)
+// 1. the finder: a start for every chunk but the first, -1 where it found none
+int InfRun::find()
 {
-    switch (s) {
-    case INF_E_CODE: return "invalid Huffman code";
-    case INF_E_TRUNC: return "truncated stream";
-    case INF_E_DIST: return "distance before the start of the member";
-    case INF_E_HEADER: return "bad gzip member header";
-    case INF_E_BLOCK: return "invalid block header";
-    default: return "error";
+    const int nch = ck.nch;
+    DALLOC(p, int64_t, (size_t)nch * 8);
+    d_starts = p;
+    starts.assign((size_t)nch, -1);
+    starts[0] = hdr * 8;
+    DCHK(hipMemcpyAsync(d_starts, starts.data(), (size_t)nch * 8, hipMemcpyHostToDevice, st));
+    if (nch > 1 && !(flags & PHI_INFLATE_NO_FINDER)) {
+        hipLaunchKernelGGL(phi_inflate_find_kernel, dim3(nch - 1), dim3(64), 0, st, d_in, n * 8, ck.C * 8, d_starts);
+        DCHK(hipGetLastError());
+        DCHK(hipMemcpyAsync(starts.data(), d_starts, (size_t)nch * 8, hipMemcpyDeviceToHost, st));
+        DCHK(hipStreamSynchronize(st));
+        starts[0] = hdr * 8;
     }
+    return PHI_OK;
 }
 
-int64_t default_chunk()
+// the jobs js through the decode kernel; their results are in `out` once the stream is synchronised
+int InfRun::run_decoders(const std::vector<InfJob> &js, InfMember *d_m, int32_t *d_nm, int32_t mem_cap, std::vector<InfResult> &out)
 {
-    const char *e = getenv("PHI_INFLATE_CHUNK");
-    const long long v = e ? atoll(e) : 0;
-    return v > 0 ? v : PHI_INFLATE_CHUNK_DEFAULT;
+    const size_t nj = js.size();
+    DALLOC(d_jobs, InfJob, nj * sizeof(InfJob));
+    DALLOC(d_res, InfResult, nj * sizeof(InfResult));
+    DCHK(hipMemcpyAsync(d_jobs, js.data(), nj * sizeof(InfJob), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(phi_inflate_decode_kernel, dim3((unsigned)nj), dim3(64), 0, st, d_in, n, d_starts, ck.nch, d_jobs, d_res, d_m, d_nm, mem_cap);
+    DCHK(hipGetLastError());
+    out.resize(nj);
+    DCHK(hipMemcpyAsync(out.data(), d_res, nj * sizeof(InfResult), hipMemcpyDeviceToHost, st));
+    return PHI_OK;
+}
+
+// 2. one decoder per found start, and 3. the chain of those that began at true block boundaries
+int InfRun::decode()
+{
+    inf_job_index(starts, job_of, chunk_of);
+    const size_t nj = chunk_of.size();
+    const int64_t cap = inf_sym_capacity(src, n, ck.C);
+    const int32_t mem_cap = inf_member_capacity(n, (int64_t)nj);
+    DALLOC(d_sym, uint16_t, nj * (size_t)cap * 2);
+    inf_job_list(starts, chunk_of, cap, d_sym, jobs);
+    DALLOC(m, InfMember, (size_t)mem_cap * sizeof(InfMember));
+    d_mem = m;
+    DALLOC(d_nmem, int32_t, 64);
+    DCHK(hipMemsetAsync(d_nmem, 0, 64, st));
+    if (const int rc = run_decoders(jobs, d_mem, d_nmem, mem_cap, res)) return rc;
+    DCHK(hipMemcpyAsync(&nmem, d_nmem, 4, hipMemcpyDeviceToHost, st));
+    DCHK(hipStreamSynchronize(st));
+    if (nmem > mem_cap) return fail(info, PHI_ERR_OVERFLOW, "phi_inflate: %d member records, capacity %d", nmem, mem_cap);
+    return inf_chain(job_of, res, chain, err) ? refused() : PHI_OK;
+}
+
+// the chain's decoders whose output outgrew the guess: again, at its size (no member records: the first run's stand)
+int InfRun::redecode()
+{
+    InfAgain A;
+    inf_again_plan(chain, res, A);
+    if (A.again.empty()) return PHI_OK;
+    DALLOC(d_sym2, uint16_t, (size_t)A.total * 2);
+    inf_again_jobs(A, res, d_sym2, jobs, jobs2);
+    if (const int rc = run_decoders(jobs2, nullptr, nullptr, 0, res2)) return rc;
+    DCHK(hipStreamSynchronize(st));
+    return inf_again_check(A, jobs, res, res2, err) ? refused() : PHI_OK;
+}
+
+// 4. pieces and members, and 5. the markers resolved: the tails in order, then everything else in parallel
+int InfRun::layout_resolve()
+{
+    mem.resize((size_t)nmem);
+    if (nmem) {
+        DCHK(hipMemcpyAsync(mem.data(), d_mem, (size_t)nmem * sizeof(InfMember), hipMemcpyDeviceToHost, st));
+        DCHK(hipStreamSynchronize(st));
+    }
+    if (inf_layout(chain, res, jobs, mem, pieces, ends, total, err)) return refused();
+    DALLOC(o, uint8_t, (size_t)total + 16);
+    d_out = o;
+    DALLOC(d_pieces, InfPiece, pieces.size() * sizeof(InfPiece));
+    DALLOC(s, unsigned long long, 64);
+    d_stat = s;
+    DCHK(hipMemsetAsync(d_stat, 0, 64, st));
+    DCHK(hipMemcpyAsync(d_pieces, pieces.data(), pieces.size() * sizeof(InfPiece), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(phi_inflate_tail_kernel, dim3(1), dim3(1024), 0, st, d_pieces, (int32_t)pieces.size(), d_out, d_stat, (int32_t *)(d_stat + 1));
+    DCHK(hipGetLastError());
+    inf_slabs(pieces, slabs);
+    if (!slabs.empty()) {
+        DALLOC(d_slabs, InfSlab, slabs.size() * sizeof(InfSlab));
+        DCHK(hipMemcpyAsync(d_slabs, slabs.data(), slabs.size() * sizeof(InfSlab), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(phi_inflate_resolve_kernel, dim3((unsigned)slabs.size()), dim3(256), 0, st, d_pieces, d_slabs, d_out, d_stat, (int32_t *)(d_stat + 1));
+        DCHK(hipGetLastError());
+    }
+    return PHI_OK;
+}
+
+// 6. CRC32 and ISIZE of every member
+int InfRun::crc_check()
+{
+    inf_segments(ends, segs);
+    crcs.assign(segs.size(), 0);
+    if (!segs.empty()) {
+        DALLOC(d_segs, InfSeg, segs.size() * sizeof(InfSeg));
+        DALLOC(d_crc, uint32_t, segs.size() * 4);
+        DCHK(hipMemcpyAsync(d_segs, segs.data(), segs.size() * sizeof(InfSeg), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(phi_inflate_crc_kernel, dim3((unsigned)((segs.size() + 255) / 256)), dim3(256), 0, st, d_out, d_segs, (int64_t)segs.size(), d_crc);
+        DCHK(hipGetLastError());
+        DCHK(hipMemcpyAsync(crcs.data(), d_crc, segs.size() * 4, hipMemcpyDeviceToHost, st));
+    }
+    DCHK(hipMemcpyAsync(stat, d_stat, 16, hipMemcpyDeviceToHost, st));
+    DCHK(hipEventRecord(dev.ev[1], st));
+    DCHK(hipStreamSynchronize(st));
+    if ((int32_t)(stat[1] & 0xffffffffu))
+        return fail(info, PHI_ERR_INVALID, "gzip stream corrupt: a distance reaches before the start of its member");
+    return inf_member_check(ends, segs, crcs, err) ? refused() : PHI_OK;
+}
+
+void InfRun::fill_info()
+{
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, dev.ev[0], dev.ev[1]);
+    info->out_bytes = total;
+    info->members = (int64_t)ends.size();
+    info->confirmed = (int64_t)chain.size() - 1;
+    info->redecoded = ck.nch - (int64_t)chain.size();
+    info->marker_bytes = (int64_t)stat[0];
+    info->device_ms = ms;
+}
+
+// the whole inflate; the checked output stays in *d_out_ret (one of dev's buffers), *out_size bytes
+int inflate_run(Dev &dev, int32_t device, const void *in, int64_t n, int64_t chunk_bytes, int32_t flags, int64_t *out_size,
+                uint8_t **d_out_ret, phi_inflate_info *info)
+{
+    if (info) memset(info, 0, sizeof(*info));
+    if (!out_size || n < 0 || (n > 0 && !in)) return fail(info, PHI_ERR_INVALID, "phi_inflate: null pointer or negative size");
+    *out_size = 0;
+    InfRun R{dev, info, (const uint8_t *)in, n, flags};
+    R.hdr = inf_gz_header(R.src, n, 0);
+    if (R.hdr < 0) return fail(info, PHI_ERR_INVALID, "phi_inflate: %s gzip header", R.hdr == -2 ? "truncated" : "not a");
+    if (inf_chunk_plan(n, chunk_bytes, getenv("PHI_INFLATE_CHUNK"), R.ck, R.err)) return R.refused();
+    if (info) { info->in_bytes = n; info->chunks = R.ck.nch; }
+    int rc;
+    if ((rc = R.upload(device)) || (rc = R.find()) || (rc = R.decode()) || (rc = R.redecode()) || (rc = R.layout_resolve()) || (rc = R.crc_check())) return rc;
+    if (info) R.fill_info();
+    *out_size = R.total;
+    *d_out_ret = R.d_out;
+    return PHI_OK;
 }
 
 }  // namespace
-
-#define DCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(info, PHI_ERR_DEVICE, "%s: %s", #call, hipGetErrorString(e_)); } while (0)
-#define DALLOC(var, T, bytes) T *var = dev.alloc<T>(bytes); if (!var) return fail(info, PHI_ERR_NOMEM, "device allocation of %zu bytes failed", (size_t)(bytes))
 
 extern "C" {
 
@@ -672,238 +734,7 @@ int phi_gzip_header(const void *data, int64_t n, int64_t pos, int64_t *deflate_s
     return PHI_OK;
 }
 
-uint32_t phi_crc32_combine(uint32_t crc_a, uint32_t crc_b, int64_t len_b)
-{
-    // crc(A B) = shift_|B|(crc(A)) ^ crc(B): the initial and final inversions of crc(A) and crc(B) cancel
-    return crc_ops().shift(crc_a, (uint64_t)(len_b < 0 ? 0 : len_b)) ^ crc_b;
-}
-
-}  // extern "C"
-
-namespace {
-
-// the whole inflate; the checked output stays in *d_out (one of dev's buffers), *out_size bytes
-int inflate_run(Dev &dev, int32_t device, const void *in, int64_t n, int64_t chunk_bytes, int32_t flags, int64_t *out_size,
-                uint8_t **d_out_ret, phi_inflate_info *info)
-{
-    if (info) memset(info, 0, sizeof(*info));
-    if (!out_size || n < 0 || (n > 0 && !in)) return fail(info, PHI_ERR_INVALID, "phi_inflate: null pointer or negative size");
-    *out_size = 0;
-    const uint8_t *src = (const uint8_t *)in;
-    const int64_t hdr = inf_gz_header(src, n, 0);
-    if (hdr < 0) return fail(info, PHI_ERR_INVALID, "phi_inflate: %s gzip header", hdr == -2 ? "truncated" : "not a");
-    const int64_t C = chunk_bytes > 0 ? std::max<int64_t>(chunk_bytes, 64) : default_chunk();
-    const int64_t nch64 = (n + C - 1) / C;
-    if (nch64 >= (1 << 30)) return fail(info, PHI_ERR_UNSUPPORTED, "phi_inflate: %lld chunks", (long long)nch64);
-    const int nch = (int)nch64;
-    if (info) { info->in_bytes = n; info->chunks = nch; }
-
-    if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return fail(info, PHI_ERR_DEVICE, "phi_inflate: no device %d", device); }
-    DCHK(hipStreamCreateWithFlags(&dev.st, hipStreamNonBlocking));
-    DCHK(hipEventCreate(&dev.ev[0]));
-    DCHK(hipEventCreate(&dev.ev[1]));
-    hipStream_t st = dev.st;
-
-    const size_t in_pad = (((size_t)n + 3) & ~(size_t)3) + 256;
-    DALLOC(d_in, uint32_t, in_pad);
-    DCHK(hipMemsetAsync(d_in, 0, in_pad, st));
-    DCHK(hipMemcpyAsync(d_in, src, (size_t)n, hipMemcpyHostToDevice, st));
-    DCHK(hipEventRecord(dev.ev[0], st));
-
-    // 1. the finder
-    DALLOC(d_starts, int64_t, (size_t)nch * 8);
-    std::vector<int64_t> starts(nch, -1);
-    starts[0] = hdr * 8;
-    DCHK(hipMemcpyAsync(d_starts, starts.data(), (size_t)nch * 8, hipMemcpyHostToDevice, st));
-    if (nch > 1 && !(flags & PHI_INFLATE_NO_FINDER)) {
-        hipLaunchKernelGGL(phi_inflate_find_kernel, dim3(nch - 1), dim3(64), 0, st, d_in, n * 8, C * 8, d_starts);
-        DCHK(hipGetLastError());
-        DCHK(hipMemcpyAsync(starts.data(), d_starts, (size_t)nch * 8, hipMemcpyDeviceToHost, st));
-        DCHK(hipStreamSynchronize(st));
-        starts[0] = hdr * 8;
-    }
-
-    // 2. one decoder per found start; symbol capacity from the last member's ISIZE (a guess: overflows decode again)
-    std::vector<int> job_of(nch, -1), chunk_of;
-    for (int i = 0; i < nch; i++)
-        if (starts[i] >= 0) { job_of[i] = (int)chunk_of.size(); chunk_of.push_back(i); }
-    const int nj = (int)chunk_of.size();
-    double ratio = 4.0;
-    if (n >= 18) {
-        const uint32_t isz = src[n - 4] | (src[n - 3] << 8) | (src[n - 2] << 16) | ((uint32_t)src[n - 1] << 24);
-        ratio = std::max(ratio, std::min(1100.0, (double)isz / (double)n));
-    }
-    const int64_t cap1 = (int64_t)((double)C * ratio * 1.25) + 4096;
-    DALLOC(d_sym, uint16_t, (size_t)nj * cap1 * 2);
-    std::vector<InfJob> jobs(nj);
-    for (int k = 0; k < nj; k++) jobs[k] = InfJob{starts[chunk_of[k]], cap1, d_sym + (size_t)k * cap1, chunk_of[k], 0};
-    const int mem_cap = (int)std::min<int64_t>(n / 18 + 4 * (int64_t)nj + 64, 1 << 30);
-    DALLOC(d_jobs, InfJob, (size_t)nj * sizeof(InfJob));
-    DALLOC(d_res, InfResult, (size_t)nj * sizeof(InfResult));
-    DALLOC(d_mem, InfMember, (size_t)mem_cap * sizeof(InfMember));
-    DALLOC(d_nmem, int32_t, 64);
-    DCHK(hipMemsetAsync(d_nmem, 0, 64, st));
-    DCHK(hipMemcpyAsync(d_jobs, jobs.data(), (size_t)nj * sizeof(InfJob), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(phi_inflate_decode_kernel, dim3(nj), dim3(64), 0, st, d_in, n, d_starts, nch, d_jobs, d_res, d_mem, d_nmem, mem_cap);
-    DCHK(hipGetLastError());
-    std::vector<InfResult> res(nj);
-    int32_t nmem = 0;
-    DCHK(hipMemcpyAsync(res.data(), d_res, (size_t)nj * sizeof(InfResult), hipMemcpyDeviceToHost, st));
-    DCHK(hipMemcpyAsync(&nmem, d_nmem, 4, hipMemcpyDeviceToHost, st));
-    DCHK(hipStreamSynchronize(st));
-    if (nmem > mem_cap) return fail(info, PHI_ERR_OVERFLOW, "phi_inflate: %d member records, capacity %d", nmem, mem_cap);
-
-    // 3. the chain of decoders that began at true block boundaries
-    std::vector<int> chain;
-    for (int ch = 0;;) {
-        const int k = job_of[ch];
-        const InfResult &r = res[k];
-        chain.push_back(k);
-        if (r.status < 0)
-            return fail(info, PHI_ERR_INVALID, "gzip stream corrupt: %s (near compressed byte %lld)", status_text(r.status), (long long)(r.end_bit / 8));
-        if (r.status == INF_END) break;
-        ch = r.end_chunk;
-    }
-    std::vector<int> again;
-    for (int k : chain)
-        if (res[k].ovf) again.push_back(k);
-    if (!again.empty()) {                                       // decoders whose output outgrew the guess: again, at its size
-        int64_t tot = 0;
-        for (int k : again) tot += res[k].out_len + 1;
-        DALLOC(d_sym2, uint16_t, (size_t)tot * 2);
-        std::vector<InfJob> j2;
-        int64_t off = 0;
-        for (int k : again) {
-            j2.push_back(InfJob{jobs[k].start, res[k].out_len + 1, d_sym2 + off, jobs[k].chunk, 0});
-            jobs[k].sym = d_sym2 + off;
-            off += res[k].out_len + 1;
-        }
-        DALLOC(d_jobs2, InfJob, j2.size() * sizeof(InfJob));
-        DALLOC(d_res2, InfResult, j2.size() * sizeof(InfResult));
-        DCHK(hipMemcpyAsync(d_jobs2, j2.data(), j2.size() * sizeof(InfJob), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(phi_inflate_decode_kernel, dim3((unsigned)j2.size()), dim3(64), 0, st, d_in, n, d_starts, nch, d_jobs2, d_res2,
-                           (InfMember *)nullptr, (int32_t *)nullptr, 0);
-        DCHK(hipGetLastError());
-        std::vector<InfResult> r2(j2.size());
-        DCHK(hipMemcpyAsync(r2.data(), d_res2, r2.size() * sizeof(InfResult), hipMemcpyDeviceToHost, st));
-        DCHK(hipStreamSynchronize(st));
-        for (size_t q = 0; q < again.size(); q++)
-            if (r2[q].ovf || r2[q].out_len != res[again[q]].out_len || r2[q].status != res[again[q]].status)
-                return fail(info, PHI_ERR_DEVICE, "phi_inflate: decoder of chunk %d differs on its second run (internal error)", jobs[again[q]].chunk);
-    }
-
-    // 4. pieces, members
-    std::vector<int> piece_of(nj, -1);
-    std::vector<InfPiece> pieces;
-    int64_t total = 0;
-    for (int k : chain) {
-        piece_of[k] = (int)pieces.size();
-        pieces.push_back(InfPiece{total, res[k].out_len, 0, jobs[k].sym});
-        total += res[k].out_len;
-    }
-    std::vector<InfMember> mem(nmem);
-    if (nmem) {
-        DCHK(hipMemcpyAsync(mem.data(), d_mem, (size_t)nmem * sizeof(InfMember), hipMemcpyDeviceToHost, st));
-        DCHK(hipStreamSynchronize(st));
-    }
-    struct MemEnd { int64_t abs; int idx; uint32_t crc, isize; };
-    std::vector<MemEnd> ends;
-    for (int q = 0; q < nmem; q++) {
-        const int pc = piece_of[mem[q].job];
-        if (pc >= 0) ends.push_back(MemEnd{pieces[pc].abs + mem[q].pos, q, mem[q].crc, mem[q].isize});
-    }
-    std::sort(ends.begin(), ends.end(), [](const MemEnd &a, const MemEnd &b) { return a.abs != b.abs ? a.abs < b.abs : a.idx < b.idx; });
-    if (ends.empty() || ends.back().abs != total)
-        return fail(info, PHI_ERR_DEVICE, "phi_inflate: member ends do not cover the output (internal error)");
-    {
-        size_t e = 0;
-        int64_t lo = 0;
-        for (InfPiece &pc : pieces) {
-            while (e < ends.size() && ends[e].abs <= pc.abs) lo = ends[e++].abs;
-            pc.lo = lo;
-        }
-    }
-
-    // 5. resolve the markers: the tails in order, then everything else in parallel
-    DALLOC(d_out, uint8_t, (size_t)total + 16);
-    DALLOC(d_pieces, InfPiece, pieces.size() * sizeof(InfPiece));
-    DALLOC(d_stat, unsigned long long, 64);
-    DCHK(hipMemsetAsync(d_stat, 0, 64, st));
-    DCHK(hipMemcpyAsync(d_pieces, pieces.data(), pieces.size() * sizeof(InfPiece), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(phi_inflate_tail_kernel, dim3(1), dim3(1024), 0, st, d_pieces, (int32_t)pieces.size(), d_out, d_stat, (int32_t *)(d_stat + 1));
-    DCHK(hipGetLastError());
-    std::vector<InfSlab> slabs;
-    const int64_t SLAB = 64 << 10;
-    for (size_t p = 0; p < pieces.size(); p++) {
-        const int64_t body = std::max<int64_t>(0, pieces[p].len - INF_WIN);
-        for (int64_t k = 0; k < body; k += SLAB) slabs.push_back(InfSlab{(int32_t)p, 0, k, std::min(body, k + SLAB)});
-    }
-    if (!slabs.empty()) {
-        DALLOC(d_slabs, InfSlab, slabs.size() * sizeof(InfSlab));
-        DCHK(hipMemcpyAsync(d_slabs, slabs.data(), slabs.size() * sizeof(InfSlab), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(phi_inflate_resolve_kernel, dim3((unsigned)slabs.size()), dim3(256), 0, st, d_pieces, d_slabs, d_out, d_stat, (int32_t *)(d_stat + 1));
-        DCHK(hipGetLastError());
-    }
-
-    // 6. CRC32 and ISIZE of every member
-    std::vector<InfSeg> segs;
-    std::vector<int64_t> mstart(ends.size());
-    {
-        int64_t s = 0;
-        for (size_t m = 0; m < ends.size(); m++) {
-            mstart[m] = s;
-            for (int64_t k = s; k < ends[m].abs; k += INF_SEG) segs.push_back(InfSeg{k, std::min<int64_t>(INF_SEG, ends[m].abs - k)});
-            s = ends[m].abs;
-        }
-    }
-    std::vector<uint32_t> crcs(segs.size());
-    if (!segs.empty()) {
-        DALLOC(d_segs, InfSeg, segs.size() * sizeof(InfSeg));
-        DALLOC(d_crc, uint32_t, segs.size() * 4);
-        DCHK(hipMemcpyAsync(d_segs, segs.data(), segs.size() * sizeof(InfSeg), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(phi_inflate_crc_kernel, dim3((unsigned)((segs.size() + 255) / 256)), dim3(256), 0, st, d_out, d_segs, (int64_t)segs.size(), d_crc);
-        DCHK(hipGetLastError());
-        DCHK(hipMemcpyAsync(crcs.data(), d_crc, segs.size() * 4, hipMemcpyDeviceToHost, st));
-    }
-    unsigned long long stat[2] = {0, 0};
-    DCHK(hipMemcpyAsync(stat, d_stat, 16, hipMemcpyDeviceToHost, st));
-    DCHK(hipEventRecord(dev.ev[1], st));
-    DCHK(hipStreamSynchronize(st));
-    if ((int32_t)(stat[1] & 0xffffffffu))
-        return fail(info, PHI_ERR_INVALID, "gzip stream corrupt: a distance reaches before the start of its member");
-    {
-        const CrcOps &ops = crc_ops();
-        size_t sg = 0;
-        for (size_t m = 0; m < ends.size(); m++) {
-            const int64_t len = ends[m].abs - mstart[m];
-            uint32_t raw = 0;
-            for (; sg < segs.size() && segs[sg].off < ends[m].abs; sg++)
-                raw = (segs[sg].len == INF_SEG ? CrcOps::times(ops.ops[12], raw) : ops.shift(raw, (uint64_t)segs[sg].len)) ^ crcs[sg];
-            const uint32_t crc = ops.shift(0xffffffffu, (uint64_t)len) ^ raw ^ 0xffffffffu;
-            if (crc != ends[m].crc)
-                return fail(info, PHI_ERR_INVALID, "gzip stream corrupt: CRC32 mismatch in member %zu (%08x, trailer %08x)", m, crc, ends[m].crc);
-            if ((uint32_t)len != ends[m].isize)
-                return fail(info, PHI_ERR_INVALID, "gzip stream corrupt: ISIZE mismatch in member %zu (%u, trailer %u)", m, (uint32_t)len, ends[m].isize);
-        }
-    }
-    if (info) {
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, dev.ev[0], dev.ev[1]);
-        info->out_bytes = total;
-        info->members = (int64_t)ends.size();
-        info->confirmed = (int64_t)chain.size() - 1;
-        info->redecoded = nch - (int64_t)chain.size();
-        info->marker_bytes = (int64_t)stat[0];
-        info->device_ms = ms;
-    }
-    *out_size = total;
-    *d_out_ret = d_out;
-    return PHI_OK;
-}
-
-}  // namespace
-
-extern "C" {
+uint32_t phi_crc32_combine(uint32_t crc_a, uint32_t crc_b, int64_t len_b) { return inf_crc_combine(crc_a, crc_b, (uint64_t)(len_b < 0 ? 0 : len_b)); }
 
 int phi_inflate(int32_t device, const void *in, int64_t n, void *out, int64_t cap, int64_t chunk_bytes, int32_t flags,
                 int64_t *out_size, phi_inflate_info *info)

@@ -126,6 +126,20 @@ def test_sync_and_full_flush_points(phi, inputs):
         assert phi.inflate(comp, chunk_bytes=chunk)[0] == text
 
 
+def test_decoders_that_outgrow_the_capacity_guess_decode_again(phi):
+    """One member of 1 MiB of random bytes, then 8 MiB of zeros: ISIZE over the compressed size is about 9, so a decoder's
+    symbol capacity is about 50 K, while a 4 KB chunk of the zeros inflates a thousandfold: its decoder overflows and runs
+    a second time at its true size."""
+    rng = np.random.default_rng(4)
+    text = rng.integers(0, 256, 1 << 20, dtype=np.uint8).tobytes() + bytes(8 << 20)
+    comp = gz(text, 6)
+    assert 8 < len(text) / len(comp) < 10
+    for chunk in (SMALL, 0):
+        out, info = phi.inflate(comp, chunk_bytes=chunk)
+        assert out == text
+        assert info["members"] == 1 and info["out_bytes"] == len(text)
+
+
 def member(payload, flags=0, extra=b"", name=b"", comment=b""):
     """one gzip member with a header built here (FTEXT aside, every flag RFC 1952 defines)"""
     h = bytearray(b"\x1f\x8b\x08" + bytes([flags]) + struct.pack("<I", 0) + b"\x00\x03")
