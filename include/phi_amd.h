@@ -863,7 +863,7 @@ int phi_reads_bam_last_batch(phi_ctx *ctx, char *bases, int64_t cap_bases, int64
  *                    a leave-one-out truth -- the dropped sample's own calls -- is made by the same code.
  *   phi_calls_stats  (no reference counterpart) what the last successful call did: sizes, the algorithmic bytes as DESIGN.md
  *                    4.16 counts them, GPU milliseconds per stage by HIP events on the context's stream.
- * The buffers behind phi_calls are owned by the context and stay valid until the next phi_calls_*, phi_solve, phi_set_graph*
+ * The buffers behind phi_calls are owned by the context and stay valid until the next phi_calls_path / phi_calls_walk, phi_solve, phi_set_graph*
  * or phi_ctx_destroy.  Limits: fewer than 2^31 calls, a query and a reference walk of fewer than 2^31 - 1 entries each, an
  * allele of fewer than 2^31 bytes (PHI_ERR_UNSUPPORTED beyond); byte offsets are 64-bit.  walk or ref_walk outside the set
  * graph's walks (after a panel: the kept ones, renumbered): PHI_ERR_INVALID.  Before phi_set_graph or on a scout:
@@ -889,6 +889,60 @@ typedef struct {
 int phi_calls_path(phi_ctx *ctx, int32_t ref_walk, phi_calls *out);
 int phi_calls_walk(phi_ctx *ctx, int32_t walk, int32_t ref_walk, phi_calls *out);
 int phi_calls_stats(phi_ctx *ctx, phi_calls_info *out);
+
+/*
+ * READ SUPPORT OF EVERY CALL: how many minimisers witness each call's ALT and REF, and how many of those the reads have seen
+ * (calls_support.hip).  No reference counterpart: the reference writes no calls.  It is the per-record evidence
+ * a genotyper's VCF carries (PanGenie, `bcftools`): at 0.1x to 2x most of the path is imputed from the panel, and INFO/PH alone
+ * does not tell a call with ten witnessed minimisers from one with none.  THE RULE IS THIS PROJECT'S OWN: it is no other
+ * tool's count and has not been compared with any other tool.
+ *
+ * The rule.  k and w are the context's parameters.  M(h) is the list phi_walk_minimizers(h) returns: occurrences (hash, pos),
+ * pos in bases of walk h.  Entry t of walk h covers the bases [B_h(t), B_h(t + 1)); an occurrence LIES IN the entry that holds
+ * its pos.  Q(j) is the number of bases of the query before query index j, R(p) that of walk r before its index p.
+ *   1. Occurrences of the query.  Query index j sits on walk h_j at entry t_j: for phi_calls_walk h_j = walk and t_j = j; for
+ *      the path h_j is the walk of the stretch that holds j (the result's path_hap[j]) and t_j that vertex's index on it.
+ *      Index j contributes the occurrences of M(h_j) that lie in entry t_j, at the query coordinate
+ *      x = Q(j) + (pos - B_{h_j}(t_j)).  For a walk that is M(walk) as it stands.  For the path it is a union per entry: THE
+ *      K-MER OF AN OCCURRENCE WITHIN k + w - 2 BASES BEFORE A SWITCH CONTINUES ALONG THE WALK IT WAS SKETCHED ON, NOT ALONG
+ *      THE PATH, and the windows are that walk's.  This is not corrected.
+ *   2. Occurrences of the reference walk r: M(r), in its own coordinates.
+ *   3. Witnesses.  Call k has its anchors at query indices i < i' and at indices p < p' on r (rule 3 of the calls).  The
+ *      unpadded ALT is the interval [A0, A1) = [Q(i + 1), Q(i')) of the query, the unpadded REF is [R(p + 1), R(p')) of r;
+ *      either may be empty.  An occurrence at x WITNESSES an interval when x < A1 and x + k > A0.  For a non-empty interval the
+ *      k-mer holds at least one base of the allele; for an empty one (A0 = A1 = J) it holds both bases at the junction, so a
+ *      deletion is witnessed by the k-mers that span it.
+ *   4. Counts.  alt_n[k] and ref_n[k] are the witnesses of call k, as occurrences and not as distinct hashes.  alt_hit[k] and
+ *      ref_hit[k] are those whose minimiser has its flag set in the context's CURRENT hit vector: after a solve the vector the
+ *      solve read; several read sets, a ladder level, an exchanged multi-GPU vector are whatever is current.  0 of 0 is a
+ *      valid answer (a walk shorter than w + k - 1 bases has no occurrence at all).
+ *
+ *   phi_calls_support        (no reference counterpart) the four counts of every call of the last successful phi_calls_path /
+ *                            phi_calls_walk, their totals, the (call, side, entry) items the device worked through and its
+ *                            GPU milliseconds by HIP events.  (The struct is phi_call_support: C has one name space for
+ *                            both.)  The arrays are owned by the context and stay valid exactly as long as the buffers
+ *                            behind phi_calls do.  PHI_ERR_STATE without a current calls result or on a scout; after a
+ *                            refusal the context is as it was, the calls included.
+ *   phi_calls_support_stats  (no reference counterpart) what the last successful phi_calls_support did: items, entries
+ *                            visited, class records looked at, witnesses, the algorithmic bytes as DESIGN.md 4.16 counts
+ *                            them, GPU milliseconds.
+ * Limits: fewer than 2^39 items (PHI_ERR_UNSUPPORTED beyond).
+ */
+typedef struct {
+    int64_t n_calls;
+    const int32_t *alt_hit, *alt_n, *ref_hit, *ref_n; /* [n_calls] rule 4 */
+    int64_t alt_hit_total, alt_n_total, ref_hit_total, ref_n_total;
+    int64_t n_items;                                 /* (call, side, target entry) triples */
+    double gpu_ms;                                   /* first fill to last kernel, by HIP events */
+} phi_call_support;
+typedef struct {
+    int64_t n_calls, n_items;
+    int64_t n_visited, n_records, n_witnesses;       /* walk entries whose class was read; class records looked at; witnesses */
+    int64_t bytes_moved;                             /* the algorithmic bytes of the stage */
+    double gpu_ms;
+} phi_calls_support_info;
+int phi_calls_support(phi_ctx *ctx, phi_call_support *out);
+int phi_calls_support_stats(phi_ctx *ctx, phi_calls_support_info *out);
 
 #ifdef __cplusplus
 }

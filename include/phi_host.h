@@ -229,6 +229,21 @@ int phi_format_calls_vcf(const char *contig, int64_t contig_len, const char *sam
                          int64_t *n_written, int64_t *n_dropped, char *err, int err_cap);
 void phi_host_free_text(char *p);
 
+/* The same file with the read support of every call (phi_calls_support of phi_amd.h: alt_hit, alt_n, ref_hit, ref_n, [n_calls]
+ * each).  Two more header lines behind the FORMAT line of GT,
+ *     ##FORMAT=<ID=AK,Number=2,Type=Integer,Description="ALT witness minimisers: seen in the reads, all">
+ * and the same for RK and REF, and every record ends  GT:AK:RK  1:alt_hit,alt_n:ref_hit,ref_n .  Everything else is byte for byte
+ * what phi_write_calls_vcf / phi_format_calls_vcf give, their refusals and the dropped REF = ALT calls included (the counts of a
+ * dropped call go with it).  The counts follow this project's own rule and are no other tool's. */
+int phi_write_calls_vcf_support(const char *path, const char *contig, int64_t contig_len, const char *sample, int64_t n_calls, const int64_t *pos,
+                                const int64_t *ref_off, const char *ref_bytes, const int64_t *alt_off, const char *alt_bytes, const char *const *ph,
+                                const int32_t *alt_hit, const int32_t *alt_n, const int32_t *ref_hit, const int32_t *ref_n, int64_t *n_written,
+                                int64_t *n_dropped, char *err, int err_cap);
+int phi_format_calls_vcf_support(const char *contig, int64_t contig_len, const char *sample, int64_t n_calls, const int64_t *pos, const int64_t *ref_off,
+                                 const char *ref_bytes, const int64_t *alt_off, const char *alt_bytes, const char *const *ph, const int32_t *alt_hit,
+                                 const int32_t *alt_n, const int32_t *ref_hit, const int32_t *ref_n, char **out, int64_t *n, int64_t *n_written,
+                                 int64_t *n_dropped, char *err, int err_cap);
+
 #ifdef __cplusplus
 }
 #endif

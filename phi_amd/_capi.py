@@ -39,7 +39,7 @@ SYMBOLS = [
     "phi_scout_graph", "phi_scout_scores", "phi_scout_choose", "phi_reads_collect_score", "phi_vcf_walks_wide",
     "phi_prefix_sums",
     "phi_reads_bam_begin", "phi_add_reads_bam", "phi_add_reads_bam_parked", "phi_reads_bam_end", "phi_reads_bam_last_batch",
-    "phi_calls_path", "phi_calls_walk", "phi_calls_stats",
+    "phi_calls_path", "phi_calls_walk", "phi_calls_stats", "phi_calls_support", "phi_calls_support_stats",
     "phi_deflate_bgzf_bound", "phi_deflate_bgzf", "phi_deflate_bgzf_alloc", "phi_deflate_free",
 ]
 PHI_PANEL_RETAIN = 1
@@ -113,6 +113,15 @@ class PhiCalls(C.Structure):
                 ("ref_bytes", C.c_void_p), ("alt_bytes", C.c_void_p), ("anchor", C.POINTER(C.c_int32)),
                 ("n_shared", C.c_int64), ("n_query", C.c_int64), ("n_ref", C.c_int64),
                 ("ref_span", C.c_int64 * 2), ("query_span", C.c_int64 * 2), ("gpu_ms", C.c_double)]
+
+
+class PhiCallSupport(C.Structure):
+    _fields_ = [("n_calls", C.c_int64)] + [(n, C.POINTER(C.c_int32)) for n in ("alt_hit", "alt_n", "ref_hit", "ref_n")] + [
+        (n, C.c_int64) for n in ("alt_hit_total", "alt_n_total", "ref_hit_total", "ref_n_total", "n_items")] + [("gpu_ms", C.c_double)]
+
+
+class PhiCallsSupportInfo(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_calls", "n_items", "n_visited", "n_records", "n_witnesses", "bytes_moved")] + [("gpu_ms", C.c_double)]
 
 
 class PhiCallsInfo(C.Structure):
@@ -219,6 +228,8 @@ def load():
     L.phi_calls_path.argtypes = [vp, i32, C.POINTER(PhiCalls)]
     L.phi_calls_walk.argtypes = [vp, i32, i32, C.POINTER(PhiCalls)]
     L.phi_calls_stats.argtypes = [vp, C.POINTER(PhiCallsInfo)]
+    L.phi_calls_support.argtypes = [vp, C.POINTER(PhiCallSupport)]
+    L.phi_calls_support_stats.argtypes = [vp, C.POINTER(PhiCallsSupportInfo)]
     L.phi_reads_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
     L.phi_hits_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(i64)]
     L.phi_read_table.argtypes = [vp, C.POINTER(vp), C.POINTER(i64)]

@@ -2,7 +2,8 @@
 
 The calls are made on the device by the rule of include/phi_amd.h (this project's own: not `vg deconstruct`'s, not
 compared with it or with `bcftools`).  Here: the consensus of the rule (apply), the provenance tag of every call
-(ph_names), the VCF writer over libphi_host (write_vcf) and a reader of the files it writes (read_vcf).
+(ph_names), the VCF writer over libphi_host (write_vcf), with the read support of every call where Context.calls_support()
+is handed in, and readers of the files it writes (read_vcf, read_support).
 """
 import ctypes as C
 import os
@@ -39,12 +40,16 @@ def ph_names(calls, path_hap, hap_names):
     return [hap_names[int(path_hap[int(i) + 1])] for i in calls["anchor"]]
 
 
-def write_vcf(path, calls, contig, contig_len, sample, ph=None, bgzf=False, device=0):
+SUPPORT_ARRAYS = ("alt_hit", "alt_n", "ref_hit", "ref_n")
+
+
+def write_vcf(path, calls, contig, contig_len, sample, ph=None, bgzf=False, device=0, support=None):
     """The calls as plain-text VCFv4.2 (phi_write_calls_vcf of include/phi_host.h): one haploid sample with genotype 1, POS
     1-based, PH=<ph[k]> in INFO where ph (a list of names, one per call) is given.  Calls whose REF and ALT are the same bytes
     are dropped.  Returns (records written, calls dropped).  A name ending in .gz is refused (HostError: this writer has no
     deflate of its own) unless bgzf is set: then the same text (phi_format_calls_vcf) is compressed into BGZF blocks on
-    `device` (deflate_bgzf) and written under the name as given."""
+    `device` (deflate_bgzf) and written under the name as given.  support: the dict of Context.calls_support() for these
+    calls; the records then carry FORMAT/AK and RK (phi_write_calls_vcf_support), everything else is the same bytes."""
     from .ilp_index import HostError, host_lib
     L = host_lib()
     n = int(len(calls["pos"]))
@@ -59,10 +64,16 @@ def write_vcf(path, calls, contig, contig_len, sample, ph=None, bgzf=False, devi
         names = (C.c_char_p * max(n, 1))(*[s.encode() if isinstance(s, str) else s for s in ph])
     nw, nd = C.c_int64(), C.c_int64()
     err = C.create_string_buffer(512)
+    sup, fmt, wr = (), L.phi_format_calls_vcf, L.phi_write_calls_vcf
+    if support is not None:
+        arrays = [np.ascontiguousarray(support[f], np.int32) for f in SUPPORT_ARRAYS]
+        if any(len(a) != n for a in arrays):
+            raise ValueError(f"support must hold one count per call ({n})")
+        sup, fmt, wr = tuple(a.ctypes.data for a in arrays), L.phi_format_calls_vcf_support, L.phi_write_calls_vcf_support
     if bgzf:
         text, size = C.c_void_p(), C.c_int64()
-        rc = L.phi_format_calls_vcf(contig.encode(), int(contig_len), sample.encode(), n, pos.ctypes.data, ro.ctypes.data, rb, ao.ctypes.data, ab,
-                                    names, C.byref(text), C.byref(size), C.byref(nw), C.byref(nd), err, 512)
+        rc = fmt(contig.encode(), int(contig_len), sample.encode(), n, pos.ctypes.data, ro.ctypes.data, rb, ao.ctypes.data, ab,
+                 names, *sup, C.byref(text), C.byref(size), C.byref(nw), C.byref(nd), err, 512)
         if rc:
             raise HostError(rc, err.value.decode())
         try:
@@ -73,8 +84,8 @@ def write_vcf(path, calls, contig, contig_len, sample, ph=None, bgzf=False, devi
         with open(path, "wb") as f:
             f.write(deflate_bgzf(plain, device=device))
         return nw.value, nd.value
-    rc = L.phi_write_calls_vcf(os.fsencode(path), contig.encode(), int(contig_len), sample.encode(), n, pos.ctypes.data, ro.ctypes.data, rb,
-                               ao.ctypes.data, ab, names, C.byref(nw), C.byref(nd), err, 512)
+    rc = wr(os.fsencode(path), contig.encode(), int(contig_len), sample.encode(), n, pos.ctypes.data, ro.ctypes.data, rb,
+            ao.ctypes.data, ab, names, *sup, C.byref(nw), C.byref(nd), err, 512)
     if rc:
         raise HostError(rc, err.value.decode())
     return nw.value, nd.value
@@ -104,3 +115,20 @@ def read_vcf(path):
     np.cumsum([len(a) for a in alts], out=ao[1:])
     calls = dict(pos=np.array(pos, np.int64), ref_off=ro, alt_off=ao, ref_bytes=b"".join(refs), alt_bytes=b"".join(alts))
     return header, sample, calls, infos
+
+
+def read_support(path):
+    """FORMAT/AK and RK of a file write_vcf(support=) wrote (plain text): a dict of alt_hit, alt_n, ref_hit, ref_n, int32 per
+    record.  ValueError for a file without them."""
+    cols = {f: [] for f in SUPPORT_ARRAYS}
+    with open(path, "rb") as f:
+        for ln in f.read().split(b"\n"):
+            if not ln or ln.startswith(b"#"):
+                continue
+            c = ln.split(b"\t")
+            if c[8] != b"GT:AK:RK":
+                raise ValueError(f"{path}: a record without FORMAT GT:AK:RK")
+            _, ak, rk = c[9].split(b":")
+            for name, v in zip(SUPPORT_ARRAYS, ak.split(b",") + rk.split(b",")):
+                cols[name].append(int(v))
+    return {f: np.array(v, np.int32) for f, v in cols.items()}

@@ -687,6 +687,26 @@ class Context:
         self._chk(self._L.phi_calls_stats(self._h, C.byref(r)))
         return {n: getattr(r, n) for n, _ in _capi.PhiCallsInfo._fields_}
 
+    def calls_support(self):
+        """The read support of every call of the last calls() (phi_calls_support, the rule of include/phi_amd.h): a dict of
+        alt_hit, alt_n, ref_hit, ref_n (int32 per call: the minimiser occurrences that witness the allele, and those of them
+        the reads have seen), their totals (<name>_total), n_calls, n_items and gpu_ms.  phi_amd.calls.write_vcf(support=)
+        writes them as FORMAT/AK and RK."""
+        r = _capi.PhiCallSupport()
+        self._chk(self._L.phi_calls_support(self._h, C.byref(r)))
+        n = r.n_calls
+        out = {f: getattr(r, f) for f in ("n_calls", "alt_hit_total", "alt_n_total", "ref_hit_total", "ref_n_total", "n_items", "gpu_ms")}
+        for f in ("alt_hit", "alt_n", "ref_hit", "ref_n"):
+            out[f] = np.ctypeslib.as_array(getattr(r, f), shape=(n,)).copy() if n else np.zeros(0, np.int32)
+        return out
+
+    def calls_support_stats(self):
+        """What the last calls_support() did (phi_calls_support_stats): items, entries visited, records, witnesses, the
+        algorithmic bytes, GPU milliseconds."""
+        r = _capi.PhiCallsSupportInfo()
+        self._chk(self._L.phi_calls_support_stats(self._h, C.byref(r)))
+        return {n: getattr(r, n) for n, _ in _capi.PhiCallsSupportInfo._fields_}
+
     # ------------------------------------------------------------------ evaluation
     def edit_distances(self, a_list, b_list, max_distance=-1):
         """edlib NW edit distance of every pair (a_list[i], b_list[i]) of byte strings on the GPU (phi_edit_distances):

@@ -21,6 +21,8 @@
 //              (an allele of 52 kb stands beside thousands of one-base ones at MHC scale): every lane owns four consecutive
 //              bytes and stores them as one word, a wave 256 consecutive bytes; a lane finds its call by a search of the
 //              allele offsets and its source vertex by a search of the base offsets between the call's two vertex indices
+// The base offsets of both walks, the anchors and the allele sources of the calls stay on the device behind the call, and the
+// query as stretches of walk entries on the host: phi_calls_support (calls_support.hip) counts every call's read support from them.
 // Every output has a fixed place: no atomics but the error words, the same bytes from run to run, nothing read before it
 // is written.  Bound (from the code): the 4-byte gathers into pos_of[] and d_vlen[] per entry and
 // the per-vertex gathers into d_seq -- latency, not HBM bandwidth.
@@ -105,10 +107,7 @@ __global__ void calls_span_kernel(const int32_t *__restrict__ query, const int32
     span[5] = q_base[n_query];
 }
 
-struct CallSrc {             // where an allele's bytes lie on its walk: first base (in bases of the walk), vertex indices [v0, v1)
-    int64_t base;
-    int32_t v0, v1;
-};
+using CallSrc = phi_ctx::PhiCallSrc;       // where an allele's bytes lie on its walk
 
 // call k = shared pair pairs[k].  REF = the reference walk's vertices p + 1 .. p2 - 1, ALT = the query's i + 1 .. i2 - 1; when
 // one is empty both get the last base of a in front, which on either walk is the base right before the allele's own.
@@ -203,10 +202,11 @@ inline unsigned blocks_of(int64_t n) { return (unsigned)std::max<int64_t>(1, (n 
 
 // The calls of a query of n_query vertices -- d_query, or when that is null the path's stretches expanded here -- against
 // reference walk r.  On any refusal the context's graph, reads and result are as they were and the last calls are gone.
-int calls_impl(phi_ctx *c, const char *what, const int32_t *d_query, int64_t n_query64, int32_t r, phi_calls *out)
+int calls_impl(phi_ctx *c, const char *what, const int32_t *d_query, int64_t q_ent0, int64_t n_query64, int32_t r, phi_calls *out)
 {
     auto &K = c->calls;
     K.have = false;
+    K.support.have = false;
     const int32_t n_vtx = c->n_vtx;
     const int64_t n_ref64 = c->h_walk_off[(size_t)r + 1] - c->h_walk_off[(size_t)r];
     if (n_query64 >= 0x7fffffffLL || n_ref64 >= 0x7fffffffLL)
@@ -218,10 +218,12 @@ int calls_impl(phi_ctx *c, const char *what, const int32_t *d_query, int64_t n_q
     phi_calls_info info{};
     info.n_query = n_query; info.n_ref = n_ref;
 
-    DevBuf d_pos_of, d_ref_len, d_r_base, d_q_own, d_seg, d_q_len, d_q_base, d_shared, d_sh, d_is_call, d_pairs, d_err, d_span;
-    DevBuf d_pos, d_anchor, d_ref_n, d_alt_n, d_ref_src, d_alt_src, d_ref_off, d_alt_off, d_ref_out, d_alt_out;
-    PhiDevGuard guard{{&d_pos_of, &d_ref_len, &d_r_base, &d_q_own, &d_seg, &d_q_len, &d_q_base, &d_shared, &d_sh, &d_is_call, &d_pairs, &d_err, &d_span,
-                       &d_pos, &d_anchor, &d_ref_n, &d_alt_n, &d_ref_src, &d_alt_src, &d_ref_off, &d_alt_off, &d_ref_out, &d_alt_out}};
+    DevBuf d_pos_of, d_ref_len, d_q_own, d_seg, d_q_len, d_shared, d_sh, d_is_call, d_pairs, d_err, d_span;
+    DevBuf d_pos, d_ref_n, d_alt_n, d_ref_off, d_alt_off, d_ref_out, d_alt_out;
+    PhiDevGuard guard{{&d_pos_of, &d_ref_len, &d_q_own, &d_seg, &d_q_len, &d_shared, &d_sh, &d_is_call, &d_pairs, &d_err, &d_span,
+                       &d_pos, &d_ref_n, &d_alt_n, &d_ref_off, &d_alt_off, &d_ref_out, &d_alt_out}};
+    // (these five stay behind the call, for phi_calls_support)
+    DevBuf &d_r_base = K.d_r_base, &d_q_base = K.d_q_base, &d_anchor = K.d_anchor, &d_ref_src = K.d_ref_src, &d_alt_src = K.d_alt_src;
     CallsEvents ev;
     for (int i = 0; i < 5; i++) HIPCHK(hipEventCreate(&ev.e[i]));
     PHICHK(phi_dev_ensure(c, d_pos_of, (size_t)n_vtx * 4));
@@ -366,6 +368,18 @@ int calls_impl(phi_ctx *c, const char *what, const int32_t *d_query, int64_t n_q
                        + 2 * (ref_total + alt_total)            // fill: a sequence byte read, a byte written
                        + 60 * ((ref_total + alt_total + 3) / 4);// fill, per lane: its call's record and offsets (32), two base offsets, the entry, seq_off[] (28); the searches' probes, shared between neighbouring lanes, are not counted
     K.info = info;
+    K.ref_walk = r;
+    {
+        // the query as stretches of walk entries, for phi_calls_support: a walk is one stretch
+        const size_t ns = q_ent0 >= 0 ? 1 : c->path_segs.size();
+        K.stretches.assign(3 * ns + 1, 0);
+        for (size_t s = 0; s < ns; s++) {
+            const int64_t es = q_ent0 >= 0 ? q_ent0 : c->path_segs[s].es;
+            K.stretches[s + 1] = K.stretches[s] + (q_ent0 >= 0 ? (int64_t)n_query : c->path_segs[s].ee - es + 1);
+            K.stretches[ns + 1 + s] = es;
+            K.stretches[2 * ns + 1 + s] = q_ent0 >= 0 ? q_ent0 : c->h_walk_off[(size_t)c->path_segs[s].h];
+        }
+    }
     K.span[0] = span[0]; K.span[1] = span[1]; K.span[2] = span[2]; K.span[3] = span[3];
     K.have = true;
     if (out) {
@@ -407,7 +421,7 @@ int phi_calls_path(phi_ctx *c, int32_t ref_walk, phi_calls *out)
     HIPCHK(hipSetDevice(c->device));
     int64_t n = 0;
     for (const auto &s : c->path_segs) n += s.ee - s.es + 1;
-    return calls_impl(c, "phi_calls_path", nullptr, n, ref_walk, out);
+    return calls_impl(c, "phi_calls_path", nullptr, -1, n, ref_walk, out);
 }
 
 int phi_calls_walk(phi_ctx *c, int32_t walk, int32_t ref_walk, phi_calls *out)
@@ -417,7 +431,7 @@ int phi_calls_walk(phi_ctx *c, int32_t walk, int32_t ref_walk, phi_calls *out)
     if (walk < 0 || walk >= c->n_walks)
         return phi_fail(c, PHI_ERR_INVALID, "phi_calls_walk: walk %d is not among the set graph's %d walks", walk, c->n_walks);
     HIPCHK(hipSetDevice(c->device));
-    return calls_impl(c, "phi_calls_walk", c->d_walk_vtx.as<int32_t>() + c->h_walk_off[(size_t)walk],
+    return calls_impl(c, "phi_calls_walk", c->d_walk_vtx.as<int32_t>() + c->h_walk_off[(size_t)walk], c->h_walk_off[(size_t)walk],
                       c->h_walk_off[(size_t)walk + 1] - c->h_walk_off[(size_t)walk], ref_walk, out);
 }
 

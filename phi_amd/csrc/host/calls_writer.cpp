@@ -16,11 +16,16 @@ int fail(char *err, int err_cap, int code, const std::string &msg)
     return code;
 }
 
-// the file's text; the arguments are checked by the callers
+// the four count arrays of phi_calls_support (phi_amd.h), or none: the plain file
+struct Support { const int32_t *alt_hit, *alt_n, *ref_hit, *ref_n; };
+
+// the file's text, with FORMAT/AK and RK where sup is given; the arguments are checked by the callers
 int format_calls(std::string &out, const char *contig, int64_t contig_len, const char *sample, int64_t n_calls, const int64_t *pos, const int64_t *ref_off,
-                 const char *ref_bytes, const int64_t *alt_off, const char *alt_bytes, const char *const *ph, int64_t *n_written, int64_t *n_dropped,
-                 char *err, int err_cap, const char *who)
+                 const char *ref_bytes, const int64_t *alt_off, const char *alt_bytes, const char *const *ph, const Support *sup, int64_t *n_written,
+                 int64_t *n_dropped, char *err, int err_cap, const char *who)
 {
+    if (sup && n_calls > 0 && (!sup->alt_hit || !sup->alt_n || !sup->ref_hit || !sup->ref_n))
+        return fail(err, err_cap, PHI_HOST_ERR_INVALID, std::string(who) + ": null argument");
     if (!contig || !sample || n_calls < 0 || (n_calls > 0 && (!pos || !ref_off || !alt_off || !ref_bytes || !alt_bytes)))
         return fail(err, err_cap, PHI_HOST_ERR_INVALID, std::string(who) + ": null argument");
     for (int64_t k = 0; k < n_calls; k++)
@@ -31,6 +36,10 @@ int format_calls(std::string &out, const char *contig, int64_t contig_len, const
     out += ",length=" + std::to_string((long long)contig_len) + ">\n";
     out += "##INFO=<ID=PH,Number=1,Type=String,Description=\"Panel haplotype the inferred path follows through the call\">\n";
     out += "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n";
+    if (sup) {
+        out += "##FORMAT=<ID=AK,Number=2,Type=Integer,Description=\"ALT witness minimisers: seen in the reads, all\">\n";
+        out += "##FORMAT=<ID=RK,Number=2,Type=Integer,Description=\"REF witness minimisers: seen in the reads, all\">\n";
+    }
     out += "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t";
     out += sample;
     out += '\n';
@@ -47,8 +56,12 @@ int format_calls(std::string &out, const char *contig, int64_t contig_len, const
         out += '\t';
         out.append(a, an);
         const char *name = ph ? ph[k] : nullptr;
-        if (name && *name) { out += "\t.\tPASS\tPH="; out += name; out += "\tGT\t1\n"; }
-        else out += "\t.\tPASS\t.\tGT\t1\n";
+        if (name && *name) { out += "\t.\tPASS\tPH="; out += name; }
+        else out += "\t.\tPASS\t.";
+        if (sup) {
+            out += "\tGT:AK:RK\t1:" + std::to_string(sup->alt_hit[k]) + "," + std::to_string(sup->alt_n[k]) + ":" + std::to_string(sup->ref_hit[k]) + "," +
+                   std::to_string(sup->ref_n[k]) + "\n";
+        } else out += "\tGT\t1\n";
         nw++;
     }
     if (n_written) *n_written = nw;
@@ -66,42 +79,40 @@ int hand_over(const std::string &text, char **out, int64_t *n)
     return PHI_HOST_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int phi_format_calls_vcf(const char *contig, int64_t contig_len, const char *sample, int64_t n_calls, const int64_t *pos, const int64_t *ref_off,
-                         const char *ref_bytes, const int64_t *alt_off, const char *alt_bytes, const char *const *ph, char **out, int64_t *n,
-                         int64_t *n_written, int64_t *n_dropped, char *err, int err_cap)
+// the text handed out in memory: the body of phi_format_calls_vcf and phi_format_calls_vcf_support
+int format_to_memory(const char *contig, int64_t contig_len, const char *sample, int64_t n_calls, const int64_t *pos, const int64_t *ref_off,
+                     const char *ref_bytes, const int64_t *alt_off, const char *alt_bytes, const char *const *ph, const Support *sup, char **out, int64_t *n,
+                     int64_t *n_written, int64_t *n_dropped, char *err, int err_cap, const char *who)
 {
     if (n_written) *n_written = 0;
     if (n_dropped) *n_dropped = 0;
-    if (!out || !n) return fail(err, err_cap, PHI_HOST_ERR_INVALID, "phi_format_calls_vcf: null argument");
+    if (!out || !n) return fail(err, err_cap, PHI_HOST_ERR_INVALID, std::string(who) + ": null argument");
     *out = nullptr;
     *n = 0;
     std::string text;
     int64_t nw = 0, nd = 0;
-    const int rc = format_calls(text, contig, contig_len, sample, n_calls, pos, ref_off, ref_bytes, alt_off, alt_bytes, ph, &nw, &nd, err, err_cap, "phi_format_calls_vcf");
+    const int rc = format_calls(text, contig, contig_len, sample, n_calls, pos, ref_off, ref_bytes, alt_off, alt_bytes, ph, sup, &nw, &nd, err, err_cap, who);
     if (rc) return rc;
-    if (hand_over(text, out, n)) return fail(err, err_cap, PHI_HOST_ERR_IO, "phi_format_calls_vcf: out of memory");
+    if (hand_over(text, out, n)) return fail(err, err_cap, PHI_HOST_ERR_IO, std::string(who) + ": out of memory");
     if (n_written) *n_written = nw;
     if (n_dropped) *n_dropped = nd;
     return PHI_HOST_OK;
 }
 
-int phi_write_calls_vcf(const char *path, const char *contig, int64_t contig_len, const char *sample, int64_t n_calls, const int64_t *pos,
-                        const int64_t *ref_off, const char *ref_bytes, const int64_t *alt_off, const char *alt_bytes, const char *const *ph,
-                        int64_t *n_written, int64_t *n_dropped, char *err, int err_cap)
+// the text written to a file: the body of phi_write_calls_vcf and phi_write_calls_vcf_support
+int format_to_file(const char *path, const char *contig, int64_t contig_len, const char *sample, int64_t n_calls, const int64_t *pos, const int64_t *ref_off,
+                   const char *ref_bytes, const int64_t *alt_off, const char *alt_bytes, const char *const *ph, const Support *sup, int64_t *n_written,
+                   int64_t *n_dropped, char *err, int err_cap, const char *who)
 {
     if (n_written) *n_written = 0;
     if (n_dropped) *n_dropped = 0;
-    if (!path) return fail(err, err_cap, PHI_HOST_ERR_INVALID, "phi_write_calls_vcf: null argument");
+    if (!path) return fail(err, err_cap, PHI_HOST_ERR_INVALID, std::string(who) + ": null argument");
     const size_t pn = strlen(path);
     if (pn >= 3 && strcmp(path + pn - 3, ".gz") == 0)
         return fail(err, err_cap, PHI_HOST_ERR_INVALID, std::string("cannot write ") + path + ": this writer writes plain text and has no deflate of its own; give a name that does not end in .gz, or compress the text of phi_format_calls_vcf with phi_deflate_bgzf (PHI --bgzf, write_vcf(bgzf=True))");
     std::string text;
     int64_t nw = 0, nd = 0;
-    const int rc = format_calls(text, contig, contig_len, sample, n_calls, pos, ref_off, ref_bytes, alt_off, alt_bytes, ph, &nw, &nd, err, err_cap, "phi_write_calls_vcf");
+    const int rc = format_calls(text, contig, contig_len, sample, n_calls, pos, ref_off, ref_bytes, alt_off, alt_bytes, ph, sup, &nw, &nd, err, err_cap, who);
     if (rc) return rc;
     FILE *fp = fopen(path, "w");
     if (!fp) return fail(err, err_cap, PHI_HOST_ERR_IO, std::string("cannot write ") + path);
@@ -110,6 +121,46 @@ int phi_write_calls_vcf(const char *path, const char *contig, int64_t contig_len
     if (n_written) *n_written = nw;
     if (n_dropped) *n_dropped = nd;
     return PHI_HOST_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int phi_format_calls_vcf(const char *contig, int64_t contig_len, const char *sample, int64_t n_calls, const int64_t *pos, const int64_t *ref_off,
+                         const char *ref_bytes, const int64_t *alt_off, const char *alt_bytes, const char *const *ph, char **out, int64_t *n,
+                         int64_t *n_written, int64_t *n_dropped, char *err, int err_cap)
+{
+    return format_to_memory(contig, contig_len, sample, n_calls, pos, ref_off, ref_bytes, alt_off, alt_bytes, ph, nullptr, out, n, n_written, n_dropped, err,
+                            err_cap, "phi_format_calls_vcf");
+}
+
+int phi_format_calls_vcf_support(const char *contig, int64_t contig_len, const char *sample, int64_t n_calls, const int64_t *pos, const int64_t *ref_off,
+                                 const char *ref_bytes, const int64_t *alt_off, const char *alt_bytes, const char *const *ph, const int32_t *alt_hit,
+                                 const int32_t *alt_n, const int32_t *ref_hit, const int32_t *ref_n, char **out, int64_t *n, int64_t *n_written,
+                                 int64_t *n_dropped, char *err, int err_cap)
+{
+    const Support sup{alt_hit, alt_n, ref_hit, ref_n};
+    return format_to_memory(contig, contig_len, sample, n_calls, pos, ref_off, ref_bytes, alt_off, alt_bytes, ph, &sup, out, n, n_written, n_dropped, err,
+                            err_cap, "phi_format_calls_vcf_support");
+}
+
+int phi_write_calls_vcf(const char *path, const char *contig, int64_t contig_len, const char *sample, int64_t n_calls, const int64_t *pos,
+                        const int64_t *ref_off, const char *ref_bytes, const int64_t *alt_off, const char *alt_bytes, const char *const *ph,
+                        int64_t *n_written, int64_t *n_dropped, char *err, int err_cap)
+{
+    return format_to_file(path, contig, contig_len, sample, n_calls, pos, ref_off, ref_bytes, alt_off, alt_bytes, ph, nullptr, n_written, n_dropped, err,
+                          err_cap, "phi_write_calls_vcf");
+}
+
+int phi_write_calls_vcf_support(const char *path, const char *contig, int64_t contig_len, const char *sample, int64_t n_calls, const int64_t *pos,
+                                const int64_t *ref_off, const char *ref_bytes, const int64_t *alt_off, const char *alt_bytes, const char *const *ph,
+                                const int32_t *alt_hit, const int32_t *alt_n, const int32_t *ref_hit, const int32_t *ref_n, int64_t *n_written,
+                                int64_t *n_dropped, char *err, int err_cap)
+{
+    const Support sup{alt_hit, alt_n, ref_hit, ref_n};
+    return format_to_file(path, contig, contig_len, sample, n_calls, pos, ref_off, ref_bytes, alt_off, alt_bytes, ph, &sup, n_written, n_dropped, err,
+                          err_cap, "phi_write_calls_vcf_support");
 }
 
 // exactly the bytes phi_write_fasta (reads_reader.cpp) writes: ">" name " LN:" len, then 80-column lines

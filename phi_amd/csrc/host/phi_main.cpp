@@ -11,6 +11,7 @@
 //                                                             (data/chop_graph.sh:46-66); -o 'out.{panel}.fa': one FASTA per panel
 //         [--calls FILE [--calls-ref NAME] [--calls-contig NAME]]   the inferred haplotype as variant calls against a reference walk
 //                                                             (plain-text VCF; one --calls per -o, in order, same placeholder)
+//         [--calls-support]                                   FORMAT/AK and RK in every --calls file: the witness minimisers of ALT and REF, seen in the reads and all
 //         [--bgzf]                                            every -o and --calls file as BGZF, compressed on the device
 //   ./PHI -g <target.gfa> -r a.fq -o a.fa -r b.fq -o b.fa ...      several read sets against ONE graph: the graph is parsed and
 //         indexed once (the reference's harness runs PHI once per sample x coverage on the same graph,
@@ -146,6 +147,7 @@ static void usage(FILE *fp, int k, int w, int R, int q, int m, float T, int t, c
     fprintf(fp, "    --calls FILE           the inferred haplotype as variant calls (plain-text VCFv4.2; .gz only with --bgzf) against a reference walk of\n");
     fprintf(fp, "                           the graph; one per -o, in order, with the same {cov} / {panel} placeholder where -o takes one.\n");
     fprintf(fp, "                           The rule is this program's own (not vg deconstruct's): nothing is trimmed or left-aligned\n");
+    fprintf(fp, "    --calls-support        with --calls: per record FORMAT/AK and RK, the minimisers that witness ALT and REF -- seen in the reads, all\n");
     fprintf(fp, "    --calls-ref NAME       the reference walk, named as the log names walks (SAMPLE.HAP); required with -g, REF.0 with --vcf;\n");
     fprintf(fp, "                           under a panel it must be among the kept walks (--panel-always keeps it)\n");
     fprintf(fp, "    --calls-contig NAME    the contig of the records [--vcf: the VCF's contig; -g: the reference walk's name].  With -g POS\n");
@@ -186,6 +188,7 @@ struct Options {
     // (phi_calls_path, phi_write_calls_vcf; no reference counterpart: for the comparison of data/run_PG.py:54-60); one per -o
     std::vector<std::string> calls_files;
     std::string calls_ref, calls_contig;
+    bool calls_support = false;                               // --calls-support: FORMAT/AK and RK in every --calls file (phi_calls_support)
     bool bgzf = false;                                        // --bgzf: every -o and --calls file compressed into BGZF blocks on the device
     bool panel() const { return have_keep || have_drop || !panel_sizes.empty() || panel_auto > 0; }
     int argc = 0;
@@ -1186,6 +1189,11 @@ struct Driver {
         phi_calls_info ci;
         int rc;
         if ((rc = phi_calls_path(ctx, r, &cl)) || (rc = phi_calls_stats(ctx, &ci))) return fail_on(ctx, "calls", rc);
+        phi_call_support sup{};                               // --calls-support: the read support of every call, counted behind the calls
+        if (o.calls_support) {
+            Stage ss("calls support (device)");
+            if ((rc = phi_calls_support(ctx, &sup))) return fail_on(ctx, "calls support", rc);
+        }
         const char *ref_name = walk_name(r);
         const bool vcf_ref = o.from_vcf && !strcmp(ref_name, "REF.0");
         const std::string contig = !o.calls_contig.empty() ? o.calls_contig : vcf_ref ? phi_vcf_contig(vcf) : ref_name;
@@ -1197,16 +1205,26 @@ struct Driver {
         if (o.bgzf) {
             char *text = nullptr;
             int64_t n_text = 0;
-            if (phi_format_calls_vcf(contig.c_str(), contig_len, hap_name, cl.n_calls, cl.pos, cl.ref_off, cl.ref_bytes, cl.alt_off, cl.alt_bytes, ph.data(), &text, &n_text,
-                                     &n_written, &n_dropped, werr, sizeof werr) != PHI_HOST_OK)
+            const int frc = o.calls_support
+                                ? phi_format_calls_vcf_support(contig.c_str(), contig_len, hap_name, cl.n_calls, cl.pos, cl.ref_off, cl.ref_bytes, cl.alt_off, cl.alt_bytes,
+                                                               ph.data(), sup.alt_hit, sup.alt_n, sup.ref_hit, sup.ref_n, &text, &n_text, &n_written, &n_dropped, werr, sizeof werr)
+                                : phi_format_calls_vcf(contig.c_str(), contig_len, hap_name, cl.n_calls, cl.pos, cl.ref_off, cl.ref_bytes, cl.alt_off, cl.alt_bytes, ph.data(),
+                                                       &text, &n_text, &n_written, &n_dropped, werr, sizeof werr);
+            if (frc != PHI_HOST_OK)
                 return fail("[E::main] %s\n", werr[0] ? werr : "cannot format the calls");
             const int wrc = write_bgzf(file, text, n_text);
             phi_host_free_text(text);
             if (wrc) return 1;
-        } else if (phi_write_calls_vcf(file.c_str(), contig.c_str(), contig_len, hap_name, cl.n_calls, cl.pos, cl.ref_off, cl.ref_bytes, cl.alt_off, cl.alt_bytes,
-                                       ph.data(), &n_written, &n_dropped, werr, sizeof werr) != PHI_HOST_OK)
+        } else if ((o.calls_support
+                        ? phi_write_calls_vcf_support(file.c_str(), contig.c_str(), contig_len, hap_name, cl.n_calls, cl.pos, cl.ref_off, cl.ref_bytes, cl.alt_off,
+                                                      cl.alt_bytes, ph.data(), sup.alt_hit, sup.alt_n, sup.ref_hit, sup.ref_n, &n_written, &n_dropped, werr, sizeof werr)
+                        : phi_write_calls_vcf(file.c_str(), contig.c_str(), contig_len, hap_name, cl.n_calls, cl.pos, cl.ref_off, cl.ref_bytes, cl.alt_off, cl.alt_bytes,
+                                              ph.data(), &n_written, &n_dropped, werr, sizeof werr)) != PHI_HOST_OK)
             return fail("[E::main] %s\n", werr[0] ? werr : "cannot write the calls");
         stamp("main");
+        if (o.calls_support)
+            fprintf(stderr, "Call support: %lld calls, %lld of %lld ALT and %lld of %lld REF witness minimisers seen\n", (long long)sup.n_calls,
+                    (long long)sup.alt_hit_total, (long long)sup.alt_n_total, (long long)sup.ref_hit_total, (long long)sup.ref_n_total);
         fprintf(stderr, "Calls: %lld written to %s, %lld dropped as REF = ALT; called span [%lld,%lld) of %s (%lld bases), [%lld,%lld) of the haplotype\n",
                 (long long)n_written, file.c_str(), (long long)n_dropped, (long long)cl.ref_span[0], (long long)cl.ref_span[1], ref_name, (long long)ci.ref_bases,
                 (long long)cl.query_span[0], (long long)cl.query_span[1]);
@@ -1433,7 +1451,7 @@ int main(int argc, char *argv[])
                                            {"keep-samples", required_argument, 0, 311}, {"drop-samples", required_argument, 0, 312}, {"panels", required_argument, 0, 313},
                                            {"panel-seed", required_argument, 0, 314}, {"panel-always", required_argument, 0, 315},
                                            {"panel-auto", required_argument, 0, 316}, {"panel-blocks", required_argument, 0, 317},
-                                           {"calls", required_argument, 0, 318}, {"calls-ref", required_argument, 0, 319}, {"calls-contig", required_argument, 0, 320}, {"bgzf", no_argument, 0, 321}, {0, 0, 0, 0}};
+                                           {"calls", required_argument, 0, 318}, {"calls-ref", required_argument, 0, 319}, {"calls-contig", required_argument, 0, 320}, {"bgzf", no_argument, 0, 321}, {"calls-support", no_argument, 0, 322}, {0, 0, 0, 0}};
     int c;
     std::string gfa_arg, vcf_arg;
     // main.cpp:38 declares -h with an argument; a bare -h falls into the usage branch either way
@@ -1499,6 +1517,7 @@ int main(int argc, char *argv[])
         else if (c == 319) o.calls_ref = optarg;
         else if (c == 320) o.calls_contig = optarg;
         else if (c == 321) o.bgzf = true;
+        else if (c == 322) o.calls_support = true;
         else if (c == 304) o.shard_min_bases = std::max<long long>(1, atoll(optarg));
         else if (c == 303) {                                   // --devices 0,1,2,...: shard the reads over these GPUs
             o.devices.clear();
@@ -1551,6 +1570,7 @@ int main(int argc, char *argv[])
     }
     if (o.calls_files.empty()) {
         if (!o.calls_ref.empty() || !o.calls_contig.empty()) { fprintf(stderr, "[E::main] --calls-ref and --calls-contig go with --calls FILE\n"); return 1; }
+        if (o.calls_support) { fprintf(stderr, "[E::main] --calls-support goes with --calls FILE: it adds the read support of every call to that file\n"); return 1; }
     } else {
         if (o.calls_files.size() != o.hap_files.size()) { fprintf(stderr, "[E::main] %zu --calls but %zu -o: one --calls per -o, paired in order (-r a.fq -o a.fa --calls a.vcf -r b.fq -o b.fa --calls b.vcf ...), or none at all\n", o.calls_files.size(), o.hap_files.size()); return 1; }
         if (!o.from_vcf && o.calls_ref.empty()) { fprintf(stderr, "[E::main] --calls with -g needs --calls-ref NAME: the walk the calls are made against, named as the log names walks (SAMPLE.HAP)\n"); return 1; }

@@ -217,6 +217,7 @@ int phi_set_graph_panel(phi_ctx *c, int32_t n_vtx, const char *seq_concat, const
     P.on = false;
     phi_scout_end(c);                                          // (the choice has been made: the score matrix goes before the panel's index is built)
     c->solved = false;
+    c->calls.have = false;
     // PHI_PANEL_KEEP_READS: a finished store steps aside while the graph is set anew (every stage below drops what it finds) and
     // comes back when the panel stands; on failure it goes, as the graph it was collected under has
     struct KeptReads {

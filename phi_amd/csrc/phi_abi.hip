@@ -152,7 +152,7 @@ void phi_ctx_destroy(phi_ctx *c)
                      &c->d_g_keys, &c->d_g_rep, &c->d_g_cnt, &c->d_slot_maxcnt, &c->d_slot_multi, &c->d_a_e1,
                      &c->d_g_off, &c->d_g_span, &c->d_a_weight, &c->d_dmax, &c->d_bstart, &c->d_k_rec, &c->d_k_in, &c->d_cvtx, &c->d_ev_e, &c->d_ev_off, &c->d_ev,
                      &c->d_off_end, &c->d_off_start, &c->d_scan_blk, &c->d_scan_blk64, &c->d_scan_blkoff, &c->d_top,
-                     &c->d_ent};
+                     &c->d_ent, &c->calls.d_r_base, &c->calls.d_q_base, &c->calls.d_anchor, &c->calls.d_ref_src, &c->calls.d_alt_src};
     phi_pool_flush(c->device);
     phi_pool_bypass(true);                                 // (a context that goes gives its memory back to the driver)
     struct Bypass { ~Bypass() { phi_pool_bypass(false); } } bypass_guard;

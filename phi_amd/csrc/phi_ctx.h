@@ -322,6 +322,10 @@ struct phi_ctx {
     // expands on the device (calls.hip)
     struct PhiPathSeg { int32_t h; int64_t es, ee; };
     std::vector<PhiPathSeg> path_segs;
+    struct PhiCallSrc {      // where an allele's bytes lie on its walk: first base (in bases of the walk), vertex indices [v0, v1)
+        int64_t base;
+        int32_t v0, v1;
+    };
     // ---- variant calls of the path or of a walk against a reference walk (calls.hip): the host copies phi_calls points into
     struct PhiCalls {
         bool have = false;
@@ -330,6 +334,20 @@ struct phi_ctx {
         std::vector<char> ref_bytes, alt_bytes;
         int64_t span[4] = {0, 0, 0, 0};
         phi_calls_info info{};
+        // what phi_calls_support (calls_support.hip) counts from, left on the device by the calls: the base offsets of the
+        // reference walk's and the query's entries, per call the left anchor's query index and where the alleles lie on their
+        // walks; on the host the query as stretches of walk entries ([0, n]: where every stretch starts in the query; behind:
+        // its first walk entry; behind: the first entry of its walk) and the reference walk
+        DevBuf d_r_base, d_q_base, d_anchor, d_ref_src, d_alt_src;
+        std::vector<int64_t> stretches;
+        int32_t ref_walk = 0;
+        // the read support of the calls above: the host copies phi_call_support points into
+        struct PhiSupport {
+            bool have = false;
+            std::vector<int32_t> cnt;                 // [4][n_calls]: alt_hit, alt_n, ref_hit, ref_n
+            phi_call_support out{};
+            phi_calls_support_info info{};
+        } support;
     } calls;
 
     // ---- profiling of the sketch kernel

@@ -277,6 +277,7 @@ int set_graph_check_args(phi_ctx *c, int32_t n_vtx, const char *seq_concat, cons
     c->panel.on = false;
     phi_scout_end(c);
     c->solved = false;
+    c->calls.have = false;
     phi_ladder_drop(c);                                        // (a collected read set and its bands belong to the graph they were collected under)
     return PHI_OK;
 }
@@ -789,6 +790,7 @@ extern "C" int phi_scout_graph(phi_ctx *c, int32_t n_vtx, const char *seq_concat
     P.on = false;
     phi_scout_end(c);
     c->solved = false;
+    c->calls.have = false;
     phi_ladder_drop(c);
     // (on failure below the context holds no graph and retains nothing)
     if (from == FROM_RETAINED) { phi_dev_free(c->d_walk_vtx); std::swap(c->d_walk_vtx, P.d_full); }
