@@ -714,6 +714,49 @@ int phi_deflate_bgzf_alloc(int32_t device, const void *in, int64_t n, int32_t fl
                            phi_deflate_info *info);   /* freed with phi_deflate_free */
 void phi_deflate_free(void *p);
 
+/* The same file with an index built beside it on the device, DESIGN.md 4.18.  *out[0, *out_size) is byte for byte what
+ * phi_deflate_bgzf_alloc gives for in, n and flags; *index[0, *index_size) is the finished index file; both are freed with
+ * phi_deflate_free.  index_kind is exactly one of the two values below (anything else: PHI_ERR_INVALID, nothing launched), and
+ * so is PHI_DEFLATE_NO_EOF with an index.  On any error both outputs are NULL and iinfo->detail says why.  Needs no phi_ctx.
+ *
+ * Virtual offsets: with off[0..nb] the file offsets of the members (off[nb] the EOF block's), uncompressed byte p in [0, n] is
+ * (off[p / PHI_BGZF_BLOCK] << 16) | (p % PHI_BGZF_BLOCK); so p == n with n a multiple of the block size points at the EOF block.
+ *
+ * PHI_BGZF_INDEX_GZI: little-endian uint64 count nb - 1 (0 for nb <= 1), then for the members 1 .. nb-1 the pair (off[b],
+ * PHI_BGZF_BLOCK * b).  Built on the host from the members' sizes; no kernel runs for it.
+ *
+ * PHI_BGZF_INDEX_TBI_VCF: a tabix index with the VCF preset, itself BGZF.  The text is lines ended by '\n' (a last line without
+ * one counts); a line beginning with '#' is a meta line wherever it stands, every other line a record of at least the 8 fields
+ * CHROM POS ID REF ALT QUAL FILTER INFO.  Contigs are numbered by first appearance.  beg = POS - 1 (at least 0), end = beg +
+ * len(REF), or the value of the first key END of INFO (the field begins with "END=" or holds ";END="); an end <= beg becomes
+ * beg + 1.  bin = reg2bin(beg, end) of the SAM/tabix specification (5 levels, 14 bits).  A chunk is a maximal run of records
+ * consecutive in the file that share contig and bin, from the virtual offset of its first record's first byte to that of the
+ * byte after its last record's line; within a contig bins ascend, within a bin chunks keep file order; no merging of chunks,
+ * no pseudo-bin 37450.  The linear index of a contig has ((max end - 1) >> 14) + 1 windows, window w the smallest virtual
+ * offset of a record start among the records overlapping [w << 14, (w + 1) << 14); an empty window takes its predecessor's
+ * value, leading ones 0.  Header: "TBI\1", n_ref, format 2, col_seq 1, col_beg 2, col_end 0, meta '#', skip 0, l_nm, the
+ * NUL-terminated names; per contig n_bin, the bins, n_intv, the offsets; then n_no_coor = 0 (uint64).  A text without a record
+ * (n_ref 0) and n == 0 are valid.
+ * PHI_ERR_INVALID: a record with fewer than 8 fields; an empty line; a POS or END value that is empty, not all digits or longer
+ * than 10 digits; a POS smaller than the previous record's on the same contig; a contig name that comes back after another
+ * contig.  PHI_ERR_UNSUPPORTED: an end above 2^29 (CSI would be needed and is not written); a contig name above 1024 bytes; more
+ * than 2^31 - 2 lines.  PHI_ERR_NOMEM: the text does not fit the device beside a batch's buffers.
+ *
+ * These rules are stated here and checked against themselves (a per-line writer and an index reader in tests/tabix_ref.py): the
+ * bytes are NOT compared with those of `tabix -p vcf` or `bgzip -i`, which merge chunks and add a pseudo-bin. */
+#define PHI_BGZF_INDEX_GZI     1       /* bgzip's .gzi: where every member begins, compressed and uncompressed */
+#define PHI_BGZF_INDEX_TBI_VCF 2       /* tabix .tbi with the VCF preset, itself BGZF-compressed */
+typedef struct {
+    int64_t records, meta_lines, contigs;   /* of the text (TBI); 0 for GZI */
+    int64_t bins, chunks, windows;          /* written to the index (TBI); for GZI chunks = the member entries written */
+    int64_t index_bytes;                    /* *index_size */
+    double  device_ms;                      /* GPU time of the index kernels alone, by HIP events (0 for GZI) */
+    char    detail[192];
+} phi_bgzf_index_info;
+int phi_deflate_bgzf_indexed(int32_t device, const void *in, int64_t n, int32_t flags, int32_t index_kind, void **out,
+                             int64_t *out_size, void **index, int64_t *index_size, phi_deflate_info *info,
+                             phi_bgzf_index_info *iinfo);
+
 /* A gzip GFA split on the device: the file (RFC 1952, any number of members) is inflated on the context's
  * device, the walk field of every W-line -- everything after its 6th tab, tags included, by the host reader's line rules
  * (include/phi_host.h) -- stays there, laid out as phi_walk_text_upload lays it out (phi_walk_text_resolve follows as after

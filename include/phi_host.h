@@ -224,6 +224,11 @@ int phi_write_calls_vcf(const char *path, const char *contig, int64_t contig_len
  * bytes phi_write_fasta / phi_write_calls_vcf write to their file; free it with phi_host_free_text.  phi_format_calls_vcf has
  * phi_write_calls_vcf's refusals (the file name's aside) and its count of dropped REF = ALT calls. */
 int phi_format_fasta(const char *name, const char *seq, int64_t len, char **out, int64_t *n);
+/* The one-line .fai of the file phi_format_fasta makes for this name and length (PHI --bgzf-index, beside the .gzi of
+ * phi_deflate_bgzf_indexed): NAME \t LEN \t OFFSET \t LINEBASES \t LINEWIDTH \n, with NAME the header up to its first blank,
+ * OFFSET the header line's length (where the sequence begins), LINEBASES = min(len, 80) and LINEWIDTH = LINEBASES + 1, both 0
+ * for len == 0.  Free it with phi_host_free_text.  Written from the format's description; NOT compared with `samtools faidx`. */
+int phi_format_fasta_fai(const char *name, int64_t len, char **out, int64_t *n);
 int phi_format_calls_vcf(const char *contig, int64_t contig_len, const char *sample, int64_t n_calls, const int64_t *pos, const int64_t *ref_off,
                          const char *ref_bytes, const int64_t *alt_off, const char *alt_bytes, const char *const *ph, char **out, int64_t *n,
                          int64_t *n_written, int64_t *n_dropped, char *err, int err_cap);

@@ -7,6 +7,6 @@ There is no CPU fallback: importing works anywhere, using the hot path needs the
 """
 from ._capi import (PHI_ERR_DEVICE, PHI_ERR_INVALID, PHI_ERR_NOMEM, PHI_ERR_OVERFLOW, PHI_ERR_STATE,  # noqa: F401
                     PHI_ERR_UNSUPPORTED, PHI_ERR_WALK, PHI_FLAG_MIXED, PHI_FLAG_QCLP, PHI_OK)
-from .context import Context, PhiError, TextPark, crc32_combine, deflate_bgzf, gzip_header, inflate  # noqa: F401
+from .context import Context, PhiError, TextPark, crc32_combine, deflate_bgzf, deflate_bgzf_indexed, gzip_header, inflate  # noqa: F401
 
-__all__ = ["Context", "PhiError", "TextPark", "crc32_combine", "deflate_bgzf", "gzip_header", "inflate"]
+__all__ = ["Context", "PhiError", "TextPark", "crc32_combine", "deflate_bgzf", "deflate_bgzf_indexed", "gzip_header", "inflate"]

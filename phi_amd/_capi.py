@@ -41,6 +41,7 @@ SYMBOLS = [
     "phi_reads_bam_begin", "phi_add_reads_bam", "phi_add_reads_bam_parked", "phi_reads_bam_end", "phi_reads_bam_last_batch",
     "phi_calls_path", "phi_calls_walk", "phi_calls_stats", "phi_calls_support", "phi_calls_support_stats",
     "phi_deflate_bgzf_bound", "phi_deflate_bgzf", "phi_deflate_bgzf_alloc", "phi_deflate_free",
+    "phi_deflate_bgzf_indexed",
 ]
 PHI_PANEL_RETAIN = 1
 PHI_PANEL_KEEP_READS = 2
@@ -52,6 +53,8 @@ PHI_BGZF_BLOCK = 65280
 PHI_DEFLATE_NO_MATCH = 1
 PHI_DEFLATE_NO_EOF = 2
 PHI_DEFLATE_BATCH_DEFAULT = 512
+PHI_BGZF_INDEX_GZI = 1
+PHI_BGZF_INDEX_TBI_VCF = 2
 
 
 class PhiIndexInfo(C.Structure):
@@ -147,6 +150,11 @@ class PhiInflateInfo(C.Structure):
 
 class PhiDeflateInfo(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("in_bytes", "out_bytes", "blocks", "stored_blocks", "matches", "match_bytes")] + [
+        ("device_ms", C.c_double), ("detail", C.c_char * 192)]
+
+
+class PhiBgzfIndexInfo(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("records", "meta_lines", "contigs", "bins", "chunks", "windows", "index_bytes")] + [
         ("device_ms", C.c_double), ("detail", C.c_char * 192)]
 
 
@@ -284,6 +292,8 @@ def load():
     L.phi_deflate_bgzf_bound.restype = i64
     L.phi_deflate_bgzf.argtypes = [i32, vp, i64, vp, i64, i32, C.POINTER(i64), C.POINTER(PhiDeflateInfo)]
     L.phi_deflate_bgzf_alloc.argtypes = [i32, vp, i64, i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(PhiDeflateInfo)]
+    L.phi_deflate_bgzf_indexed.argtypes = [i32, vp, i64, i32, i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(vp), C.POINTER(i64),
+                                           C.POINTER(PhiDeflateInfo), C.POINTER(PhiBgzfIndexInfo)]
     L.phi_deflate_free.argtypes = [vp]
     L.phi_deflate_free.restype = None
     L.phi_text_park_gzip_begin.argtypes = [vp, i64]

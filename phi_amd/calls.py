@@ -43,15 +43,19 @@ def ph_names(calls, path_hap, hap_names):
 SUPPORT_ARRAYS = ("alt_hit", "alt_n", "ref_hit", "ref_n")
 
 
-def write_vcf(path, calls, contig, contig_len, sample, ph=None, bgzf=False, device=0, support=None):
+def write_vcf(path, calls, contig, contig_len, sample, ph=None, bgzf=False, device=0, support=None, index=False):
     """The calls as plain-text VCFv4.2 (phi_write_calls_vcf of include/phi_host.h): one haploid sample with genotype 1, POS
     1-based, PH=<ph[k]> in INFO where ph (a list of names, one per call) is given.  Calls whose REF and ALT are the same bytes
     are dropped.  Returns (records written, calls dropped).  A name ending in .gz is refused (HostError: this writer has no
     deflate of its own) unless bgzf is set: then the same text (phi_format_calls_vcf) is compressed into BGZF blocks on
     `device` (deflate_bgzf) and written under the name as given.  support: the dict of Context.calls_support() for these
-    calls; the records then carry FORMAT/AK and RK (phi_write_calls_vcf_support), everything else is the same bytes."""
+    calls; the records then carry FORMAT/AK and RK (phi_write_calls_vcf_support), everything else is the same bytes.
+    index (needs bgzf): a tabix index of the file, built on the device beside it (deflate_bgzf_indexed), as path + ".tbi";
+    the file's bytes are the same with and without."""
     from .ilp_index import HostError, host_lib
     L = host_lib()
+    if index and not bgzf:
+        raise ValueError("index=True needs bgzf=True: the index is one of a BGZF file")
     n = int(len(calls["pos"]))
     pos = np.ascontiguousarray(calls["pos"], np.int64)
     ro = np.ascontiguousarray(calls["ref_off"], np.int64)
@@ -80,9 +84,13 @@ def write_vcf(path, calls, contig, contig_len, sample, ph=None, bgzf=False, devi
             plain = C.string_at(text, size.value)
         finally:
             L.phi_host_free_text(text)
-        from .context import deflate_bgzf
+        from .context import deflate_bgzf, deflate_bgzf_indexed
+        packed, tbi = deflate_bgzf_indexed(plain, "tbi", device=device)[:2] if index else (deflate_bgzf(plain, device=device), None)
         with open(path, "wb") as f:
-            f.write(deflate_bgzf(plain, device=device))
+            f.write(packed)
+        if index:
+            with open(os.fspath(path) + ".tbi", "wb") as f:
+                f.write(tbi)
         return nw.value, nd.value
     rc = wr(os.fsencode(path), contig.encode(), int(contig_len), sample.encode(), n, pos.ctypes.data, ro.ctypes.data, rb,
             ao.ctypes.data, ab, names, *sup, C.byref(nw), C.byref(nd), err, 512)

@@ -913,6 +913,33 @@ def deflate_bgzf(data, device=0, match=True, eof=True, with_info=False):
     return out, {n: getattr(info, n) for n, _ in _capi.PhiDeflateInfo._fields_ if n != "detail"}
 
 
+def deflate_bgzf_indexed(data, kind, device=0):
+    """data as a BGZF file with an index built beside it on `device` (include/phi_amd.h phi_deflate_bgzf_indexed).  kind:
+    "gzi" (bgzip's .gzi: where every member begins) or "tbi" (a tabix index with the VCF preset; data is then VCF text), or
+    the header's PHI_BGZF_INDEX_* value.  Returns (file, index, info): file is byte for byte deflate_bgzf(data), index the
+    finished index file, info a dict of phi_bgzf_index_info with the writer's phi_deflate_info under "deflate".  PhiError
+    for a text the index refuses (its detail says which line and why)."""
+    L = _capi.load()
+    kind = {"gzi": _capi.PHI_BGZF_INDEX_GZI, "tbi": _capi.PHI_BGZF_INDEX_TBI_VCF}.get(kind, kind)
+    buf = np.frombuffer(data, np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, np.uint8)
+    p, size, q, qsize = C.c_void_p(), C.c_int64(), C.c_void_p(), C.c_int64()
+    info, iinfo = _capi.PhiDeflateInfo(), _capi.PhiBgzfIndexInfo()
+    rc = L.phi_deflate_bgzf_indexed(device, _ptr(buf) if len(buf) else None, len(buf), 0, int(kind), C.byref(p), C.byref(size),
+                                    C.byref(q), C.byref(qsize), C.byref(info), C.byref(iinfo))
+    if rc:
+        assert not p.value and not q.value
+        raise PhiError(rc, iinfo.detail.decode())
+    try:
+        out = C.string_at(p, size.value) if size.value else b""
+        index = C.string_at(q, qsize.value) if qsize.value else b""
+    finally:
+        L.phi_deflate_free(p)
+        L.phi_deflate_free(q)
+    d = {n: getattr(iinfo, n) for n, _ in _capi.PhiBgzfIndexInfo._fields_ if n != "detail"}
+    d["deflate"] = {n: getattr(info, n) for n, _ in _capi.PhiDeflateInfo._fields_ if n != "detail"}
+    return out, index, d
+
+
 def gzip_header(data, pos=0):
     """The offset of the deflate data of the gzip member header at data[pos:] (PhiError when there is none)."""
     L = _capi.load()

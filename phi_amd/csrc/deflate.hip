@@ -409,8 +409,12 @@ int check_args(const void *in, int64_t n, int32_t flags, int64_t *out_size, phi_
     return PHI_OK;
 }
 
-// the whole file into dst[0, phi_deflate_bgzf_bound(n)) on the host; *out_size = its bytes (arguments checked by the caller)
-int deflate_run(int32_t device, const uint8_t *src, int64_t n, int32_t flags, uint8_t *dst, int64_t *out_size, phi_deflate_info *info)
+// the whole file into dst[0, phi_deflate_bgzf_bound(n)) on the host; *out_size = its bytes (arguments checked by the caller).
+// d_src (may be null): the same n bytes already on the device, 64 readable bytes behind them -- the batches then read their
+// blocks there and nothing is uploaded.  member_off (may be null) receives off[0..blocks]: where every member begins in the
+// file, and where the EOF block does (bgzf_index.hip; phi_deflate_run below)
+int deflate_run(int32_t device, const uint8_t *src, int64_t n, int32_t flags, uint8_t *dst, int64_t *out_size, phi_deflate_info *info,
+                const uint8_t *d_src = nullptr, std::vector<int64_t> *member_off = nullptr)
 {
     const int64_t nb_all = n_blocks(n);
     int64_t total = 0;
@@ -424,7 +428,7 @@ int deflate_run(int32_t device, const uint8_t *src, int64_t n, int32_t flags, ui
         hipStream_t st = dev.st;
         const int64_t B = std::min(batch_blocks(), nb_all);
         const bool no_match = (flags & PHI_DEFLATE_NO_MATCH) != 0;
-        DALLOC(d_in, uint8_t, (size_t)B * PHI_BGZF_BLOCK + 64);
+        DALLOC(d_in, uint8_t, d_src ? 16 : (size_t)B * PHI_BGZF_BLOCK + 64);
         DALLOC(d_res, uint32_t, no_match ? 16 : (size_t)B * PHI_BGZF_BLOCK * 4);
         DALLOC(d_stage, uint8_t, (size_t)B * DFL_SLOT);
         DALLOC(d_stat, DflBlockStat, (size_t)B * sizeof(DflBlockStat));
@@ -434,9 +438,9 @@ int deflate_run(int32_t device, const uint8_t *src, int64_t n, int32_t flags, ui
         for (int64_t b0 = 0; b0 < nb_all; b0 += B) {
             const int nb = (int)std::min(B, nb_all - b0);
             const int64_t at = b0 * PHI_BGZF_BLOCK, bytes = std::min<int64_t>(n - at, (int64_t)nb * PHI_BGZF_BLOCK);
-            DCHK(hipMemcpyAsync(d_in, src + at, (size_t)bytes, hipMemcpyHostToDevice, st));
+            if (!d_src) DCHK(hipMemcpyAsync(d_in, src + at, (size_t)bytes, hipMemcpyHostToDevice, st));
             DCHK(hipEventRecord(dev.ev[0], st));
-            hipLaunchKernelGGL(phi_deflate_block_kernel, dim3((unsigned)nb), dim3(DFL_T), 0, st, d_in, bytes, d_res, d_stage, d_stat, no_match ? 1 : 0);
+            hipLaunchKernelGGL(phi_deflate_block_kernel, dim3((unsigned)nb), dim3(DFL_T), 0, st, d_src ? d_src + at : d_in, bytes, d_res, d_stage, d_stat, no_match ? 1 : 0);
             DCHK(hipGetLastError());
             hipLaunchKernelGGL(phi_deflate_offsets_kernel, dim3(1), dim3(1024), 0, st, d_stat, nb, d_off);
             DCHK(hipGetLastError());
@@ -451,6 +455,10 @@ int deflate_run(int32_t device, const uint8_t *src, int64_t n, int32_t flags, ui
                 return fail(info, PHI_ERR_DEVICE, "phi_deflate_bgzf: %d blocks came back as %lld bytes (internal error)", nb, (long long)got);
             DCHK(hipMemcpyAsync(dst + total, d_out, (size_t)got, hipMemcpyDeviceToHost, st));
             DCHK(hipStreamSynchronize(st));
+            if (member_off) {
+                int64_t o = total;
+                for (int b = 0; b < nb; b++) { member_off->push_back(o); o += stat[(size_t)b].size; }
+            }
             total += got;
             if (info) {
                 float ms = 0;
@@ -464,6 +472,7 @@ int deflate_run(int32_t device, const uint8_t *src, int64_t n, int32_t flags, ui
             }
         }
     }
+    if (member_off) member_off->push_back(total);
     if (!(flags & PHI_DEFLATE_NO_EOF)) { memcpy(dst + total, BGZF_EOF, sizeof BGZF_EOF); total += (int64_t)sizeof BGZF_EOF; }
     if (info) info->out_bytes = total;
     *out_size = total;
@@ -471,6 +480,15 @@ int deflate_run(int32_t device, const uint8_t *src, int64_t n, int32_t flags, ui
 }
 
 }  // namespace
+
+int phi_deflate_run(int32_t device, const uint8_t *src, const uint8_t *d_src, int64_t n, int32_t flags, uint8_t *dst, int64_t *out_size,
+                    phi_deflate_info *info, std::vector<int64_t> *member_off)
+{
+    if (info) memset(info, 0, sizeof(*info));
+    if (member_off) member_off->clear();
+    *out_size = 0;
+    return deflate_run(device, src, n, flags, dst, out_size, info, d_src, member_off);
+}
 
 extern "C" {
 

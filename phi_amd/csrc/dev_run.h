@@ -49,6 +49,12 @@ template <class Info> int fail(Info *info, int code, const char *fmt, ...)
 
 }  // namespace
 
+// deflate.hip: the BGZF writer's run for the indexed entry (bgzf_index.hip).  The file of src[0, n) into dst[0,
+// phi_deflate_bgzf_bound(n)); d_src (may be null): the same bytes already on the device, 64 readable bytes behind them, from
+// which the batches then read; member_off (may be null): off[0..blocks], where every member and the EOF block begin
+int phi_deflate_run(int32_t device, const uint8_t *src, const uint8_t *d_src, int64_t n, int32_t flags, uint8_t *dst, int64_t *out_size,
+                    phi_deflate_info *info, std::vector<int64_t> *member_off);
+
 // inside a function with `info` (and, for DALLOC, a Dev `dev`) in scope that returns a status
 #define DCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(info, PHI_ERR_DEVICE, "%s: %s", #call, hipGetErrorString(e_)); } while (0)
 #define DALLOC(var, T, bytes) T *var = dev.alloc<T>(bytes); if (!var) return fail(info, PHI_ERR_NOMEM, "device allocation of %zu bytes failed", (size_t)(bytes))

@@ -184,6 +184,24 @@ int phi_format_fasta(const char *name, const char *seq, int64_t len, char **out,
     return PHI_HOST_OK;
 }
 
+// the .fai line of that text: NAME (the header up to its first blank), LEN, where the sequence begins, bases and bytes per line
+int phi_format_fasta_fai(const char *name, int64_t len, char **out, int64_t *n)
+{
+    if (!name || !out || !n || len < 0) return PHI_HOST_ERR_INVALID;
+    const std::string head = std::string(">") + name + " LN:" + std::to_string((long long)len) + "\n";
+    size_t id = 0;
+    while (name[id] && name[id] != ' ' && name[id] != '\t') id++;
+    const long long bases = len < 80 ? len : 80, width = len > 0 ? bases + 1 : 0;
+    const std::string line = std::string(name, id) + "\t" + std::to_string((long long)len) + "\t" + std::to_string(head.size()) + "\t" +
+                             std::to_string(bases) + "\t" + std::to_string(width) + "\n";
+    char *p = (char *)malloc(line.size());
+    if (!p) return PHI_HOST_ERR_IO;
+    memcpy(p, line.data(), line.size());
+    *out = p;
+    *n = (int64_t)line.size();
+    return PHI_HOST_OK;
+}
+
 void phi_host_free_text(char *p) { free(p); }
 
 }  // extern "C"

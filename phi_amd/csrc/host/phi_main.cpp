@@ -13,6 +13,7 @@
 //                                                             (plain-text VCF; one --calls per -o, in order, same placeholder)
 //         [--calls-support]                                   FORMAT/AK and RK in every --calls file: the witness minimisers of ALT and REF, seen in the reads and all
 //         [--bgzf]                                            every -o and --calls file as BGZF, compressed on the device
+//         [--bgzf-index]                                      with --bgzf: FILE.tbi beside every --calls file, FILE.gzi and FILE.fai beside every -o file
 //   ./PHI -g <target.gfa> -r a.fq -o a.fa -r b.fq -o b.fa ...      several read sets against ONE graph: the graph is parsed and
 //         indexed once (the reference's harness runs PHI once per sample x coverage on the same graph,
 //         data/run_batch_4_miqp.py:31-46), every job prints the log of a run of its own and writes its own FASTA
@@ -144,6 +145,7 @@ static void usage(FILE *fp, int k, int w, int R, int q, int m, float T, int t, c
     fprintf(fp, "    -o INT       Output haplotype [%s]\n", o);
     fprintf(fp, "    -d bool      Debug mode [%d]\n", d);
     fprintf(fp, "    --bgzf                 every -o and --calls file compressed into BGZF blocks on the GPU; names are taken as given\n");
+    fprintf(fp, "    --bgzf-index           with --bgzf: a tabix index FILE.tbi of every --calls file and FILE.gzi + FILE.fai of every -o file, built with the file\n");
     fprintf(fp, "    --calls FILE           the inferred haplotype as variant calls (plain-text VCFv4.2; .gz only with --bgzf) against a reference walk of\n");
     fprintf(fp, "                           the graph; one per -o, in order, with the same {cov} / {panel} placeholder where -o takes one.\n");
     fprintf(fp, "                           The rule is this program's own (not vg deconstruct's): nothing is trimmed or left-aligned\n");
@@ -189,6 +191,7 @@ struct Options {
     std::vector<std::string> calls_files;
     std::string calls_ref, calls_contig;
     bool calls_support = false;                               // --calls-support: FORMAT/AK and RK in every --calls file (phi_calls_support)
+    bool bgzf_index = false;                                  // --bgzf-index: the indexes of those files, built beside them
     bool bgzf = false;                                        // --bgzf: every -o and --calls file compressed into BGZF blocks on the device
     bool panel() const { return have_keep || have_drop || !panel_sizes.empty() || panel_auto > 0; }
     int argc = 0;
@@ -1120,8 +1123,9 @@ struct Driver {
                 int64_t n_text = 0;
                 if (phi_format_fasta(hap_name, seq.get(), res.hap_len, &text, &n_text) != PHI_HOST_OK) return fail("[E::main] cannot format %s\n", hap_file.c_str());
                 seq.reset();
-                const int wrc = write_bgzf(hap_file, text, n_text);
+                int wrc = write_bgzf(hap_file, text, n_text, o.bgzf_index ? PHI_BGZF_INDEX_GZI : 0);
                 phi_host_free_text(text);
+                if (!wrc && o.bgzf_index) wrc = write_fai(hap_file + ".fai", hap_name, res.hap_len);
                 if (wrc) return 1;
             } else if (phi_write_fasta(hap_file.c_str(), hap_name, seq.get(), res.hap_len) != PHI_HOST_OK) return fail("[E::main] cannot write %s\n", hap_file.c_str());
         }
@@ -1158,22 +1162,54 @@ struct Driver {
         return fail("[E::main] --calls-ref %s: the panel does not keep this walk, and calls are made against no other; keep it with --panel-always %s (or --keep-samples)\n",
                     want.c_str(), sample_of(want.c_str()).c_str());
     }
-    // --bgzf: text[0, n) compressed into BGZF blocks on the command's device (phi_deflate_bgzf), written under the name as given
-    int write_bgzf(const std::string &file, const char *text, int64_t n)
+    static bool write_all(const std::string &file, const void *p, int64_t n)
     {
-        void *z = nullptr;
-        int64_t zn = 0;
-        phi_deflate_info di;
-        const int rc = phi_deflate_bgzf_alloc(devices[0], text, n, 0, &z, &zn, &di);
-        if (rc) return fail("[E::main] --bgzf %s: %s: %s\n", file.c_str(), phi_strerror(rc), di.detail);
         FILE *fp = fopen(file.c_str(), "wb");
-        bool ok = fp && fwrite(z, 1, (size_t)zn, fp) == (size_t)zn;
+        bool ok = fp && fwrite(p, 1, (size_t)n, fp) == (size_t)n;
         if (fp && fclose(fp) != 0) ok = false;
+        return ok;
+    }
+    // --bgzf: text[0, n) compressed into BGZF blocks on the command's device (phi_deflate_bgzf), written under the name as given.
+    // --bgzf-index (index_kind, 0 without): its index built with it (phi_deflate_bgzf_indexed) and written to FILE.gzi / FILE.tbi
+    int write_bgzf(const std::string &file, const char *text, int64_t n, int32_t index_kind)
+    {
+        void *z = nullptr, *x = nullptr;
+        int64_t zn = 0, xn = 0;
+        phi_deflate_info di;
+        phi_bgzf_index_info xi;
+        if (index_kind) {
+            const int rc = phi_deflate_bgzf_indexed(devices[0], text, n, 0, index_kind, &z, &zn, &x, &xn, &di, &xi);
+            if (rc) return fail("[E::main] --bgzf-index %s: %s: %s\n", file.c_str(), phi_strerror(rc), xi.detail);
+        } else {
+            const int rc = phi_deflate_bgzf_alloc(devices[0], text, n, 0, &z, &zn, &di);
+            if (rc) return fail("[E::main] --bgzf %s: %s: %s\n", file.c_str(), phi_strerror(rc), di.detail);
+        }
+        const std::string index_file = file + (index_kind == PHI_BGZF_INDEX_GZI ? ".gzi" : ".tbi");
+        const bool ok = write_all(file, z, zn), ok_index = !index_kind || write_all(index_file, x, xn);
         phi_deflate_free(z);
-        if (!ok) return fail("[E::main] cannot write %s\n", file.c_str());
+        phi_deflate_free(x);
+        if (!ok || !ok_index) return fail("[E::main] cannot write %s\n", ok ? index_file.c_str() : file.c_str());
         stamp("main");
         fprintf(stderr, "BGZF: %lld bytes written to %s, %lld bytes of text in %lld blocks (%lld stored); %.3f ms on device %d\n", (long long)zn, file.c_str(),
                 (long long)di.in_bytes, (long long)di.blocks, (long long)di.stored_blocks, di.device_ms, devices[0]);
+        if (index_kind) {
+            stamp("main");
+            fprintf(stderr, "BGZF index: %lld bytes written to %s, %lld records on %lld contigs, %lld chunks, %lld windows; %.3f ms on device %d\n", (long long)xn,
+                    index_file.c_str(), (long long)xi.records, (long long)xi.contigs, (long long)xi.chunks, (long long)xi.windows, xi.device_ms, devices[0]);
+        }
+        return 0;
+    }
+    // --bgzf-index: the .fai of a FASTA that phi_format_fasta made; with the .gzi a reader finds any base without inflating the rest
+    int write_fai(const std::string &file, const char *name, int64_t len)
+    {
+        char *line = nullptr;
+        int64_t n_line = 0;
+        if (phi_format_fasta_fai(name, len, &line, &n_line) != PHI_HOST_OK) return fail("[E::main] cannot format %s\n", file.c_str());
+        const bool ok = write_all(file, line, n_line);
+        phi_host_free_text(line);
+        if (!ok) return fail("[E::main] cannot write %s\n", file.c_str());
+        stamp("main");
+        fprintf(stderr, "BGZF index: %lld bytes written to %s, 1 records on 1 contigs, 0 chunks, 0 windows; 0.000 ms on device %d\n", (long long)n_line, file.c_str(), devices[0]);
         return 0;
     }
     // the path of the solve just reported as calls against the reference walk, written beside the FASTA
@@ -1212,7 +1248,7 @@ struct Driver {
                                                        &text, &n_text, &n_written, &n_dropped, werr, sizeof werr);
             if (frc != PHI_HOST_OK)
                 return fail("[E::main] %s\n", werr[0] ? werr : "cannot format the calls");
-            const int wrc = write_bgzf(file, text, n_text);
+            const int wrc = write_bgzf(file, text, n_text, o.bgzf_index ? PHI_BGZF_INDEX_TBI_VCF : 0);
             phi_host_free_text(text);
             if (wrc) return 1;
         } else if ((o.calls_support
@@ -1451,7 +1487,7 @@ int main(int argc, char *argv[])
                                            {"keep-samples", required_argument, 0, 311}, {"drop-samples", required_argument, 0, 312}, {"panels", required_argument, 0, 313},
                                            {"panel-seed", required_argument, 0, 314}, {"panel-always", required_argument, 0, 315},
                                            {"panel-auto", required_argument, 0, 316}, {"panel-blocks", required_argument, 0, 317},
-                                           {"calls", required_argument, 0, 318}, {"calls-ref", required_argument, 0, 319}, {"calls-contig", required_argument, 0, 320}, {"bgzf", no_argument, 0, 321}, {"calls-support", no_argument, 0, 322}, {0, 0, 0, 0}};
+                                           {"calls", required_argument, 0, 318}, {"calls-ref", required_argument, 0, 319}, {"calls-contig", required_argument, 0, 320}, {"bgzf", no_argument, 0, 321}, {"calls-support", no_argument, 0, 322}, {"bgzf-index", no_argument, 0, 323}, {0, 0, 0, 0}};
     int c;
     std::string gfa_arg, vcf_arg;
     // main.cpp:38 declares -h with an argument; a bare -h falls into the usage branch either way
@@ -1517,6 +1553,7 @@ int main(int argc, char *argv[])
         else if (c == 319) o.calls_ref = optarg;
         else if (c == 320) o.calls_contig = optarg;
         else if (c == 321) o.bgzf = true;
+        else if (c == 323) o.bgzf_index = true;
         else if (c == 322) o.calls_support = true;
         else if (c == 304) o.shard_min_bases = std::max<long long>(1, atoll(optarg));
         else if (c == 303) {                                   // --devices 0,1,2,...: shard the reads over these GPUs
@@ -1568,6 +1605,7 @@ int main(int argc, char *argv[])
             for (const std::string &h : o.hap_files)
                 if (h.find("{panel}") == std::string::npos) { fprintf(stderr, "[E::main] --panels with several sizes: -o must contain {panel} (got %s), e.g. -o 'out.{panel}.fa'\n", h.c_str()); return 1; }
     }
+    if (o.bgzf_index && !o.bgzf) { fprintf(stderr, "[E::main] --bgzf-index goes with --bgzf: the indexes are those of BGZF files\n"); return 1; }
     if (o.calls_files.empty()) {
         if (!o.calls_ref.empty() || !o.calls_contig.empty()) { fprintf(stderr, "[E::main] --calls-ref and --calls-contig go with --calls FILE\n"); return 1; }
         if (o.calls_support) { fprintf(stderr, "[E::main] --calls-support goes with --calls FILE: it adds the read support of every call to that file\n"); return 1; }

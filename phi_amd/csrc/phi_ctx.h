@@ -494,3 +494,10 @@ int phi_scan(phi_ctx *c, const int32_t *cnt, int64_t n, int32_t *off);   // off 
 int phi_scan(phi_ctx *c, const int32_t *cnt, int64_t n, int64_t *off);   // one workgroup up to 8192 items, three phases beyond
 // flags[n] (0/1) -> ascending list of flagged indices (int32) in out (waits for the stream)
 int phi_compact(phi_ctx *c, const uint8_t *flags, int64_t n, DevBuf &out, int64_t *n_out);
+// The same kernels for a run that has no context (bgzf_index.hip): launches on the caller's stream over the caller's scratch,
+// nothing waited for.  phi_scan_tiles: the one-workgroup scan, any n.  phi_compact_count: blk_cnt[phi_compact_blocks(n)] and
+// blk_off[.. + 1], whose last entry is the number of flagged items; phi_compact_write: their indices, ascending.
+int64_t phi_compact_blocks(int64_t n);
+void phi_scan_tiles(hipStream_t st, const int32_t *cnt, int64_t n, int64_t *off);
+void phi_compact_count(hipStream_t st, const uint8_t *flags, int64_t n, int32_t *blk_cnt, int64_t *blk_off);
+void phi_compact_write(hipStream_t st, const uint8_t *flags, int64_t n, const int64_t *blk_off, int32_t *out);

@@ -9,6 +9,8 @@
 // All of it is integer addition with a fixed place for every output: no result depends on the order of the additions.
 // The entry points run on the context's stream and own their scratch (d_scan_blk, d_scan_blk64, d_scan_blkoff, d_blk_cnt,
 // d_blk_off): calls on one context follow one another on that stream, from one host thread at a time.
+// A run without a context (bgzf_index.hip) launches the same kernels on its own stream over its own scratch: phi_scan_tiles,
+// phi_compact_count, phi_compact_write (phi_ctx.h).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include "phi_ctx.h"
@@ -165,6 +167,21 @@ int phi_compact(phi_ctx *c, const uint8_t *flags, int64_t n, DevBuf &out, int64_
                        out.as<int32_t>());
     *n_out = total;
     return PHI_OK;
+}
+
+// ------------------------------------------------------------------ the same for a run without a context (phi_ctx.h)
+int64_t phi_compact_blocks(int64_t n) { return (n + 256 * CMP_ITEMS - 1) / (256 * CMP_ITEMS); }
+void phi_scan_tiles(hipStream_t st, const int32_t *cnt, int64_t n, int64_t *off) { launch_scan_tiles(st, cnt, n, off); }
+void phi_compact_count(hipStream_t st, const uint8_t *flags, int64_t n, int32_t *blk_cnt, int64_t *blk_off)
+{
+    const int64_t nb = phi_compact_blocks(n);
+    if (nb > 0) hipLaunchKernelGGL(phi_flag_count_kernel, dim3((unsigned)nb), dim3(256), 0, st, flags, n, blk_cnt);
+    launch_scan_tiles(st, blk_cnt, nb, blk_off);
+}
+void phi_compact_write(hipStream_t st, const uint8_t *flags, int64_t n, const int64_t *blk_off, int32_t *out)
+{
+    const int64_t nb = phi_compact_blocks(n);
+    if (nb > 0) hipLaunchKernelGGL(phi_flag_write_kernel, dim3((unsigned)nb), dim3(256), 0, st, flags, n, blk_off, out);
 }
 
 // ------------------------------------------------------------------ the exported entry (include/phi_amd.h)

@@ -36,7 +36,7 @@ HOST_SYMBOLS = [
     "phi_vcf_parse_gt", "phi_vcf_build", "phi_vcf_n_units", "phi_vcf_unit_first", "phi_vcf_n_real_sites", "phi_vcf_site_backbone",
     "phi_vcf_site_allele0", "phi_vcf_n_kept_haps", "phi_vcf_choice",
     "phi_bam_header", "phi_panel_choose", "phi_write_calls_vcf",
-    "phi_format_fasta", "phi_format_calls_vcf", "phi_host_free_text",
+    "phi_format_fasta", "phi_format_fasta_fai", "phi_format_calls_vcf", "phi_host_free_text",
     "phi_write_calls_vcf_support", "phi_format_calls_vcf_support",
 ]
 PHI_HOST_NEED_MORE = -6
@@ -127,6 +127,7 @@ def host_lib():
     L.phi_write_calls_vcf.argtypes = [C.c_char_p, C.c_char_p, C.c_int64, C.c_char_p, C.c_int64, vp, vp, vp, vp, vp, vp,
                                       C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_char_p, C.c_int]
     L.phi_format_fasta.argtypes = [C.c_char_p, C.c_char_p, C.c_int64, C.POINTER(vp), C.POINTER(C.c_int64)]
+    L.phi_format_fasta_fai.argtypes = [C.c_char_p, C.c_int64, C.POINTER(vp), C.POINTER(C.c_int64)]
     L.phi_format_calls_vcf.argtypes = [C.c_char_p, C.c_int64, C.c_char_p, C.c_int64, vp, vp, vp, vp, vp, vp, C.POINTER(vp), C.POINTER(C.c_int64),
                                        C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_char_p, C.c_int]
     L.phi_write_calls_vcf_support.argtypes = [C.c_char_p, C.c_char_p, C.c_int64, C.c_char_p, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
