@@ -757,6 +757,40 @@ int phi_deflate_bgzf_indexed(int32_t device, const void *in, int64_t n, int32_t 
                              int64_t *out_size, void **index, int64_t *index_size, phi_deflate_info *info,
                              phi_bgzf_index_info *iinfo);
 
+/* The records of one region of a BGZF VCF, DESIGN.md 4.19: what `tabix FILE REGION` prints below the header.  gz[0, n_gz): the
+ * BGZF members a .tbi points at for the region, back to back (a multi-member gzip stream); range[2 * n_ranges]: byte ranges
+ * [p0, p1) of their inflated concatenation, ascending and disjoint, each beginning at a line's first byte and ending behind a
+ * line feed -- both as phi_region_plan of include/phi_host.h leaves them (phi_region_gz, phi_region_ranges), passed unchanged.
+ * *text[0, *n_text) (NUL behind it, freed with phi_vcf_region_free) holds, in file order, exactly the lines that start inside one
+ * of the ranges, do not begin with '#', whose CHROM equals name byte for byte, and whose interval overlaps [beg, end) (0-based,
+ * half-open: rec_beg < end and rec_end > beg); each line is followed by one line feed.  The interval is the .tbi writer's, stated
+ * above for PHI_BGZF_INDEX_TBI_VCF: rec_beg = max(POS - 1, 0), rec_end = rec_beg + len(REF) or the value of the first key END of
+ * INFO, and a rec_end <= rec_beg becomes rec_beg + 1.  (tests/tabix_ref.py: overlapping(), and what query() finds through the index.)
+ * A range's first byte begins a line even where no line feed stands before it: planned members need not be neighbours in the file.
+ * PHI_ERR_INVALID: inside a range, a line that is no meta line and has fewer than 8 fields (an empty line too), or whose POS or
+ * END is empty, not all digits or longer than 10 digits -- of any contig; the detail text names the line's offset in the inflated
+ * members; bytes that are no chain of BGZF members; ranges that are empty, out of order or beyond the text; members whose text is
+ * not as long as their ISIZE says.  A corrupt member is phi_inflate's error, with its detail.  PHI_ERR_UNSUPPORTED: a record of
+ * 2^31 bytes or more.  On any error *text is NULL and nothing stays allocated on the device.
+ * The members go through the device in batches of PHI_VCF_REGION_BATCH members (environment; else the default below, a starting
+ * value, not measured), so device memory stays bounded by a batch whatever the region.  A batch that ends inside a line starts
+ * the next at the member that holds that line's first byte (inflated a second time: reinflated_members), with twice the members
+ * when that is the batch's own first member; a line is looked at once, in the batch that holds its line feed, so nothing is kept
+ * twice and nothing is lost.  Needs no phi_ctx. */
+#define PHI_VCF_REGION_BATCH_DEFAULT 256   /* members per batch: 16 MiB of text at most; a starting value, not measured */
+typedef struct {
+    int64_t members, gz_bytes;         /* the members read and their compressed bytes */
+    int64_t text_bytes;                /* their inflated bytes */
+    int64_t lines_seen, lines_kept;    /* lines that start inside a range; lines written to *text */
+    int64_t batches;
+    int64_t reinflated_members;        /* members inflated again because a batch ended inside a line */
+    double  inflate_ms, filter_ms;     /* GPU milliseconds by HIP events: phi_inflate_info.device_ms summed; marks, lines, offsets, copy */
+    char    detail[192];
+} phi_vcf_region_info;
+int phi_vcf_region_filter(int32_t device, const void *gz, int64_t n_gz, const int64_t *range, int32_t n_ranges, const char *name,
+                          int64_t beg, int64_t end, char **text, int64_t *n_text, phi_vcf_region_info *info);
+void phi_vcf_region_free(char *text);
+
 /* A gzip GFA split on the device: the file (RFC 1952, any number of members) is inflated on the context's
  * device, the walk field of every W-line -- everything after its 6th tab, tags included, by the host reader's line rules
  * (include/phi_host.h) -- stays there, laid out as phi_walk_text_upload lays it out (phi_walk_text_resolve follows as after

@@ -137,6 +137,69 @@ const int32_t *phi_vcf_site_allele0(const phi_vcf *v);
 int32_t phi_vcf_n_kept_haps(const phi_vcf *v);
 const int32_t *phi_vcf_choice(const phi_vcf *v);
 
+/* A region of an indexed VCF and FASTA: what `tabix FILE REGION` and `samtools faidx FILE REGION` do before a
+ * record is looked at, so that a chromosome's VCF is neither inflated nor walked as a whole.  None of it needs a GPU.
+ *   phi_region_parse   NAME, NAME:BEG or NAME:BEG-END, 1-based and inclusive as tabix and samtools read them, commas allowed in
+ *                      the numbers; *end1 = -1 without END.  PHI_HOST_ERR_INVALID: empty, no name, BEG 0, END before BEG, a
+ *                      number of more than 18 digits.
+ *   phi_region_plan    the BGZF members of vcf_path that can hold a record of contig `name` overlapping the 0-based half-open
+ *                      [beg, end), through vcf_path + ".tbi" (VCF preset only; a .csi and any other preset:
+ *                      PHI_HOST_ERR_UNSUPPORTED; a gzip that is not BGZF too): reg2bins over 5 levels of 14 bits, chunks that end
+ *                      at or before the linear index's value for window beg >> 14 dropped (a window beyond the list: no records),
+ *                      the rest sorted and merged where they touch or overlap; a chunk (vbeg, vend) takes the members from
+ *                      vbeg >> 16 on, through the one at vend >> 16 when vend & 0xffff is not 0, followed by BSIZE with pread --
+ *                      nothing is inflated but the header: phi_region_header is every ## line and the #CHROM line.
+ *                      phi_region_gz[n_gz] is the members' compressed bytes back to back (load != 0), a valid multi-member gzip
+ *                      stream; phi_region_ranges[2 * n_ranges] every merged chunk as [p0, p1) of their inflated concatenation
+ *                      (member m's text begins at phi_region_member_text_off[m], from the ISIZEs); both go unchanged to
+ *                      phi_vcf_region_filter (phi_amd.h).  A contig the index does not name, an empty interval and a window
+ *                      beyond the list give no members (phi_region_in_index tells the first).  Reads what htslib writes: several
+ *                      chunks per bin, merged chunks, pseudo-bin 37450 (skipped), n_no_coor of any value or absent.
+ *   phi_fasta_slice    bases [beg, end) (end < 0 or beyond: the record's length) of record `name` of a FASTA through
+ *                      fasta_path + ".fai" (NAME LEN OFFSET LINEBASES LINEWIDTH, any number of records), upper-cased, line ends
+ *                      removed, NUL behind them; freed with phi_region_free_bases.  A plain file: one pread.  A BGZF file: the
+ *                      members that hold the range, found through fasta_path + ".gzi" (pairs as phi_amd.h describes them) and
+ *                      inflated on the host.  A missing .fai or .gzi is PHI_HOST_ERR_IO and named; gzip that is not BGZF is
+ *                      PHI_HOST_ERR_UNSUPPORTED.
+ *   phi_region_open    all of it for PHI --region: parse, the contig's length from the .fai (a missing END or one beyond it
+ *                      becomes that length; an empty interval and a name the .fai or the .tbi does not hold are refused), the
+ *                      plan, the reference slice (phi_region_ref).
+ *   phi_vcf_read_text  phi_vcf_read's rule pass over text in memory: ref[ref_len] is the reference from base `origin` of the
+ *                      contig on, a record's position is POS - 1 - origin, so that the rule "inside the reference" drops the
+ *                      records that reach over either edge (counted: phi_vcf_n_outside); contig: the one contig read (NULL: the
+ *                      first seen).  phi_vcf_read is this with the whole files, origin 0 and NULL.
+ *   phi_vcf_read_region   that over phi_region_header followed by the lines phi_vcf_region_filter kept. */
+typedef struct phi_region phi_region;
+int phi_region_parse(const char *region, char *name, int name_cap, int64_t *beg1, int64_t *end1, char *err, int err_cap);
+int phi_region_plan(const char *vcf_path, const char *name, int64_t beg, int64_t end, int32_t load, phi_region **out, char *err, int err_cap);
+int phi_region_open(const char *vcf_path, const char *fasta_path, const char *region, phi_region **out, char *err, int err_cap);
+void phi_region_free(phi_region *r);
+const char *phi_region_name(const phi_region *r);
+int64_t phi_region_beg(const phi_region *r);               /* 0-based, half-open */
+int64_t phi_region_end(const phi_region *r);
+int64_t phi_region_contig_len(const phi_region *r);        /* the .fai's (phi_region_open) */
+int32_t phi_region_in_index(const phi_region *r);
+int64_t phi_region_n_members(const phi_region *r);
+const int64_t *phi_region_member_at(const phi_region *r);        /* [n_members] file offsets */
+const int64_t *phi_region_member_text_off(const phi_region *r);  /* [n_members + 1] */
+int32_t phi_region_n_ranges(const phi_region *r);
+const int64_t *phi_region_ranges(const phi_region *r);
+const char *phi_region_gz(const phi_region *r);
+int64_t phi_region_n_gz(const phi_region *r);
+const char *phi_region_header(const phi_region *r);
+int64_t phi_region_n_header(const phi_region *r);
+const char *phi_region_ref(const phi_region *r);
+int64_t phi_region_n_ref(const phi_region *r);
+int64_t phi_region_fasta_members(const phi_region *r);     /* BGZF members inflated for the slice */
+int phi_fasta_slice(const char *fasta_path, const char *name, int64_t beg, int64_t end, char **bases, int64_t *n_bases, int64_t *contig_len,
+                    int64_t *members_read, char *err, int err_cap);
+void phi_region_free_bases(char *p);
+int phi_vcf_read_text(const char *text, int64_t n_text, const char *ref, int64_t ref_len, const char *ref_name, int64_t origin, const char *contig,
+                      phi_vcf **out, char *err, int err_cap);
+int phi_vcf_read_region(const phi_region *rg, const char *lines, int64_t n_lines, phi_vcf **out, char *err, int err_cap);
+int64_t phi_vcf_origin(const phi_vcf *v);                  /* where phi_vcf_ref_seq begins on the contig */
+int64_t phi_vcf_n_outside(const phi_vcf *v);               /* records with GT that reach beyond the reference (a region's edges) */
+
 /* FASTA/FASTQ reader with kseq's record rules (multi-line FASTA, '+' quality blocks). */
 int phi_reads_read(const char *path, phi_reads **out, char *err, int err_cap);
 void phi_reads_free(phi_reads *r);

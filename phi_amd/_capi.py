@@ -41,7 +41,7 @@ SYMBOLS = [
     "phi_reads_bam_begin", "phi_add_reads_bam", "phi_add_reads_bam_parked", "phi_reads_bam_end", "phi_reads_bam_last_batch",
     "phi_calls_path", "phi_calls_walk", "phi_calls_stats", "phi_calls_support", "phi_calls_support_stats",
     "phi_deflate_bgzf_bound", "phi_deflate_bgzf", "phi_deflate_bgzf_alloc", "phi_deflate_free",
-    "phi_deflate_bgzf_indexed",
+    "phi_deflate_bgzf_indexed", "phi_vcf_region_filter", "phi_vcf_region_free",
 ]
 PHI_PANEL_RETAIN = 1
 PHI_PANEL_KEEP_READS = 2
@@ -151,6 +151,11 @@ class PhiInflateInfo(C.Structure):
 class PhiDeflateInfo(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("in_bytes", "out_bytes", "blocks", "stored_blocks", "matches", "match_bytes")] + [
         ("device_ms", C.c_double), ("detail", C.c_char * 192)]
+
+
+class PhiVcfRegionInfo(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("members", "gz_bytes", "text_bytes", "lines_seen", "lines_kept", "batches", "reinflated_members")] + [
+        ("inflate_ms", C.c_double), ("filter_ms", C.c_double), ("detail", C.c_char * 192)]
 
 
 class PhiBgzfIndexInfo(C.Structure):
@@ -296,6 +301,9 @@ def load():
                                            C.POINTER(PhiDeflateInfo), C.POINTER(PhiBgzfIndexInfo)]
     L.phi_deflate_free.argtypes = [vp]
     L.phi_deflate_free.restype = None
+    L.phi_vcf_region_filter.argtypes = [i32, vp, i64, vp, i32, C.c_char_p, i64, i64, C.POINTER(vp), C.POINTER(i64), C.POINTER(PhiVcfRegionInfo)]
+    L.phi_vcf_region_free.argtypes = [vp]
+    L.phi_vcf_region_free.restype = None
     L.phi_text_park_gzip_begin.argtypes = [vp, i64]
     L.phi_text_park_gzip_add.argtypes = [vp, vp, i64]
     L.phi_text_park_gzip_end.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(PhiInflateInfo)]

@@ -43,7 +43,7 @@ def ph_names(calls, path_hap, hap_names):
 SUPPORT_ARRAYS = ("alt_hit", "alt_n", "ref_hit", "ref_n")
 
 
-def write_vcf(path, calls, contig, contig_len, sample, ph=None, bgzf=False, device=0, support=None, index=False):
+def write_vcf(path, calls, contig, contig_len, sample, ph=None, bgzf=False, device=0, support=None, index=False, origin=0):
     """The calls as plain-text VCFv4.2 (phi_write_calls_vcf of include/phi_host.h): one haploid sample with genotype 1, POS
     1-based, PH=<ph[k]> in INFO where ph (a list of names, one per call) is given.  Calls whose REF and ALT are the same bytes
     are dropped.  Returns (records written, calls dropped).  A name ending in .gz is refused (HostError: this writer has no
@@ -51,13 +51,15 @@ def write_vcf(path, calls, contig, contig_len, sample, ph=None, bgzf=False, devi
     `device` (deflate_bgzf) and written under the name as given.  support: the dict of Context.calls_support() for these
     calls; the records then carry FORMAT/AK and RK (phi_write_calls_vcf_support), everything else is the same bytes.
     index (needs bgzf): a tabix index of the file, built on the device beside it (deflate_bgzf_indexed), as path + ".tbi";
-    the file's bytes are the same with and without."""
+    the file's bytes are the same with and without.
+    origin: added to every POS -- calls against the reference of set_graph_vcf(region=) are written in the contig's
+    coordinates with origin=v.origin, contig=v.region[0] and contig_len=v.contig_len; an index is that of the shifted positions."""
     from .ilp_index import HostError, host_lib
     L = host_lib()
     if index and not bgzf:
         raise ValueError("index=True needs bgzf=True: the index is one of a BGZF file")
     n = int(len(calls["pos"]))
-    pos = np.ascontiguousarray(calls["pos"], np.int64)
+    pos = np.ascontiguousarray(calls["pos"], np.int64) + int(origin)
     ro = np.ascontiguousarray(calls["ref_off"], np.int64)
     ao = np.ascontiguousarray(calls["alt_off"], np.int64)
     rb, ab = bytes(calls["ref_bytes"]), bytes(calls["alt_bytes"])

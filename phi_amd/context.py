@@ -177,7 +177,8 @@ class Context:
         context handed the same reads directly."""
         self._chk(self._L.phi_reads_collect_score(self._h))
 
-    def set_graph_vcf(self, vcf_path, fasta_path, max_len=30, keep_samples=None, auto_panel=None, reads=None, always=None, n_blocks=0, text=False):
+    def set_graph_vcf(self, vcf_path, fasta_path, max_len=30, keep_samples=None, auto_panel=None, reads=None, always=None, n_blocks=0, text=False,
+                      region=None):
         """ "Set graph" from a phased VCF + reference FASTA (the graph of phi_amd.vcf2gfa, no GFA in between): vcf_graph(), then
         phi_set_graph takes the walk entries from where the device left them.  Returns the host graph description (VcfGraph:
         hap_id2name, the arrays, walk_off, n_other_contig / n_ref_mismatch / warnings()) with .stats = vcf_stats() plus host
@@ -191,13 +192,16 @@ class Context:
         haplotype's walk is written, up to 65 535, the reads are scored against the index of them all, and the N that lead
         the blocks of the graph are kept; always=[haplotype names] are kept whatever the reads say).  The reads are scored
         against the panel when the call returns: solve() follows.  v.auto holds what the choice did, the rest as with
-        keep_samples.  A VCF of at most N haplotypes takes the ordinary route and the reads are added."""
+        keep_samples.  A VCF of at most N haplotypes takes the ordinary route and the reads are added.
+        region="NAME", "NAME:BEG" or "NAME:BEG-END" (1-based, inclusive, as tabix and samtools read it): the graph of that
+        part of one contig of an indexed BGZF VCF (.tbi) and an indexed FASTA (.fai, .gzi), see vcf_graph; everything else as
+        without it, in the region's coordinates (v.region = (name, b, e), 0-based half-open)."""
         import time
         if auto_panel is not None:
             if keep_samples is not None or reads is None:
                 raise ValueError("auto_panel=N goes with reads=... and without keep_samples")
             from . import panel as _panel
-            v = self.vcf_graph(vcf_path, fasta_path, max_len, wide=True)
+            v = self.vcf_graph(vcf_path, fasta_path, max_len, wide=True, region=region)
             t4 = time.perf_counter()
             if v.num_walks <= int(auto_panel):
                 self.set_graph(v.seq_concat, v.seq_off, v.adj_off, v.adj, v.walk_off, None, v.top_order_map)
@@ -220,7 +224,7 @@ class Context:
                 v.walk_off = v.auto["walk_off"]
             v.stats["set_graph_s"] = time.perf_counter() - t4
             return v
-        v = self.vcf_graph(vcf_path, fasta_path, max_len, keep_samples=keep_samples)
+        v = self.vcf_graph(vcf_path, fasta_path, max_len, keep_samples=keep_samples, region=region)
         t4 = time.perf_counter()
         if keep_samples is None:
             self.set_graph(v.seq_concat, v.seq_off, v.adj_off, v.adj, v.walk_off, None, v.top_order_map)
@@ -229,15 +233,29 @@ class Context:
         v.stats["set_graph_s"] = time.perf_counter() - t4
         return v
 
-    def vcf_graph(self, vcf_path, fasta_path, max_len=30, keep_samples=None, wide=False):
+    def vcf_graph(self, vcf_path, fasta_path, max_len=30, keep_samples=None, wide=False, region=None):
         """The VCF route up to "set graph": the host reads the fixed columns and builds the per-vertex arrays
         (ilp_index.VcfGraph), the device parses the genotype text (phi_vcf_genotypes; records it flags go through the host's
         scalar parser) and writes the walk entries (phi_vcf_walks): walk_entries() returns them, set_graph(..., walk_vtx=None)
-        takes them.  wide=True: up to 65 535 haplotypes (phi_vcf_walks_wide), for scout_graph."""
+        takes them.  wide=True: up to 65 535 haplotypes (phi_vcf_walks_wide), for scout_graph.
+        region: the host plans which BGZF members of the VCF the .tbi points at and slices the FASTA through .fai / .gzi
+        (ilp_index.RegionPlan), the device inflates those members and keeps exactly the region's records
+        (phi_vcf_region_filter), and the host's rule pass runs over header + kept lines with positions counted from the
+        region's first base; v.stats then also holds phi_vcf_region_info and plan_s / filter_s."""
         import time
         from .ilp_index import VcfGraph
         t0 = time.perf_counter()
-        v = VcfGraph(vcf_path, fasta_path)
+        extra = {}
+        if region is None:
+            v = VcfGraph(vcf_path, fasta_path)
+        else:
+            from .ilp_index import RegionPlan
+            with RegionPlan.open(vcf_path, fasta_path, region) as plan:
+                tp = time.perf_counter()
+                lines, rinfo = vcf_region_filter(plan.gz, plan.ranges, plan.name, plan.beg, plan.end, device=self.device)
+                tf = time.perf_counter()
+                v = VcfGraph(None, None, region=plan, lines=lines)
+            extra = dict(rinfo, plan_s=tp - t0, filter_s=tf - tp, fasta_members=plan.fasta_members)
         t1 = time.perf_counter()
         n_s, n_r = len(v.samples), v.n_records
         gt = np.zeros((n_r, n_s, 2), np.uint16)
@@ -264,7 +282,7 @@ class Context:
                                         _ptr(choice), v.num_walks, _ptr(walk_off)))
         t4 = time.perf_counter()
         v.walk_off = walk_off
-        v.stats = dict(self.vcf_stats(), read_s=t1 - t0, genotypes_s=t2 - t1, build_s=t3 - t2, walks_s=t4 - t3, set_graph_s=0.0)
+        v.stats = dict(self.vcf_stats(), read_s=t1 - t0, genotypes_s=t2 - t1, build_s=t3 - t2, walks_s=t4 - t3, set_graph_s=0.0, **extra)
         return v
 
     def vcf_stats(self):
@@ -938,6 +956,26 @@ def deflate_bgzf_indexed(data, kind, device=0):
     d = {n: getattr(iinfo, n) for n, _ in _capi.PhiBgzfIndexInfo._fields_ if n != "detail"}
     d["deflate"] = {n: getattr(info, n) for n, _ in _capi.PhiDeflateInfo._fields_ if n != "detail"}
     return out, index, d
+
+
+def vcf_region_filter(gz, ranges, name, beg, end, device=0):
+    """The record lines of contig `name` that overlap the 0-based half-open [beg, end), out of the BGZF members gz (bytes) and
+    the byte ranges of their inflated text (int64 pairs) that ilp_index.RegionPlan holds: include/phi_amd.h
+    phi_vcf_region_filter, what `tabix FILE REGION` prints below the header.  Returns (text, info)."""
+    L = _capi.load()
+    buf = np.frombuffer(gz, np.uint8) if not isinstance(gz, np.ndarray) else np.ascontiguousarray(gz, np.uint8)
+    rng = np.ascontiguousarray(ranges, np.int64).ravel()
+    p, size, info = C.c_void_p(), C.c_int64(), _capi.PhiVcfRegionInfo()
+    rc = L.phi_vcf_region_filter(device, _ptr(buf) if len(buf) else None, len(buf), _ptr(rng) if len(rng) else None, len(rng) // 2,
+                                 name if isinstance(name, bytes) else str(name).encode(), beg, end, C.byref(p), C.byref(size), C.byref(info))
+    if rc:
+        assert not p.value
+        raise PhiError(rc, info.detail.decode())
+    try:
+        out = C.string_at(p, size.value) if size.value else b""
+    finally:
+        L.phi_vcf_region_free(p)
+    return out, {n: getattr(info, n) for n, _ in _capi.PhiVcfRegionInfo._fields_ if n != "detail"}
 
 
 def gzip_header(data, pos=0):

@@ -30,40 +30,15 @@
 #include "phi_ctx.h"
 #include "phi_wave.h"
 #include "dev_run.h"
+#include "vcf_lines_dev.h"
 #include "bgzf_index_host.h"
 
-#define BIX_T 256                       // threads per workgroup
-#define BIX_LANE 16                     // bytes per lane: one 16-byte load
-#define BIX_WG (BIX_T * BIX_LANE)       // bytes per workgroup
 #define BIX_MAX_LINES 2147483646ll      // lines are numbered in 32 bits (the compaction's indices)
 static_assert(PHI_BGZF_BLOCK == bgzfx::BLOCK, "one block size");
 
 namespace {
 
 enum { BIX_EMPTY = 1, BIX_FIELDS, BIX_POS, BIX_END, BIX_ORDER, BIX_RANGE, BIX_NAME };
-
-// the position lists of phase 1 (device pointers) and their sizes
-struct BixLists {
-    const uint8_t *text;
-    int64_t n;
-    const int64_t *nl_pos, *nl_tab, *nl_end;            // per newline: where, and the tabs / END places before it
-    const int64_t *tab_pos, *end_pos;
-    int64_t n_nl, n_tab, n_end;
-};
-struct BixLine { int64_t s, e, tab_lo, tab_hi, end_lo, end_hi; };       // text[s, e) without its newline; its tabs, its END places
-
-__device__ __forceinline__ BixLine bix_line(const BixLists &L, int64_t i)
-{
-    BixLine l;
-    l.s = i ? L.nl_pos[i - 1] + 1 : 0;
-    l.tab_lo = i ? L.nl_tab[i - 1] : 0;
-    l.end_lo = i ? L.nl_end[i - 1] : 0;
-    const bool closed = i < L.n_nl;                     // (the last line may have no newline)
-    l.e = closed ? L.nl_pos[i] : L.n;
-    l.tab_hi = closed ? L.nl_tab[i] : L.n_tab;
-    l.end_hi = closed ? L.nl_end[i] : L.n_end;
-    return l;
-}
 
 // the bytes of x that equal the byte repeated in pat, one bit each
 __device__ __forceinline__ uint32_t bix_eq4(uint32_t x, uint32_t pat)
@@ -159,20 +134,6 @@ __global__ void __launch_bounds__(256) phi_bix_lines_kernel(BixLists L, int64_t 
     is_rec[i] = L.text[l.s] != '#';
 }
 
-// text[a, b) as a number: 1 to 10 digits and nothing else, or -1
-__device__ __forceinline__ int64_t bix_number(const uint8_t *__restrict__ text, int64_t a, int64_t b)
-{
-    const int64_t len = b - a;
-    if (len < 1 || len > 10) return -1;
-    int64_t v = 0;
-    for (int64_t k = 0; k < len; k++) {
-        const int c = text[a + k];
-        if (c < '0' || c > '9') return -1;
-        v = v * 10 + (c - '0');
-    }
-    return v;
-}
-
 __device__ __forceinline__ uint64_t bix_voff(const int64_t *__restrict__ off, int64_t p)
 {
     return ((uint64_t)off[p / PHI_BGZF_BLOCK] << 16) | (uint64_t)(p % PHI_BGZF_BLOCK);
@@ -200,33 +161,13 @@ __global__ void __launch_bounds__(256) phi_bix_records_kernel(BixLists L, const 
     const int64_t ntab = l.tab_hi - l.tab_lo;
     if (ntab < 7) bix_raise(err, li, BIX_FIELDS);
     else {
-        int64_t t[7];
-#pragma unroll
-        for (int k = 0; k < 7; k++) t[k] = L.tab_pos[l.tab_lo + k];
-        const int64_t info_end = ntab > 7 ? L.tab_pos[l.tab_lo + 7] : l.e;
-        const int64_t pos = bix_number(text, t[0] + 1, t[1]);
-        bool ok = true;
-        if (pos < 0) { bix_raise(err, li, BIX_POS); ok = false; }
-        else {
-            beg = pos > 0 ? pos - 1 : 0;
-            end = beg + (t[3] - t[2] - 1);
-            int64_t lo = l.end_lo, hi = l.end_hi;       // the first END place at or behind INFO's first byte
-            while (lo < hi) {
-                const int64_t mid = lo + ((hi - lo) >> 1);
-                if (L.end_pos[mid] < t[6] + 1) lo = mid + 1; else hi = mid;
-            }
-            if (lo < l.end_hi && L.end_pos[lo] < info_end) {
-                const int64_t a = L.end_pos[lo] + 4;
-                int64_t b = a;
-                while (b < info_end && b - a <= 10 && text[b] != ';') b++;
-                const int64_t v = bix_number(text, a, b);
-                if (v < 0) { bix_raise(err, li, BIX_END); ok = false; }
-                else end = v;
-            }
-            if (end <= beg) end = beg + 1;
-            if (ok && end > bgzfx::MAX_END) { bix_raise(err, li, BIX_RANGE); ok = false; }
-        }
-        const int64_t len = t[0] - l.s;
+        int64_t pos = -1;
+        const int bad = bix_interval(L, l, &beg, &end, &pos);
+        bool ok = !bad;
+        if (bad) bix_raise(err, li, bad == 1 ? BIX_POS : BIX_END);
+        else if (end > bgzfx::MAX_END) { bix_raise(err, li, BIX_RANGE); ok = false; }
+        const int64_t t0 = L.tab_pos[l.tab_lo];
+        const int64_t len = t0 - l.s;
         if (len > bgzfx::MAX_NAME) { bix_raise(err, li, BIX_NAME); ok = false; }
         else if (r > 0) {
             const int64_t pi = rec_line[r - 1];
@@ -352,25 +293,11 @@ int tbi_run(Dev &dev, const uint8_t *text, const uint8_t *d_text, int64_t n, con
     if (n == 0) { *bytes = bgzfx::tbi_bytes(contigs, &counts); return PHI_OK; }
 
     // ---- 1. marks
-    const int64_t nblk = (n + BIX_WG - 1) / BIX_WG;
-    DALLOC(d_cnt, int32_t, (size_t)nblk * 3 * 4);
-    DALLOC(d_cnt_off, int64_t, (size_t)(nblk + 1) * 3 * 8);
-    BIX_BEGIN();
-    hipLaunchKernelGGL(phi_bix_mark_count_kernel, dim3((unsigned)nblk), dim3(BIX_T), 0, st, d_text, n, nblk, d_cnt);
-    for (int k = 0; k < 3; k++) phi_scan_tiles(st, d_cnt + k * nblk, nblk, d_cnt_off + k * (nblk + 1));
-    BIX_END_WAIT();
-    int64_t total[3];
-    for (int k = 0; k < 3; k++) DCHK(hipMemcpy(&total[k], d_cnt_off + k * (nblk + 1) + nblk, 8, hipMemcpyDeviceToHost));
-    const int64_t n_nl = total[0], n_tab = total[1], n_end = total[2];
+    BixLists L{};
+    if (const int mrc = bix_mark_run(dev, d_text, n, &L, info, &info->device_ms, "phi_deflate_bgzf_indexed")) return mrc;
+    const int64_t n_nl = L.n_nl;
     const int64_t n_lines = n_nl + (text[n - 1] != '\n');
-    if (n_nl < 0 || n_nl > n || n_tab < 0 || n_tab > n || n_end < 0 || n_end > n)
-        return fail(info, PHI_ERR_DEVICE, "phi_deflate_bgzf_indexed: %lld newlines, %lld tabs in %lld bytes (internal error)", (long long)n_nl, (long long)n_tab, (long long)n);
     if (n_lines > BIX_MAX_LINES) return fail(info, PHI_ERR_UNSUPPORTED, "phi_deflate_bgzf_indexed: %lld lines, more than 2^31 - 2", (long long)n_lines);
-    DALLOC(d_nl_pos, int64_t, (size_t)n_nl * 8);
-    DALLOC(d_nl_tab, int64_t, (size_t)n_nl * 8);
-    DALLOC(d_nl_end, int64_t, (size_t)n_nl * 8);
-    DALLOC(d_tab_pos, int64_t, (size_t)n_tab * 8);
-    DALLOC(d_end_pos, int64_t, (size_t)n_end * 8);
     DALLOC(d_is_rec, uint8_t, (size_t)n_lines);
     DALLOC(d_err, unsigned long long, 8);
     const int64_t nscr = phi_compact_blocks(n_lines);
@@ -379,11 +306,9 @@ int tbi_run(Dev &dev, const uint8_t *text, const uint8_t *d_text, int64_t n, con
     DALLOC(d_off, int64_t, off.size() * 8);
     DCHK(hipMemcpyAsync(d_off, off.data(), off.size() * 8, hipMemcpyHostToDevice, st));
     DCHK(hipMemsetAsync(d_err, 0xff, 8, st));
-    const BixLists L{d_text, n, d_nl_pos, d_nl_tab, d_nl_end, d_tab_pos, d_end_pos, n_nl, n_tab, n_end};
 
     // ---- 2. lines
     BIX_BEGIN();
-    hipLaunchKernelGGL(phi_bix_mark_write_kernel, dim3((unsigned)nblk), dim3(BIX_T), 0, st, d_text, n, nblk, d_cnt_off, d_nl_pos, d_nl_tab, d_nl_end, d_tab_pos, d_end_pos);
     hipLaunchKernelGGL(phi_bix_lines_kernel, dim3(grid(n_lines)), dim3(256), 0, st, L, n_lines, d_is_rec, d_err);
     BIX_END_WAIT();
     BIX_COMPACT(d_is_rec, n_lines, d_rec_line, n_rec);
@@ -537,6 +462,21 @@ int indexed_run(int32_t device, const uint8_t *in, int64_t n, int32_t flags, int
 }
 
 }  // namespace
+
+// the marks for the units that read VCF text on the device (vcf_lines_dev.h: bix_mark_run)
+void phi_bix_mark_count(hipStream_t st, const uint8_t *d_text, int64_t n, int32_t *cnt, int64_t *off)
+{
+    const int64_t nblk = (n + BIX_WG - 1) / BIX_WG;
+    hipLaunchKernelGGL(phi_bix_mark_count_kernel, dim3((unsigned)nblk), dim3(BIX_T), 0, st, d_text, n, nblk, cnt);
+    for (int k = 0; k < 3; k++) phi_scan_tiles(st, cnt + k * nblk, nblk, off + k * (nblk + 1));
+}
+
+void phi_bix_mark_write(hipStream_t st, const uint8_t *d_text, int64_t n, const int64_t *off, int64_t *nl_pos, int64_t *nl_tab, int64_t *nl_end,
+                        int64_t *tab_pos, int64_t *end_pos)
+{
+    const int64_t nblk = (n + BIX_WG - 1) / BIX_WG;
+    hipLaunchKernelGGL(phi_bix_mark_write_kernel, dim3((unsigned)nblk), dim3(BIX_T), 0, st, d_text, n, nblk, off, nl_pos, nl_tab, nl_end, tab_pos, end_pos);
+}
 
 extern "C" int phi_deflate_bgzf_indexed(int32_t device, const void *in, int64_t n, int32_t flags, int32_t index_kind, void **out, int64_t *out_size,
                                         void **index, int64_t *index_size, phi_deflate_info *dinfo, phi_bgzf_index_info *info)

@@ -154,6 +154,9 @@ static void usage(FILE *fp, int k, int w, int R, int q, int m, float T, int t, c
     fprintf(fp, "                           under a panel it must be among the kept walks (--panel-always keeps it)\n");
     fprintf(fp, "    --calls-contig NAME    the contig of the records [--vcf: the VCF's contig; -g: the reference walk's name].  With -g POS\n");
     fprintf(fp, "                           counts the walk's own bases from 1: a W-line's start offset is not kept by the reader\n");
+    fprintf(fp, "    --region R             with --vcf and --ref: the graph of one region, R = NAME, NAME:BEG or NAME:BEG-END (1-based, inclusive, commas\n");
+    fprintf(fp, "                           allowed, as tabix and samtools read it).  The VCF must be BGZF with its .tbi, the FASTA indexed (.fai; BGZF: .gzi);\n");
+    fprintf(fp, "                           only the BGZF members the index points at are read.  --calls records stay in the contig's coordinates\n");
 }
 
 struct Options {
@@ -168,6 +171,7 @@ struct Options {
     std::vector<int> reads_kinds;                             // per -r: its ReadsKind, decided once in main (from a regular file's first bytes)
     std::string vcf_ref;                                      // --vcf FILE --ref FILE: the graph from a phased VCF (gfa_file holds the VCF's name then)
     bool from_vcf = false;
+    std::string region;                                       // --region R: one region of an indexed VCF and FASTA
     int vcf_max_len = 30;                                     // its segments' length (--chop N; gfa2gbwt -m 30, vcf2gfa.py:53)
     std::vector<std::string> reads_files, hap_files;          // one entry per job: -r a -o a.fa -r b -o b.fa ...
     // --coverage C0,C1,.. --genome-size N [--seed S]: every read set is inferred at a ladder of coverages (data/preprocess.py:83-107,
@@ -564,6 +568,7 @@ struct Driver {
     ReadsFeed feed;
     phi_graph *g = nullptr;
     phi_vcf *vcf = nullptr;                                   // --vcf: the reader's handle (the unit tables build_index writes the walks from)
+    int64_t region_contig_len = 0;                            // --region: the contig's length by its .fai (the reference held is the region's)
     char err[512] = "";
     std::string reads_file, hap_file;                         // the job at hand, and the name in its FASTA
     int reads_kind_now = 0;                                   // the job's ReadsKind (Options::reads_kinds)
@@ -678,11 +683,42 @@ struct Driver {
     int load_graph_vcf()
     {
         int r;
-        {
+        if (!o.region.empty()) {
+            // --region: the host plans which BGZF members the .tbi points at and slices the FASTA; the device inflates those
+            // members and keeps exactly the region's records; the rule pass then runs over header + kept lines
+            phi_region *rg = nullptr;
+            {
+                Stage st("VCF region plan (host: .tbi, .fai, members)");
+                r = phi_region_open(o.gfa_file.c_str(), o.vcf_ref.c_str(), o.region.c_str(), &rg, err, sizeof err);
+            }
+            if (r != PHI_HOST_OK) return fail("[E::region] %s\n", err);
+            char *lines = nullptr;
+            int64_t n_lines = 0;
+            phi_vcf_region_info ri;
+            int frc;
+            {
+                Stage st("VCF region filter (device: inflate + records)");
+                frc = phi_vcf_region_filter(o.device, phi_region_gz(rg), phi_region_n_gz(rg), phi_region_ranges(rg), phi_region_n_ranges(rg), phi_region_name(rg),
+                                            phi_region_beg(rg), phi_region_end(rg), &lines, &n_lines, &ri);
+            }
+            if (frc) { phi_region_free(rg); return fail("[E::region] %s\n", ri.detail); }
+            fprintf(stderr, "Region %s:%lld-%lld of %lld bases: %lld BGZF members (%lld bytes, %lld inflated), %lld lines seen, %lld kept, %lld batch(es); GPU inflate %.3f ms, filter %.3f ms\n",
+                    phi_region_name(rg), (long long)phi_region_beg(rg) + 1, (long long)phi_region_end(rg), (long long)phi_region_contig_len(rg), (long long)ri.members,
+                    (long long)ri.gz_bytes, (long long)ri.text_bytes, (long long)ri.lines_seen, (long long)ri.lines_kept, (long long)ri.batches, ri.inflate_ms, ri.filter_ms);
+            region_contig_len = phi_region_contig_len(rg);
+            {
+                Stage st("VCF + FASTA read (region)");
+                r = phi_vcf_read_region(rg, lines, n_lines, &vcf, err, sizeof err);
+            }
+            phi_vcf_region_free(lines);
+            phi_region_free(rg);
+        } else {
             Stage st("VCF + FASTA read");
             r = phi_vcf_read(o.gfa_file.c_str(), o.vcf_ref.c_str(), &vcf, err, sizeof err);
         }
         if (r != PHI_HOST_OK) return fail("[E::vcf2gfa] %s\n", err);
+        if (const long long n = phi_vcf_n_outside(vcf); n && !o.region.empty())
+            fprintf(stderr, "[W::region] %lld record(s) skipped: they reach over an edge of the region %s\n", n, o.region.c_str());
         if (const long long n = phi_vcf_n_other_contig(vcf))
             fprintf(stderr, "[W::vcf2gfa] %lld record(s) of other contigs than %s skipped (vcf2gfa handles one contig)\n", n, phi_vcf_contig(vcf));
         if (const long long n = phi_vcf_n_ref_mismatch(vcf))
@@ -1233,7 +1269,13 @@ struct Driver {
         const char *ref_name = walk_name(r);
         const bool vcf_ref = o.from_vcf && !strcmp(ref_name, "REF.0");
         const std::string contig = !o.calls_contig.empty() ? o.calls_contig : vcf_ref ? phi_vcf_contig(vcf) : ref_name;
-        const int64_t contig_len = vcf_ref ? phi_vcf_ref_len(vcf) : ci.ref_bases;
+        const int64_t contig_len = vcf_ref ? (o.region.empty() ? phi_vcf_ref_len(vcf) : region_contig_len) : ci.ref_bases;
+        std::vector<int64_t> shifted;                         // --region: the records in the contig's coordinates, POS plus the region's origin
+        if (vcf_ref && !o.region.empty() && phi_vcf_origin(vcf) != 0) {
+            shifted.assign(cl.pos, cl.pos + cl.n_calls);
+            for (int64_t &p : shifted) p += phi_vcf_origin(vcf);
+            cl.pos = shifted.data();
+        }
         std::vector<const char *> ph((size_t)cl.n_calls);
         for (int64_t k = 0; k < cl.n_calls; k++) ph[(size_t)k] = walk_name(res.path_hap[cl.anchor[k] + 1]);
         int64_t n_written = 0, n_dropped = 0;
@@ -1487,7 +1529,7 @@ int main(int argc, char *argv[])
                                            {"keep-samples", required_argument, 0, 311}, {"drop-samples", required_argument, 0, 312}, {"panels", required_argument, 0, 313},
                                            {"panel-seed", required_argument, 0, 314}, {"panel-always", required_argument, 0, 315},
                                            {"panel-auto", required_argument, 0, 316}, {"panel-blocks", required_argument, 0, 317},
-                                           {"calls", required_argument, 0, 318}, {"calls-ref", required_argument, 0, 319}, {"calls-contig", required_argument, 0, 320}, {"bgzf", no_argument, 0, 321}, {"calls-support", no_argument, 0, 322}, {"bgzf-index", no_argument, 0, 323}, {0, 0, 0, 0}};
+                                           {"calls", required_argument, 0, 318}, {"calls-ref", required_argument, 0, 319}, {"calls-contig", required_argument, 0, 320}, {"bgzf", no_argument, 0, 321}, {"calls-support", no_argument, 0, 322}, {"bgzf-index", no_argument, 0, 323}, {"region", required_argument, 0, 324}, {0, 0, 0, 0}};
     int c;
     std::string gfa_arg, vcf_arg;
     // main.cpp:38 declares -h with an argument; a bare -h falls into the usage branch either way
@@ -1499,6 +1541,7 @@ int main(int argc, char *argv[])
         else if (c == 'g') { gfa_arg = optarg; }
         else if (c == 306) { vcf_arg = optarg; }
         else if (c == 307) o.vcf_ref = optarg;
+        else if (c == 324) o.region = optarg;
         else if (c == 'R') o.recombination = atoi(optarg);
         else if (c == 'q') o.is_qclp = atoi(optarg);
         else if (c == 'N') o.is_naive = atoi(optarg);
@@ -1570,6 +1613,7 @@ int main(int argc, char *argv[])
     }
     if (!vcf_arg.empty() && !gfa_arg.empty()) { fprintf(stderr, "[E::main] --vcf and -g exclude each other: the graph comes from a GFA or from a VCF + FASTA\n"); return 1; }
     if (vcf_arg.empty() != o.vcf_ref.empty()) { fprintf(stderr, "[E::main] --vcf FILE and --ref FILE go together (a phased VCF and its reference FASTA)\n"); return 1; }
+    if (!o.region.empty() && vcf_arg.empty()) { fprintf(stderr, "[E::main] --region R goes with --vcf FILE --ref FILE: a region of an indexed VCF and FASTA (a GFA has no index to read it through)\n"); return 1; }
     o.gfa_file = vcf_arg.empty() ? gfa_arg : vcf_arg;
     if (!vcf_arg.empty()) { o.from_vcf = true; o.vcf_max_len = o.chop ? o.chop : 30; o.chop = 0; }      // (--chop N: the segments are built at that length)
     if (argc < 2 || o.gfa_file.empty() || o.reads_file.empty() || o.hap_file.empty() || help) {

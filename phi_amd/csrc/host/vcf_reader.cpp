@@ -105,6 +105,7 @@ struct phi_vcf {
     std::vector<char> ref;                             // the FASTA record, upper-cased
     std::vector<std::string> samples;
     int64_t n_other = 0, n_mismatch = 0;
+    int64_t origin = 0, n_outside = 0;                 // a region read: where ref begins on the contig; records that reach beyond ref
     // kept records, sorted by (start, end) (stable)
     std::vector<int64_t> start, end;
     std::vector<int32_t> gi;                           // index of GT in FORMAT
@@ -176,26 +177,17 @@ int read_fasta_single(const char *path, phi_vcf *v, char *err, int cap)
 
 struct RawRec { int64_t start, end; int32_t gi; Sl alt; Sl cols; };
 
-}  // namespace
-
-extern "C" {
-
-int phi_vcf_read(const char *vcf_path, const char *fasta_path, phi_vcf **out, char *err, int err_cap)
+// The rule pass over VCF text in memory: v->ref is the reference (a whole record, or its bases from `origin` on), a record's
+// position is POS - 1 - origin, `only` (may be null) the one contig to read -- without it the first contig seen.  vcf_path
+// stands in the messages.
+int vcf_rules(phi_vcf *v, const char *text, size_t n_text, int64_t origin, const char *only, const char *vcf_path, char *err, int err_cap)
 {
-    if (!vcf_path || !fasta_path || !out) return vfail(err, err_cap, PHI_HOST_ERR_INVALID, "null argument");
-    *out = nullptr;
-    phi_vcf *v = new phi_vcf;
-    struct Guard { phi_vcf *&v; ~Guard() { delete v; } } guard{v};
-    int rc = read_fasta_single(fasta_path, v, err, err_cap);
-    if (rc) return rc;
-    std::vector<char> raw;
-    rc = load_file(vcf_path, raw);
-    if (rc) return vfail(err, err_cap, PHI_HOST_ERR_IO, rc == -2 ? "%s: corrupt gzip stream" : "cannot open or read %s", vcf_path);
     const int64_t ref_len = (int64_t)v->ref.size();
+    v->origin = origin;
     std::vector<RawRec> recs;
-    bool have_contig = false;
-    Sl contig{nullptr, 0};
-    const char *p = raw.data(), *e = p + raw.size();
+    bool have_contig = only != nullptr;
+    Sl contig{only, only ? strlen(only) : 0};
+    const char *p = text, *e = p + n_text;
     int64_t line_no = 0;
     while (p < e) {
         const char *nl = (const char *)memchr(p, '\n', (size_t)(e - p));
@@ -235,7 +227,7 @@ int phi_vcf_read(const char *vcf_path, const char *fasta_path, phi_vcf **out, ch
         int64_t pos1 = 0;
         if (!parse_pos(col[1], &pos1))
             return vfail(err, err_cap, PHI_HOST_ERR_INVALID, "%s line %lld: POS is no integer", vcf_path, (long long)line_no);
-        const int64_t pos = pos1 - 1;
+        const int64_t pos = pos1 - 1 - origin;
         // GT in FORMAT
         int32_t gi = -1, fi = 0;
         for (const char *s = col[8].p, *fe = s + col[8].n;; fi++) {
@@ -246,6 +238,7 @@ int phi_vcf_read(const char *vcf_path, const char *fasta_path, phi_vcf **out, ch
             s = t + 1;
         }
         const int64_t rl = (int64_t)col[3].n;
+        if (gi >= 0 && (pos < 0 || pos + rl > ref_len)) v->n_outside++;
         if (gi < 0 || pos < 0 || pos + rl > ref_len) { p = next; continue; }
         bool same = true;
         for (int64_t i = 0; i < rl && same; i++) same = up(col[3].p[i]) == v->ref[(size_t)(pos + i)];
@@ -305,6 +298,42 @@ int phi_vcf_read(const char *vcf_path, const char *fasta_path, phi_vcf **out, ch
     }
     v->site_off.push_back((int64_t)n);
     if (n == 0) v->site_off.assign(1, 0);
+    return PHI_HOST_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int phi_vcf_read(const char *vcf_path, const char *fasta_path, phi_vcf **out, char *err, int err_cap)
+{
+    if (!vcf_path || !fasta_path || !out) return vfail(err, err_cap, PHI_HOST_ERR_INVALID, "null argument");
+    *out = nullptr;
+    phi_vcf *v = new phi_vcf;
+    struct Guard { phi_vcf *&v; ~Guard() { delete v; } } guard{v};
+    int rc = read_fasta_single(fasta_path, v, err, err_cap);
+    if (rc) return rc;
+    std::vector<char> raw;
+    rc = load_file(vcf_path, raw);
+    if (rc) return vfail(err, err_cap, PHI_HOST_ERR_IO, rc == -2 ? "%s: corrupt gzip stream" : "cannot open or read %s", vcf_path);
+    if ((rc = vcf_rules(v, raw.data(), raw.size(), 0, nullptr, vcf_path, err, err_cap))) return rc;
+    *out = v;
+    v = nullptr;
+    return PHI_HOST_OK;
+}
+
+int phi_vcf_read_text(const char *text, int64_t n_text, const char *ref, int64_t ref_len, const char *ref_name, int64_t origin, const char *contig,
+                      phi_vcf **out, char *err, int err_cap)
+{
+    if (!out || n_text < 0 || ref_len < 0 || (n_text > 0 && !text) || (ref_len > 0 && !ref)) return vfail(err, err_cap, PHI_HOST_ERR_INVALID, "null argument or negative size");
+    *out = nullptr;
+    phi_vcf *v = new phi_vcf;
+    struct Guard { phi_vcf *&v; ~Guard() { delete v; } } guard{v};
+    v->ref.resize((size_t)ref_len);
+    for (int64_t i = 0; i < ref_len; i++) v->ref[(size_t)i] = up(ref[i]);
+    if (ref_name) v->ref_name = ref_name;
+    const int rc = vcf_rules(v, text, (size_t)n_text, origin, contig, "the VCF text", err, err_cap);
+    if (rc) return rc;
     *out = v;
     v = nullptr;
     return PHI_HOST_OK;
@@ -318,6 +347,8 @@ int64_t phi_vcf_n_records(const phi_vcf *v) { return (int64_t)v->start.size(); }
 int64_t phi_vcf_n_sites(const phi_vcf *v) { return (int64_t)v->site_off.size() - 1; }
 int64_t phi_vcf_n_other_contig(const phi_vcf *v) { return v->n_other; }
 int64_t phi_vcf_n_ref_mismatch(const phi_vcf *v) { return v->n_mismatch; }
+int64_t phi_vcf_origin(const phi_vcf *v) { return v->origin; }
+int64_t phi_vcf_n_outside(const phi_vcf *v) { return v->n_outside; }
 int64_t phi_vcf_ref_len(const phi_vcf *v) { return (int64_t)v->ref.size(); }
 const char *phi_vcf_ref_seq(const phi_vcf *v) { return v->ref.data(); }
 const int64_t *phi_vcf_rec_start(const phi_vcf *v) { return v->start.data(); }

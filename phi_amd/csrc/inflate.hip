@@ -526,6 +526,9 @@ struct InfRun {
     int64_t n;
     int32_t flags;
     int64_t hdr = 0;                                            // byte offset of the first member's deflate data
+    const int64_t *known = nullptr;                             // (may be null) byte offsets where deflate data begins, ascending: members whose
+    int64_t n_known = 0;                                        // bounds the caller knows (BGZF); they stand in for the finder
+    int64_t cap_hint = 0;                                       // with them: symbols a decoder may write on its first run, at the least
     InfChunks ck{};
     hipStream_t st = nullptr;
     uint32_t *d_in = nullptr;
@@ -582,8 +585,17 @@ int InfRun::find()
     d_starts = p;
     starts.assign((size_t)nch, -1);
     starts[0] = hdr * 8;
+    if (known) {
+        // A member of one final block has no start the finder takes (it looks for a block that is not the last, followed by a
+        // plausible one), so a BGZF file of such members would be decoded by one decoder.  A chunk's start is then the first
+        // known one that lies in it; the decoders and the chain treat it as a found one
+        for (int64_t k = 0; k < n_known; k++) {
+            const int64_t c = known[k] / ck.C;
+            if (known[k] > hdr && known[k] < n && c >= 1 && c < nch && starts[(size_t)c] < 0) starts[(size_t)c] = known[k] * 8;
+        }
+    }
     DCHK(hipMemcpyAsync(d_starts, starts.data(), (size_t)nch * 8, hipMemcpyHostToDevice, st));
-    if (nch > 1 && !(flags & PHI_INFLATE_NO_FINDER)) {
+    if (nch > 1 && !known && !(flags & PHI_INFLATE_NO_FINDER)) {
         hipLaunchKernelGGL(phi_inflate_find_kernel, dim3(nch - 1), dim3(64), 0, st, d_in, n * 8, ck.C * 8, d_starts);
         DCHK(hipGetLastError());
         DCHK(hipMemcpyAsync(starts.data(), d_starts, (size_t)nch * 8, hipMemcpyDeviceToHost, st));
@@ -612,7 +624,7 @@ int InfRun::decode()
 {
     inf_job_index(starts, job_of, chunk_of);
     const size_t nj = chunk_of.size();
-    const int64_t cap = inf_sym_capacity(src, n, ck.C);
+    const int64_t cap = std::max(inf_sym_capacity(src, n, ck.C), cap_hint);
     const int32_t mem_cap = inf_member_capacity(n, (int64_t)nj);
     DALLOC(d_sym, uint16_t, nj * (size_t)cap * 2);
     inf_job_list(starts, chunk_of, cap, d_sym, jobs);
@@ -703,12 +715,15 @@ void InfRun::fill_info()
 
 // the whole inflate; the checked output stays in *d_out_ret (one of dev's buffers), *out_size bytes
 int inflate_run(Dev &dev, int32_t device, const void *in, int64_t n, int64_t chunk_bytes, int32_t flags, int64_t *out_size,
-                uint8_t **d_out_ret, phi_inflate_info *info)
+                uint8_t **d_out_ret, phi_inflate_info *info, const int64_t *known = nullptr, int64_t n_known = 0, int64_t cap_hint = 0)
 {
     if (info) memset(info, 0, sizeof(*info));
     if (!out_size || n < 0 || (n > 0 && !in)) return fail(info, PHI_ERR_INVALID, "phi_inflate: null pointer or negative size");
     *out_size = 0;
     InfRun R{dev, info, (const uint8_t *)in, n, flags};
+    R.known = n_known > 0 ? known : nullptr;
+    R.n_known = n_known;
+    R.cap_hint = R.known ? cap_hint : 0;
     R.hdr = inf_gz_header(R.src, n, 0);
     if (R.hdr < 0) return fail(info, PHI_ERR_INVALID, "phi_inflate: %s gzip header", R.hdr == -2 ? "truncated" : "not a");
     if (inf_chunk_plan(n, chunk_bytes, getenv("PHI_INFLATE_CHUNK"), R.ck, R.err)) return R.refused();
@@ -776,6 +791,22 @@ int phi_inflate_to_device(int32_t device, const void *in, int64_t n, int64_t chu
     Dev dev;
     uint8_t *d = nullptr;
     const int rc = inflate_run(dev, device, in, n, chunk_bytes, flags, out_size, &d, info);
+    if (rc) return rc;
+    dev.bufs.erase(std::find(dev.bufs.begin(), dev.bufs.end(), (void *)d));   // (kept: the caller owns it now)
+    *d_out = d;
+    return PHI_OK;
+}
+
+// phi_inflate_to_device for members whose bounds the caller knows (vcf_region.hip: BGZF members followed by BSIZE): starts[0,
+// n_starts) are the byte offsets in `in` where a member's deflate data begins, ascending; they stand in for the finder, which
+// finds no start in members of one final block.  A wrong offset costs what a false start of the finder costs: its decoder's
+// output is not used.  sym_cap: symbols a decoder may write on its first run, at the least (0: the usual guess)
+int phi_inflate_to_device_starts(int32_t device, const void *in, int64_t n, int64_t chunk_bytes, const int64_t *starts, int64_t n_starts, int64_t sym_cap,
+                                 void **d_out, int64_t *out_size, phi_inflate_info *info)
+{
+    Dev dev;
+    uint8_t *d = nullptr;
+    const int rc = inflate_run(dev, device, in, n, chunk_bytes, 0, out_size, &d, info, starts, n_starts, sym_cap);
     if (rc) return rc;
     dev.bufs.erase(std::find(dev.bufs.begin(), dev.bufs.end(), (void *)d));   // (kept: the caller owns it now)
     *d_out = d;

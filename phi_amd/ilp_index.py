@@ -35,6 +35,11 @@ HOST_SYMBOLS = [
     "phi_vcf_rec_gt_index", "phi_vcf_rec_alt_off", "phi_vcf_alt_pos", "phi_vcf_alt_bytes", "phi_vcf_site_off", "phi_vcf_text", "phi_vcf_text_off",
     "phi_vcf_parse_gt", "phi_vcf_build", "phi_vcf_n_units", "phi_vcf_unit_first", "phi_vcf_n_real_sites", "phi_vcf_site_backbone",
     "phi_vcf_site_allele0", "phi_vcf_n_kept_haps", "phi_vcf_choice",
+    "phi_region_parse", "phi_region_plan", "phi_region_open", "phi_region_free", "phi_region_name", "phi_region_beg", "phi_region_end",
+    "phi_region_contig_len", "phi_region_in_index", "phi_region_n_members", "phi_region_member_at", "phi_region_member_text_off",
+    "phi_region_n_ranges", "phi_region_ranges", "phi_region_gz", "phi_region_n_gz", "phi_region_header", "phi_region_n_header",
+    "phi_region_ref", "phi_region_n_ref", "phi_region_fasta_members", "phi_fasta_slice", "phi_region_free_bases", "phi_vcf_read_text",
+    "phi_vcf_read_region", "phi_vcf_origin", "phi_vcf_n_outside",
     "phi_bam_header", "phi_panel_choose", "phi_write_calls_vcf",
     "phi_format_fasta", "phi_format_fasta_fai", "phi_format_calls_vcf", "phi_host_free_text",
     "phi_write_calls_vcf_support", "phi_format_calls_vcf_support",
@@ -110,7 +115,8 @@ def host_lib():
     L.phi_vcf_free.restype = None
     L.phi_vcf_free.argtypes = [vp]
     for n, rt in (("n_samples", C.c_int32), ("n_kept_haps", C.c_int32), ("contig", C.c_char_p), ("n_records", C.c_int64), ("n_sites", C.c_int64),
-                  ("n_other_contig", C.c_int64), ("n_ref_mismatch", C.c_int64), ("ref_len", C.c_int64), ("n_units", C.c_int64), ("n_real_sites", C.c_int64)):
+                  ("n_other_contig", C.c_int64), ("n_ref_mismatch", C.c_int64), ("ref_len", C.c_int64), ("n_units", C.c_int64), ("n_real_sites", C.c_int64),
+                  ("origin", C.c_int64), ("n_outside", C.c_int64)):
         f = getattr(L, "phi_vcf_" + n)
         f.restype = rt
         f.argtypes = [vp]
@@ -123,6 +129,23 @@ def host_lib():
     L.phi_vcf_sample_name.argtypes = [vp, C.c_int32]
     L.phi_vcf_parse_gt.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, C.c_int32, vp, vp, C.c_char_p, C.c_int]
     L.phi_vcf_build.argtypes = [vp, vp, vp, C.c_int32, C.POINTER(vp), C.c_char_p, C.c_int]
+    L.phi_region_parse.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_char_p, C.c_int]
+    L.phi_region_plan.argtypes = [C.c_char_p, C.c_char_p, C.c_int64, C.c_int64, C.c_int32, C.POINTER(vp), C.c_char_p, C.c_int]
+    L.phi_region_open.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(vp), C.c_char_p, C.c_int]
+    L.phi_region_free.restype = None
+    L.phi_region_free.argtypes = [vp]
+    for n, rt in (("name", C.c_char_p), ("beg", C.c_int64), ("end", C.c_int64), ("contig_len", C.c_int64), ("in_index", C.c_int32), ("n_members", C.c_int64),
+                  ("member_at", vp), ("member_text_off", vp), ("n_ranges", C.c_int32), ("ranges", vp), ("gz", vp), ("n_gz", C.c_int64), ("header", vp),
+                  ("n_header", C.c_int64), ("ref", vp), ("n_ref", C.c_int64), ("fasta_members", C.c_int64)):
+        f = getattr(L, "phi_region_" + n)
+        f.restype = rt
+        f.argtypes = [vp]
+    L.phi_fasta_slice.argtypes = [C.c_char_p, C.c_char_p, C.c_int64, C.c_int64, C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                  C.POINTER(C.c_int64), C.c_char_p, C.c_int]
+    L.phi_region_free_bases.restype = None
+    L.phi_region_free_bases.argtypes = [vp]
+    L.phi_vcf_read_text.argtypes = [vp, C.c_int64, vp, C.c_int64, C.c_char_p, C.c_int64, C.c_char_p, C.POINTER(vp), C.c_char_p, C.c_int]
+    L.phi_vcf_read_region.argtypes = [vp, vp, C.c_int64, C.POINTER(vp), C.c_char_p, C.c_int]
     L.phi_write_fasta.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int64]
     L.phi_write_calls_vcf.argtypes = [C.c_char_p, C.c_char_p, C.c_int64, C.c_char_p, C.c_int64, vp, vp, vp, vp, vp, vp,
                                       C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_char_p, C.c_int]
@@ -348,20 +371,113 @@ def parse_gt(text, text_off, gt_index, n_samples, rec_lo=0, rec_hi=None, gt=None
     return gt, ploidy
 
 
-class VcfGraph:
-    """A phased VCF + reference FASTA read by phi_vcf_read: the kept records (fixed columns), the sites and the sample-column
-    text; build(gt, ploidy, max_len) makes the graph of phi_amd.vcf2gfa -- the attributes of Graph, with walk_off / walk_vtx
-    None: Context.set_graph_vcf writes the walk entries on the device -- and the unit tables the device needs."""
+def parse_region(region):
+    """(name, BEG, END) of "NAME", "NAME:BEG" or "NAME:BEG-END": 1-based and inclusive as written, END None when absent
+    (phi_region_parse; HostError for a string that is no region)."""
+    L = host_lib()
+    name, b, e, err = C.create_string_buffer(4096), C.c_int64(), C.c_int64(), C.create_string_buffer(1024)
+    rc = L.phi_region_parse(os.fsencode(region), name, 4096, C.byref(b), C.byref(e), err, 1024)
+    if rc:
+        raise HostError(rc, err.value.decode())
+    return name.value.decode(), b.value, None if e.value < 0 else e.value
 
-    def __init__(self, vcf_path, fasta_path):
+
+def fasta_slice(fasta_path, name, beg, end=-1, with_info=False):
+    """Bases [beg, end) (0-based; end < 0: to the record's end) of record `name` of an indexed FASTA, upper-cased
+    (phi_fasta_slice: .fai, and .gzi for a BGZF file -- what `samtools faidx FILE REGION` prints, without its line ends)."""
+    L = host_lib()
+    p, n, ln, mem, err = C.c_void_p(), C.c_int64(), C.c_int64(), C.c_int64(), C.create_string_buffer(1024)
+    rc = L.phi_fasta_slice(os.fsencode(fasta_path), os.fsencode(name), beg, end, C.byref(p), C.byref(n), C.byref(ln), C.byref(mem), err, 1024)
+    if rc:
+        raise HostError(rc, err.value.decode())
+    try:
+        out = C.string_at(p, n.value)
+    finally:
+        L.phi_region_free_bases(p)
+    return (out, {"contig_len": ln.value, "members": mem.value}) if with_info else out
+
+
+class RegionPlan:
+    """What the host decides about a region of an indexed BGZF VCF before a record is looked at (include/phi_host.h
+    phi_region_plan / phi_region_open): the BGZF members the .tbi points at (member_at: their file offsets; gz: their bytes back
+    to back), every merged chunk as a byte range of their inflated text (ranges [n, 2]; member_text_off), the header text,
+    and from open() the reference slice ref and the contig's length.  RegionPlan(vcf, name, b, e) plans one 0-based
+    half-open interval; RegionPlan.open(vcf, fasta, "NAME:BEG-END") is the whole host side of set_graph_vcf(region=)."""
+
+    def __init__(self, vcf_path, name, beg, end, load=True, _open=None):
         L = host_lib()
         self._L = L
         self._h = C.c_void_p()
         err = C.create_string_buffer(1024)
-        rc = L.phi_vcf_read(os.fsencode(vcf_path), os.fsencode(fasta_path), C.byref(self._h), err, 1024)
+        if _open is not None:
+            rc = L.phi_region_open(os.fsencode(vcf_path), os.fsencode(_open[0]), os.fsencode(_open[1]), C.byref(self._h), err, 1024)
+        else:
+            rc = L.phi_region_plan(os.fsencode(vcf_path), os.fsencode(name), beg, end, 1 if load else 0, C.byref(self._h), err, 1024)
         if rc:
             raise HostError(rc, err.value.decode())
         h = self._h
+        self.name = L.phi_region_name(h).decode()
+        self.beg, self.end, self.contig_len = L.phi_region_beg(h), L.phi_region_end(h), L.phi_region_contig_len(h)
+        self.in_index = bool(L.phi_region_in_index(h))
+        m = L.phi_region_n_members(h)
+        self.member_at = _view(L.phi_region_member_at(h), m, C.c_int64, np.int64).copy()
+        self.member_text_off = _view(L.phi_region_member_text_off(h), m + 1, C.c_int64, np.int64).copy()
+        self.ranges = _view(L.phi_region_ranges(h), 2 * L.phi_region_n_ranges(h), C.c_int64, np.int64).copy().reshape(-1, 2)
+        self.gz = C.string_at(L.phi_region_gz(h), L.phi_region_n_gz(h)) if L.phi_region_n_gz(h) else b""
+        self.header = C.string_at(L.phi_region_header(h), L.phi_region_n_header(h)) if L.phi_region_n_header(h) else b""
+        self.ref = C.string_at(L.phi_region_ref(h), L.phi_region_n_ref(h)) if L.phi_region_n_ref(h) else b""
+        self.fasta_members = L.phi_region_fasta_members(h)
+
+    @classmethod
+    def open(cls, vcf_path, fasta_path, region):
+        return cls(vcf_path, None, 0, 0, _open=(fasta_path, region))
+
+    def close(self):
+        if self._h:
+            self._L.phi_region_free(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class VcfGraph:
+    """A phased VCF + reference FASTA read by phi_vcf_read: the kept records (fixed columns), the sites and the sample-column
+    text; build(gt, ploidy, max_len) makes the graph of phi_amd.vcf2gfa -- the attributes of Graph, with walk_off / walk_vtx
+    None: Context.set_graph_vcf writes the walk entries on the device -- and the unit tables the device needs.
+    region=RegionPlan (from RegionPlan.open) with lines=the record lines phi_vcf_region_filter kept: the same rule pass over
+    header + lines against the plan's reference slice (phi_vcf_read_region); positions count from the region's first base
+    (origin), region = (name, b, e), n_outside the records that reach over an edge of the region.
+    text=(vcf text, reference bases, origin, contig or None): the rule pass over text in memory (phi_vcf_read_text)."""
+
+    def __init__(self, vcf_path, fasta_path, region=None, lines=b"", text=None):
+        L = host_lib()
+        self._L = L
+        self._h = C.c_void_p()
+        err = C.create_string_buffer(1024)
+        self.region = None
+        if region is not None:
+            rc = L.phi_vcf_read_region(region._h, lines, len(lines), C.byref(self._h), err, 1024)
+            self.region = (region.name, region.beg, region.end)
+            self.contig_len = region.contig_len
+        elif text is not None:
+            vt, ref, origin, contig = text
+            rc = L.phi_vcf_read_text(vt, len(vt), ref, len(ref), None, origin, None if contig is None else os.fsencode(contig), C.byref(self._h), err, 1024)
+        else:
+            rc = L.phi_vcf_read(os.fsencode(vcf_path), os.fsencode(fasta_path), C.byref(self._h), err, 1024)
+        if rc:
+            raise HostError(rc, err.value.decode())
+        h = self._h
+        self.origin, self.n_outside = L.phi_vcf_origin(h), L.phi_vcf_n_outside(h)
         self.samples = [L.phi_vcf_sample_name(h, s).decode() for s in range(L.phi_vcf_n_samples(h))]
         self.contig = L.phi_vcf_contig(h).decode()
         self.n_records, self.n_sites = L.phi_vcf_n_records(h), L.phi_vcf_n_sites(h)
@@ -385,6 +501,8 @@ class VcfGraph:
             out.append(f"{self.n_other_contig} record(s) of other contigs than {self.contig} skipped (vcf2gfa handles one contig)")
         if self.n_ref_mismatch:
             out.append(f"{self.n_ref_mismatch} record(s) skipped: their REF column is not what the FASTA holds at POS (another assembly?)")
+        if self.region is not None and self.n_outside:
+            out.append(f"{self.n_outside} record(s) skipped: they reach over an edge of the region {self.region[0]}:{self.region[1] + 1}-{self.region[2]}")
         return out
 
     def alts(self, r):
