@@ -19,7 +19,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
 HIP_SOURCES = ["sketch.hip", "sketch_pooled.hip", "sketch_win_fixed.hip", "table.hip", "anchors.hip", "contexts.hip", "dp.hip", "dp_events.hip", "dp_blocks.hip", "phi_abi.hip", "dev_mem.hip", "read_batches.hip", "text_stream.hip", "text_park.hip", "set_graph.hip", "phi_solve.hip", "solve_dev.hip", "phi_comm.hip", "phi_ipc.hip", "reads_text.hip", "walk_text.hip", "edit.hip", "edit_path.hip", "inflate.hip", "gfa_text.hip", "chop.hip", "vcf.hip", "ladder.hip", "panel.hip", "panel_score.hip", "scan.hip", "bam.hip", "calls.hip", "calls_support.hip", "deflate.hip", "bgzf_index.hip", "vcf_region.hip"]
-HIP_HEADERS = ["phi_dev.h", "phi_kernels.h", "phi_ctx.h", "phi_dp_flags.h", "phi_host_par.h", "phi_wave.h", "dp_dev.h", "dp_steps.h", "solve_host.h", "reads_host.h", "bam_header.h", "deflate_codes.h", "crc32_shift.h", "inflate_host.h", "bgzf_index_host.h", "region_host.h", "vcf_lines_dev.h", "dev_run.h", "sketch_dev.h", "sketch_phases.inc", "sketch_minima.inc", "sketch_rounds.inc", "sketch_rounds_kmer.inc", "edit_band.inc", os.path.join("host", "panel_choose.h"), os.path.join("..", "..", "include", "phi_amd.h")]
+HIP_HEADERS = ["phi_dev.h", "phi_kernels.h", "phi_ctx.h", "phi_dp_flags.h", "phi_host_par.h", "phi_wave.h", "dp_dev.h", "dp_steps.h", "solve_host.h", "reads_host.h", "bam_header.h", "deflate_codes.h", "crc32_shift.h", "inflate_host.h", "bgzf_index_host.h", "region_host.h", "vcf_lines_dev.h", "text_bytes.h", "dev_run.h", "sketch_dev.h", "sketch_phases.inc", "sketch_minima.inc", "sketch_rounds.inc", "sketch_rounds_kmer.inc", "edit_band.inc", os.path.join("host", "panel_choose.h"), os.path.join("..", "..", "include", "phi_amd.h")]
 
 
 def _run(cmd, cwd=None):

@@ -31,6 +31,7 @@
 #include "phi_wave.h"
 #include "dev_run.h"
 #include "vcf_lines_dev.h"
+#include "text_bytes.h"
 #include "bgzf_index_host.h"
 
 #define BIX_MAX_LINES 2147483646ll      // lines are numbered in 32 bits (the compaction's indices)
@@ -40,31 +41,15 @@ namespace {
 
 enum { BIX_EMPTY = 1, BIX_FIELDS, BIX_POS, BIX_END, BIX_ORDER, BIX_RANGE, BIX_NAME };
 
-// the bytes of x that equal the byte repeated in pat, one bit each
-__device__ __forceinline__ uint32_t bix_eq4(uint32_t x, uint32_t pat)
-{
-    const uint32_t y = x ^ pat;
-    const uint32_t z = ~(((y & 0x7f7f7f7fu) + 0x7f7f7f7fu) | y) & 0x80808080u;
-    return ((z >> 7) & 1u) | ((z >> 14) & 2u) | ((z >> 21) & 4u) | ((z >> 28) & 8u);
-}
-
 // the three masks of the 16 bytes at 16 g (text is readable to the next multiple of BIX_WG and 64 bytes beyond)
 __device__ __forceinline__ void bix_masks(const uint8_t *__restrict__ text, int64_t n, int64_t g, uint32_t *nl, uint32_t *tab, uint32_t *end)
 {
     const int64_t p0 = g * BIX_LANE;
     *nl = *tab = *end = 0;
     if (p0 >= n) return;
-    const uint4 v = *(const uint4 *)(text + p0);
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-    const uint32_t valid = n - p0 >= BIX_LANE ? 0xffffu : (1u << (int)(n - p0)) - 1u;
-    uint32_t m_nl = 0, m_tab = 0, m_e = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        m_nl |= bix_eq4(w[k], 0x0a0a0a0au) << (4 * k);
-        m_tab |= bix_eq4(w[k], 0x09090909u) << (4 * k);
-        m_e |= bix_eq4(w[k], 0x45454545u) << (4 * k);
-    }
-    m_e &= valid;
+    const PhiText16 v = phi_load16(text, p0);
+    const uint32_t valid = phi_valid16(p0, 0, n);
+    uint32_t m_e = phi_eq16(v, 'E') & valid;
     uint32_t m_end = 0;
     while (m_e) {                                       // at most 16 turns, and 'E' is rare
         const int j = __ffs((int)m_e) - 1;
@@ -74,8 +59,8 @@ __device__ __forceinline__ void bix_masks(const uint8_t *__restrict__ text, int6
         const uint8_t b = text[p - 1];
         if ((b == '\t' || b == ';') && text[p + 1] == 'N' && text[p + 2] == 'D' && text[p + 3] == '=') m_end |= 1u << j;
     }
-    *nl = m_nl & valid;
-    *tab = m_tab & valid;
+    *nl = phi_eq16(v, '\n') & valid;
+    *tab = phi_eq16(v, '\t') & valid;
     *end = m_end;
 }
 
@@ -234,11 +219,7 @@ __global__ void __launch_bounds__(256) phi_bix_contigs_kernel(BixRecords R, int6
 {
     const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (r >= n_rec) return;
-    int64_t lo = 0, hi = n_ctg;                         // the last contig head at or before r (ctg_rec[0] == 0)
-    while (hi - lo > 1) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if (ctg_rec[mid] <= r) lo = mid; else hi = mid;
-    }
+    const int64_t lo = phi_last_le(ctg_rec, n_ctg, r);  // the last contig head at or before r (ctg_rec[0] == 0)
     R.ctg[r] = (int32_t)lo;
     atomicMax(&max_end[lo], R.end[r]);
 }

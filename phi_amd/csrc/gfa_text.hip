@@ -21,6 +21,7 @@
 #include <vector>
 #include "phi_ctx.h"
 #include "phi_wave.h"
+#include "text_bytes.h"
 
 #define GT_TILE ((int64_t)64 << 10)     // bytes per workgroup of the scan
 #define GT_CAP_DEFAULT (1 << 20)        // candidate W-lines at most (PHI_GFA_SPLIT_CAP)
@@ -29,24 +30,6 @@ extern "C" int phi_inflate_to_device(int32_t device, const void *in, int64_t n, 
                                      int64_t *out_size, phi_inflate_info *info);      // inflate.hip
 
 namespace {
-
-// bytes of x equal to ch, as 4 bits (exact: no false positives from borrows)
-__device__ __forceinline__ uint32_t eq4(uint32_t x, uint32_t ch)
-{
-    const uint32_t y = x ^ (ch * 0x01010101u);
-    const uint32_t z = ~(((y & 0x7f7f7f7fu) + 0x7f7f7f7fu) | y) & 0x80808080u;
-    return ((z >> 7) & 1u) | ((z >> 14) & 2u) | ((z >> 21) & 4u) | ((z >> 28) & 8u);
-}
-
-// bytes equal to ch among the 16 at p (p 16-byte aligned, p < n: the buffer holds 16 bytes past n), bit k = byte p + k,
-// bytes at or behind n cleared
-__device__ __forceinline__ uint32_t eq16(const uint8_t *__restrict__ text, int64_t p, int64_t n, uint32_t ch)
-{
-    const uint4 v = *reinterpret_cast<const uint4 *>(text + p);
-    uint32_t m = eq4(v.x, ch) | (eq4(v.y, ch) << 4) | (eq4(v.z, ch) << 8) | (eq4(v.w, ch) << 12);
-    if (n - p < 16) m &= (1u << (n - p)) - 1u;
-    return m;
-}
 
 __global__ void __launch_bounds__(256) phi_gfa_split_scan_kernel(const uint8_t *__restrict__ text, int64_t n, int64_t n_tiles,
                                                                  int64_t *__restrict__ tile_nl, int64_t *__restrict__ cand, int32_t cap,
@@ -62,11 +45,11 @@ __global__ void __launch_bounds__(256) phi_gfa_split_scan_kernel(const uint8_t *
         for (int64_t p = lo + 16 * (int64_t)threadIdx.x; p - 16 * (int64_t)threadIdx.x < hi; p += 16 * 256) {
             uint32_t nl = 0, w = 0, tab = 0;
             if (p < hi) {
-                const uint4 v = *reinterpret_cast<const uint4 *>(text + p);
+                const PhiText16 v = phi_load16(text, p);
                 const uint32_t x4 = p + 16 < n ? *reinterpret_cast<const uint32_t *>(text + p + 16) : 0u;   // look-ahead: bytes 16..19
-                nl = eq4(v.x, '\n') | (eq4(v.y, '\n') << 4) | (eq4(v.z, '\n') << 8) | (eq4(v.w, '\n') << 12);
-                w = eq4(v.x, 'W') | (eq4(v.y, 'W') << 4) | (eq4(v.z, 'W') << 8) | (eq4(v.w, 'W') << 12) | (eq4(x4, 'W') << 16);
-                tab = eq4(v.x, '\t') | (eq4(v.y, '\t') << 4) | (eq4(v.z, '\t') << 8) | (eq4(v.w, '\t') << 12) | (eq4(x4, '\t') << 16);
+                nl = phi_eq16(v, '\n');
+                w = phi_eq16(v, 'W') | (phi_eq4(x4, 'W') << 16);
+                tab = phi_eq16(v, '\t') | (phi_eq4(x4, '\t') << 16);
                 const int64_t room = n - p;                                   // bytes of the text from p on
                 if (room < 20) { const uint32_t ok = (1u << room) - 1u; nl &= ok; w &= ok; tab &= ok; }
                 nl &= 0xffffu;
@@ -112,8 +95,7 @@ __global__ void __launch_bounds__(256) phi_gfa_split_line_kernel(const uint8_t *
     int64_t e = -1;
     for (int64_t base = s & ~(int64_t)15; base < tile_hi; base += 1024) {
         const int64_t p = base + 16 * lane;
-        uint32_t m = p < n ? eq16(text, p, n, '\n') : 0u;
-        if (p < s) m &= ~0u << (s - p >= 16 ? 16 : (int)(s - p));
+        const uint32_t m = p < n ? phi_eq16(phi_load16(text, p), '\n') & phi_valid16(p, s, n) : 0u;      // (a line feed of [s, n))
         const unsigned long long b = __ballot(m != 0);
         if (b) {
             const int l = __ffsll((long long)b) - 1;
@@ -136,8 +118,7 @@ __global__ void __launch_bounds__(256) phi_gfa_split_line_kernel(const uint8_t *
         int need = 6;
         for (int64_t base = s & ~(int64_t)15; base < e; base += 1024) {
             const int64_t p = base + 16 * lane;
-            uint32_t m = p < e ? eq16(text, p, e, '\t') : 0u;
-            if (p < s) m &= ~0u << (s - p >= 16 ? 16 : (int)(s - p));
+            uint32_t m = p < e ? phi_eq16(phi_load16(text, p), '\t') & phi_valid16(p, s, e) : 0u;
             const int cnt = __popc(m);
             const int inc = phi_wave_incl_scan(cnt);
             const int total = __shfl(inc, 63, 64);
@@ -164,31 +145,19 @@ __global__ void __launch_bounds__(256) phi_gfa_split_copy_kernel(const uint8_t *
                                                                  const int64_t *__restrict__ tile0, int64_t n_tiles, uint8_t *__restrict__ out)
 {
     for (int64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
-        int lo = 0, hi = n_walks;                                         // walk of the tile: tile0[w] <= t < tile0[w + 1]
-        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (tile0[mid] <= t) lo = mid; else hi = mid; }
-        const GtCopy W = walks[lo];
-        const int64_t off = (t - tile0[lo]) * WT_TILE + 16 * (int64_t)threadIdx.x;
+        const int w = phi_last_le(tile0, n_walks, t);                     // walk of the tile: tile0[w] <= t < tile0[w + 1]
+        const GtCopy W = walks[w];
+        const int64_t off = (t - tile0[w]) * WT_TILE + 16 * (int64_t)threadIdx.x;
         if (off >= W.len) continue;
         const int64_t k = min((int64_t)16, W.len - off);
-        const uint8_t *s = text + W.src + off;
         uint8_t *d = out + W.dst + off;
-        const int sh = (int)(W.src & 15);                                 // (the same for the whole tile)
         if (k == 16) {
-            // the two aligned 16-byte words that hold s[0, 16), shifted into place (the second is inside the text: s + 15 < its end)
-            const uint4 v0 = *reinterpret_cast<const uint4 *>(s - sh);
-            const uint4 v1 = sh ? *reinterpret_cast<const uint4 *>(s - sh + 16) : v0;
-            const uint32_t x[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-            const int q = sh >> 2, r = sh & 3;
-            uint32_t o[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const uint32_t lo_ = q == 0 ? x[j] : q == 1 ? x[j + 1] : q == 2 ? x[j + 2] : x[j + 3];
-                const uint32_t hi_ = q == 0 ? x[j + 1] : q == 1 ? x[j + 2] : q == 2 ? x[j + 3] : x[j + 4];
-                o[j] = __builtin_amdgcn_alignbyte(hi_, lo_, (uint32_t)r);
-            }
-            *reinterpret_cast<uint4 *>(d) = make_uint4(o[0], o[1], o[2], o[3]);
+            // (an unaligned source takes a second aligned word, the one that holds the walk's byte off + 15: inside the text or its slack)
+            const PhiText16 v = phi_load16_unaligned(text, W.src + off);
+            *reinterpret_cast<uint4 *>(d) = make_uint4(v.x, v.y, v.z, v.w);
             continue;
         }
+        const uint8_t *s = text + W.src + off;
         for (int64_t j = 0; j < k; j++) d[j] = s[j];
     }
 }

@@ -1,6 +1,7 @@
 // Sums across the 64 lanes of a wave and across the waves of a workgroup: the one copy of the two idioms every scan,
-// compaction and counter of the device code is made of.  Device code only; workgroups are one-dimensional (the lane is
-// threadIdx.x & 63).  Integer sums only: the order of the additions is not part of the result.
+// compaction and counter of the device code is made of, and the scan of a whole array by one workgroup.  Device code only;
+// workgroups are one-dimensional (the lane is threadIdx.x & 63).  Integer sums only: the order of the additions is not part
+// of the result.
 // (The sketch and DP kernels keep their own DPP scans and reductions, tuned to a register count: sketch_dev.h, dp_dev.h.)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -54,4 +55,31 @@ __device__ __forceinline__ T phi_block_excl_scan(T mine, T *s_w, T *total = null
         *total = t;
     }
     return woff + inc - mine;
+}
+
+// Exclusive prefix sums by ONE workgroup of 1024 threads: out[i] = in[0] + .. + in[i - 1] for i < n; returns the total, in every
+// thread.  Tiles of 4096 items, four consecutive per thread -- the loads are coalesced whatever n is -- and a running carry.
+// out may be in itself: a thread reads its four items before it writes its four sums, and nobody else's (so neither pointer is
+// __restrict__ here).  s_w[16] is LDS of the caller.
+template <class In, class Out>
+__device__ __forceinline__ Out phi_carry_scan(const In *in, int64_t n, Out *out, Out *s_w)
+{
+    Out carry = 0;                                        // everything before the tile
+    for (int64_t base = 0; base < n; base += 4096) {
+        const int64_t i0 = base + 4 * (int64_t)threadIdx.x;
+        In v[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) v[j] = i0 + j < n ? in[i0 + j] : 0;
+        const Out c = (Out)v[0] + v[1] + v[2] + v[3];
+        Out tile;
+        Out run = carry + phi_block_excl_scan<16>(c, s_w, &tile);
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            if (i0 + j < n) out[i0 + j] = run;
+            run += v[j];
+        }
+        carry += tile;
+        __syncthreads();                                  // (s_w is written again in the next turn)
+    }
+    return carry;
 }

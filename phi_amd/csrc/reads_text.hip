@@ -23,47 +23,30 @@
 #include <algorithm>
 #include "phi_kernels.h"
 #include "phi_wave.h"
+#include "text_bytes.h"
 
 #define TXT_TILE 4096u          // bytes per workgroup of the line kernels: 256 lanes x 16 bytes
 
 namespace {
 
-// 0x80 in every byte of v that equals c
-__device__ __forceinline__ uint32_t byte_eq(uint32_t v, uint32_t c4)
+// the line feeds and carriage returns among the lane's 16 bytes at `at` that lie in [start, end); nothing is loaded where none does
+__device__ __forceinline__ void text_masks(const PhiTextArgs &A, uint32_t at, uint32_t *lf, uint32_t *cr)
 {
-    const uint32_t x = v ^ c4;
-    const uint32_t t = (x & 0x7f7f7f7fu) + 0x7f7f7f7fu;
-    return ~(t | x | 0x7f7f7f7fu);
+    *lf = *cr = 0;
+    const uint32_t valid = phi_valid16(at, A.start, A.end);
+    if (!valid) return;
+    const PhiText16 v = phi_load16(A.buf, at);
+    *lf = phi_eq16(v, '\n') & valid;
+    *cr = phi_eq16(v, '\r') & valid;
 }
-
-// the 16 bytes at aligned offset `at`, with the bytes outside [start, end) replaced by 0 (never a line feed)
-__device__ __forceinline__ uint4 load16(const uint8_t *buf, uint32_t at, uint32_t start, uint32_t end)
-{
-    uint4 v = make_uint4(0, 0, 0, 0);
-    if (at + 16 <= start || at >= end) return v;
-    v = *reinterpret_cast<const uint4 *>(buf + at);
-    if (at < start || at + 16 > end) {
-        uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int j = 0; j < 16; j++) {
-            const uint32_t p = at + (uint32_t)j;
-            if (p < start || p >= end) w[j >> 2] &= ~(0xFFu << (8 * (j & 3)));
-        }
-        v = make_uint4(w[0], w[1], w[2], w[3]);
-    }
-    return v;
-}
-
-__device__ __forceinline__ uint32_t lf_flags(uint32_t v) { return byte_eq(v, 0x0a0a0a0au); }
 
 // line feeds per tile; a carriage return anywhere makes the chunk irregular
 __global__ void __launch_bounds__(256) phi_text_count_kernel(PhiTextArgs A)
 {
     const uint32_t a0 = A.start & ~15u;
-    const uint32_t at = a0 + blockIdx.x * TXT_TILE + threadIdx.x * 16u;
-    const uint4 v = load16(A.buf, at, A.start, A.end);
-    uint32_t n = __popc(lf_flags(v.x)) + __popc(lf_flags(v.y)) + __popc(lf_flags(v.z)) + __popc(lf_flags(v.w));
-    const uint32_t cr = byte_eq(v.x, 0x0d0d0d0du) | byte_eq(v.y, 0x0d0d0d0du) | byte_eq(v.z, 0x0d0d0d0du) | byte_eq(v.w, 0x0d0d0d0du);
+    uint32_t lf, cr;
+    text_masks(A, a0 + blockIdx.x * TXT_TILE + threadIdx.x * 16u, &lf, &cr);
+    uint32_t n = __popc(lf);
     if (cr) atomicOr(&A.sum->err, PHI_TEXT_IRREGULAR_CR);
     __shared__ uint32_t s[4];
 #pragma unroll
@@ -76,23 +59,12 @@ __global__ void __launch_bounds__(256) phi_text_count_kernel(PhiTextArgs A)
 // exclusive prefix sums of the tile counts, in place; the number of whole lines; the first line start
 __global__ void __launch_bounds__(1024) phi_text_tiles_kernel(PhiTextArgs A, uint32_t n_tiles)
 {
-    __shared__ uint32_t s_wave[16];
-    __shared__ uint32_t s_carry;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
-    for (uint32_t base = 0; base < n_tiles; base += 1024) {
-        const uint32_t i = base + threadIdx.x;
-        const uint32_t v = i < n_tiles ? A.tile_cnt[i] : 0;
-        const uint32_t before = s_carry + phi_block_excl_scan<16>(v, s_wave);
-        if (i < n_tiles) A.tile_cnt[i] = before;
-        __syncthreads();
-        if (threadIdx.x == 1023) s_carry = before + v;
-        __syncthreads();
-    }
+    __shared__ uint32_t s_w[16];
+    const uint32_t n_nl = phi_carry_scan(A.tile_cnt, (int64_t)n_tiles, A.tile_cnt, s_w);
     if (threadIdx.x == 0) {
-        A.sum->n_nl = s_carry;
+        A.sum->n_nl = n_nl;
         A.ls[0] = A.start;
-        if (s_carry > A.line_cap) atomicOr(&A.sum->err, PHI_TEXT_IRREGULAR_LINES);
+        if (n_nl > A.line_cap) atomicOr(&A.sum->err, PHI_TEXT_IRREGULAR_LINES);
     }
 }
 
@@ -101,20 +73,15 @@ __global__ void __launch_bounds__(256) phi_text_lines_kernel(PhiTextArgs A)
 {
     const uint32_t a0 = A.start & ~15u;
     const uint32_t at = a0 + blockIdx.x * TXT_TILE + threadIdx.x * 16u;
-    const uint4 v = load16(A.buf, at, A.start, A.end);
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-    uint32_t n = 0;
-#pragma unroll
-    for (int j = 0; j < 4; j++) n += __popc(lf_flags(w[j]));
+    uint32_t lf, cr;
+    text_masks(A, at, &lf, &cr);
     __shared__ uint32_t s[4];
-    uint32_t r = A.tile_cnt[blockIdx.x] + phi_block_excl_scan<4>(n, s);
-    if (n == 0) return;
-#pragma unroll
-    for (int j = 0; j < 16; j++) {
-        if (((w[j >> 2] >> (8 * (j & 3))) & 0xFFu) == 0x0au) {
-            if (r < A.line_cap) A.ls[r + 1] = at + (uint32_t)j + 1u;
-            r++;
-        }
+    uint32_t r = A.tile_cnt[blockIdx.x] + phi_block_excl_scan<4>((uint32_t)__popc(lf), s);
+    while (lf) {
+        const uint32_t j = __ffs((int)lf) - 1;
+        lf &= lf - 1;
+        if (r < A.line_cap) A.ls[r + 1] = at + j + 1u;
+        r++;
     }
 }
 
@@ -171,21 +138,9 @@ __global__ void __launch_bounds__(256) phi_text_scan_sums_kernel(PhiTextArgs A)
 __global__ void __launch_bounds__(1024) phi_text_scan_blocks_kernel(PhiTextArgs A)
 {
     const uint32_t n = min(A.sum->n_nl, A.line_cap);
-    const uint32_t nb = (n + SCAN_BLOCK - 1) / SCAN_BLOCK;
-    __shared__ uint64_t s_wave[16];
-    __shared__ uint64_t s_carry;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
-    for (uint32_t base = 0; base < nb; base += 1024) {
-        const uint32_t i = base + threadIdx.x;
-        const uint64_t v = i < nb ? A.blk[i] : 0;
-        const uint64_t before = s_carry + phi_block_excl_scan<16>(v, s_wave);
-        if (i < nb) A.blk[i] = before;
-        __syncthreads();
-        if (threadIdx.x == 1023) s_carry = before + v;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) A.pre[n] = s_carry;
+    __shared__ uint64_t s_w[16];
+    const uint64_t total = phi_carry_scan(A.blk, (int64_t)((n + SCAN_BLOCK - 1) / SCAN_BLOCK), A.blk, s_w);
+    if (threadIdx.x == 0) A.pre[n] = total;
 }
 
 __global__ void __launch_bounds__(256) phi_text_scan_apply_kernel(PhiTextArgs A)
@@ -261,13 +216,8 @@ __global__ void __launch_bounds__(256) phi_text_gather_kernel(PhiTextArgs A)
     uint32_t o = (blockIdx.x * 4u + (threadIdx.x >> 6)) * GATHER_WAVE_BYTES;
     if (A.sum->err || o >= n_out) return;
     const uint32_t o_end = min(n_out, o + GATHER_WAVE_BYTES);
-    // the last line L with (sequence bytes before L) <= o
-    uint32_t lo = 0, hi = n_lines;                       // pre[n_lines] = n_out > o
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if ((uint32_t)A.pre[mid] <= o) lo = mid; else hi = mid;
-    }
-    uint32_t L = lo;
+    // the last line L with (sequence bytes before L: the low half of pre[L]) <= o; pre[n_lines] = n_out > o
+    uint32_t L = phi_last_le_key(n_lines, o, [&A](uint32_t i) { return (uint32_t)A.pre[i]; });
     while (o < o_end) {
         const uint32_t b = (uint32_t)A.pre[L], e = (uint32_t)A.pre[L + 1];
         if (e <= o) { L++; continue; }                   // a line that holds no sequence byte at or after o

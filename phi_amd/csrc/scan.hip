@@ -57,31 +57,15 @@ __global__ void __launch_bounds__(256) phi_scan_apply_kernel(const In *cnt, int6
 }
 
 // ------------------------------------------------------------------ one workgroup, tiles of 4096
-// single-workgroup exclusive scan of per-block counts (off[n] = total).  Tiles of 4096 counts, four consecutive per thread:
-// the loads are coalesced whatever n is -- a chromosome-scale graph scans 1.3 M block counts here, six times per solve
+// single-workgroup exclusive scan of per-block counts (off[n] = total): phi_carry_scan (phi_wave.h), whose tiles keep the loads
+// coalesced whatever n is -- a chromosome-scale graph scans 1.3 M block counts here, six times per solve
 // (a thread summing its own contiguous share of the array, as before, read with a stride of 5 KB between lanes: 4.4 ms a call).
 template <class In>
 __global__ void __launch_bounds__(1024) phi_scan_tiles_kernel(const In *__restrict__ cnt, int64_t n, int64_t *__restrict__ off)
 {
     __shared__ int64_t s_w[16];
-    int64_t carry = 0;                                    // everything before the tile
-    for (int64_t base = 0; base < n; base += 4096) {
-        const int64_t i0 = base + 4 * (int64_t)threadIdx.x;
-        In v[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) v[j] = i0 + j < n ? cnt[i0 + j] : 0;
-        const int64_t c = (int64_t)v[0] + v[1] + v[2] + v[3];
-        int64_t tile;
-        int64_t run = carry + phi_block_excl_scan<16>(c, s_w, &tile);
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            if (i0 + j < n) off[i0 + j] = run;
-            run += v[j];
-        }
-        carry += tile;
-        __syncthreads();                                  // (s_w is written again in the next turn)
-    }
-    if (threadIdx.x == 0) off[n] = carry;
+    const int64_t total = phi_carry_scan(cnt, n, off, s_w);
+    if (threadIdx.x == 0) off[n] = total;
 }
 
 template <class In>

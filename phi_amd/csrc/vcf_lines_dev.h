@@ -11,6 +11,7 @@
 #include "phi_ctx.h"
 #include "phi_wave.h"
 #include "dev_run.h"
+#include "text_bytes.h"
 
 #define BIX_T 256                       // threads per workgroup
 #define BIX_LANE 16                     // bytes per lane: one 16-byte load
@@ -78,11 +79,7 @@ __device__ __forceinline__ int bix_interval(const BixLists &L, const BixLine &l,
     const int64_t beg = pos > 0 ? pos - 1 : 0;
     int64_t end = beg + (t[3] - t[2] - 1);
     int bad = 0;
-    int64_t lo = l.end_lo, hi = l.end_hi;               // the first END place at or behind INFO's first byte
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if (L.end_pos[mid] < t[6] + 1) lo = mid + 1; else hi = mid;
-    }
+    const int64_t lo = phi_first_ge(L.end_pos, l.end_lo, l.end_hi, t[6] + 1);     // the first END place at or behind INFO's first byte
     if (lo < l.end_hi && L.end_pos[lo] < info_end) {
         const int64_t a = L.end_pos[lo] + 4;
         int64_t b = a;

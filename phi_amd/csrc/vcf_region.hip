@@ -48,16 +48,6 @@ struct RgnQuery {                                       // device pointers and t
     int64_t done;                                       // lines that begin before it were looked at by an earlier batch
 };
 
-// the first index in [lo, hi) whose position is >= p
-__device__ __forceinline__ int64_t rgn_lower(const int64_t *__restrict__ pos, int64_t lo, int64_t hi, int64_t p)
-{
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if (pos[mid] < p) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 // keep[i], and for a kept line where it begins in the batch's text and its bytes with the line feed; seen: lines inside a range
 __global__ void __launch_bounds__(256) phi_rgn_lines_kernel(BixLists L, int64_t n_lines, RgnQuery Q, uint8_t *__restrict__ keep, int64_t *__restrict__ src,
                                                             int32_t *__restrict__ len, unsigned long long *__restrict__ err, unsigned long long *__restrict__ seen)
@@ -71,11 +61,7 @@ __global__ void __launch_bounds__(256) phi_rgn_lines_kernel(BixLists L, int64_t 
         if (s_g >= Q.done && Q.n_ranges > 0) {
             // the last range that begins before the line's end (an empty line: at or before its only position)
             const int64_t bound = e_g > s_g ? e_g : s_g + 1;
-            int64_t lo = 0, hi = Q.n_ranges;
-            while (lo < hi) {
-                const int64_t mid = lo + ((hi - lo) >> 1);
-                if (Q.range[2 * mid] < bound) lo = mid + 1; else hi = mid;
-            }
+            const int64_t lo = phi_first_ge_key((int64_t)0, (int64_t)Q.n_ranges, bound, [&Q](int64_t r) { return Q.range[2 * r]; });
             if (lo > 0) {
                 const int64_t p0 = Q.range[2 * (lo - 1)], p1 = Q.range[2 * (lo - 1) + 1];
                 const int64_t start = p0 > s_g ? p0 : s_g;
@@ -83,8 +69,8 @@ __global__ void __launch_bounds__(256) phi_rgn_lines_kernel(BixLists L, int64_t 
                     mine = 1;
                     if (p0 > s_g) {                     // the range begins inside what the newlines call one line: its line begins there
                         l.s = p0 - Q.g0;
-                        l.tab_lo = rgn_lower(L.tab_pos, l.tab_lo, l.tab_hi, l.s);
-                        l.end_lo = rgn_lower(L.end_pos, l.end_lo, l.end_hi, l.s);
+                        l.tab_lo = phi_first_ge(L.tab_pos, l.tab_lo, l.tab_hi, l.s);
+                        l.end_lo = phi_first_ge(L.end_pos, l.end_lo, l.end_hi, l.s);
                     }
                     const unsigned long long at = (unsigned long long)(Q.g0 + l.s) << 8;
                     if (l.e > l.s && L.text[l.s] == '#') {}
@@ -128,23 +114,11 @@ __global__ void __launch_bounds__(256) phi_rgn_copy_kernel(const uint8_t *__rest
 {
     const int64_t o = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 16;
     if (o >= total) return;
-    int64_t lo = 0, hi = n_keep;                        // the last line that begins at or before o (koff[0] == 0)
-    while (hi - lo > 1) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if (koff[mid] <= o) lo = mid; else hi = mid;
-    }
-    int64_t k = lo;
+    int64_t k = phi_last_le(koff, n_keep, o);           // the last line that begins at or before o (koff[0] == 0)
     const int64_t a = ksrc[k] + (o - koff[k]);
     if (o + 16 <= koff[k + 1] && ksrc[k] + (koff[k + 1] - koff[k]) <= n) {      // inside one line whose line feed stands in the text
-        const int64_t base = a & ~(int64_t)15;
-        const uint4 A = *(const uint4 *)(text + base), B = *(const uint4 *)(text + base + 16);
-        uint64_t q0 = A.x | ((uint64_t)A.y << 32), q1 = A.z | ((uint64_t)A.w << 32), q2 = B.x | ((uint64_t)B.y << 32);
-        const uint64_t q3 = B.z | ((uint64_t)B.w << 32);
-        int bits = (int)(a & 15) * 8;
-        if (bits >= 64) { q0 = q1; q1 = q2; q2 = q3; bits -= 64; }
-        const uint64_t w0 = bits ? (q0 >> bits) | (q1 << (64 - bits)) : q0;
-        const uint64_t w1 = bits ? (q1 >> bits) | (q2 << (64 - bits)) : q1;
-        *(uint4 *)(out + o) = uint4{(uint32_t)w0, (uint32_t)(w0 >> 32), (uint32_t)w1, (uint32_t)(w1 >> 32)};
+        const PhiText16 v = phi_load16_unaligned(text, a);
+        *(uint4 *)(out + o) = uint4{v.x, v.y, v.z, v.w};
         return;
     }
     uint32_t w[4] = {0, 0, 0, 0};

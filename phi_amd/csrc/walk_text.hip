@@ -22,36 +22,22 @@
 #include "phi_ctx.h"
 #include "phi_dev.h"
 #include "phi_wave.h"
+#include "text_bytes.h"
 
 namespace {
 
 __device__ __forceinline__ bool is_step(unsigned c) { return c == '>' || c == '<'; }
 
-// walk of a tile: tile0[w] <= t < tile0[w + 1]
-__device__ __forceinline__ int walk_of_tile(const int64_t *__restrict__ tile0, int n_walks, int64_t t)
-{
-    int lo = 0, hi = n_walks;
-    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (tile0[mid] <= t) lo = mid; else hi = mid; }
-    return lo;
-}
-
+// (the walk of tile t is the last w with tile0[w] <= t: phi_last_le)
 __global__ void __launch_bounds__(256) wt_tab_kernel(const uint8_t *__restrict__ text, const int64_t *__restrict__ tile0, int n_walks, int64_t n_tiles,
                                                      unsigned long long *__restrict__ walk_end)
 {
     for (int64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
-        const int w = walk_of_tile(tile0, n_walks, t);
+        const int w = phi_last_le(tile0, n_walks, t);
         const int64_t base = t * WT_TILE + 16 * (int64_t)threadIdx.x;
         if ((unsigned long long)base >= walk_end[w]) continue;           // (racy read of a value that only shrinks: a stale one only costs a look)
-        const uint4 v = *reinterpret_cast<const uint4 *>(text + base);
-        const uint32_t x[4] = {v.x, v.y, v.z, v.w};
-        int first = -1;
-#pragma unroll
-        for (int q = 3; q >= 0; q--) {
-            const uint32_t y = x[q] ^ 0x09090909u;
-            if ((y - 0x01010101u) & ~y & 0x80808080u)
-                for (int j = 3; j >= 0; j--) if (((x[q] >> (8 * j)) & 0xFFu) == '\t') first = 4 * q + j;
-        }
-        if (first >= 0) atomicMin(&walk_end[w], (unsigned long long)(base + first));
+        const uint32_t tabs = phi_eq16(phi_load16(text, base), '\t');
+        if (tabs) atomicMin(&walk_end[w], (unsigned long long)(base + __ffs((int)tabs) - 1));
     }
 }
 
@@ -59,17 +45,11 @@ __global__ void __launch_bounds__(256) wt_tab_kernel(const uint8_t *__restrict__
 __device__ __forceinline__ uint32_t step_mask16(const uint8_t *__restrict__ text, int64_t base, int64_t end, bool *rev)
 {
     if (base >= end) return 0;
-    const uint4 v = *reinterpret_cast<const uint4 *>(text + base);
-    const uint32_t x[4] = {v.x, v.y, v.z, v.w};
-    uint32_t m = 0;
-#pragma unroll
-    for (int q = 0; q < 4; q++)
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const unsigned ch = (x[q] >> (8 * j)) & 0xFFu;
-            if (is_step(ch) && base + 4 * q + j < end) { m |= 1u << (4 * q + j); *rev |= ch == '<'; }
-        }
-    return m;
+    const PhiText16 v = phi_load16(text, base);
+    const uint32_t valid = phi_valid16(base, base, end);
+    const uint32_t back = phi_eq16(v, '<') & valid;
+    *rev |= back != 0;
+    return (phi_eq16(v, '>') & valid) | back;
 }
 
 __global__ void __launch_bounds__(256) wt_count_kernel(const uint8_t *__restrict__ text, const int64_t *__restrict__ tile0, int n_walks, int64_t n_tiles,
@@ -79,7 +59,7 @@ __global__ void __launch_bounds__(256) wt_count_kernel(const uint8_t *__restrict
     for (int64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
         if (threadIdx.x == 0) s_cnt = 0;
         __syncthreads();
-        const int w = walk_of_tile(tile0, n_walks, t);
+        const int w = phi_last_le(tile0, n_walks, t);
         bool rev = false;
         const uint32_t m = step_mask16(text, t * WT_TILE + 16 * (int64_t)threadIdx.x, (int64_t)walk_end[w], &rev);
         const int n = phi_wave_sum((int)__popc(m));
@@ -103,7 +83,7 @@ __global__ void __launch_bounds__(256) wt_parse_kernel(WtParseArgs A)
 {
     __shared__ int s_w[4];
     for (int64_t t = blockIdx.x; t < A.n_tiles; t += gridDim.x) {
-        const int w = walk_of_tile(A.tile0, A.n_walks, t);
+        const int w = phi_last_le(A.tile0, A.n_walks, t);
         const int64_t end = (int64_t)A.walk_end[w];
         const int64_t base = t * WT_TILE + 16 * (int64_t)threadIdx.x;
         bool rev = false;

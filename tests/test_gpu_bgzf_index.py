@@ -201,6 +201,52 @@ def test_the_near_side_of_every_limit(phi, name):
     _indexed_vcf(phi, ACCEPTED[name])
 
 
+# ------------------------------------------------------------------ 4b. END= across the borders of the marks' lanes
+
+def _end_text(k, border, n_mod=None, final_newline=True):
+    """A handful of records with END= in INFO, the ID of each padded so that a multiple of `border` lies in front of byte k of
+    the five bytes (tab or ';', 'E', 'N', 'D', '='); then one more padded so that len(text) % 16 == n_mod"""
+    text, pos = HEAD, 100
+    for form in (b"END=%d", b"X=1;END=%d", b"END=%d;Y=2", b"SVTYPE=DEL;END=%d"):
+        for pad in range(1, border + 1):
+            r = b"\t".join([b"c1", b"%d" % pos, b"i" * pad, b"A", b"C", b".", b"PASS", form % (pos + 50)]) + b"\n"
+            if (len(text) + r.index(b"END=") - 1 + k) % border == 0:
+                break
+        else:
+            raise AssertionError("no padding found")
+        text, pos = text + r, pos + 100
+    if n_mod is not None:
+        for pad in range(1, 17):
+            r = b"\t".join([b"c1", b"%d" % pos, b"i" * pad, b"A", b"C", b".", b"PASS", b"END=%d" % (pos + 7)]) + b"\n"
+            if (len(text) + len(r) - (not final_newline)) % 16 == n_mod:
+                break
+        text += r
+    return text if final_newline else text[:-1]
+
+
+END_CASES = {"lane_border_byte_%d" % k: (k, 16, None, True) for k in range(5)}
+END_CASES.update({
+    "workgroup_border": (1, 4096, None, True),          # the delimiter the last byte of a workgroup's 4096, END= in the next one's
+    "n_mod_16_is_0": (2, 16, 0, True), "n_mod_16_is_1": (3, 16, 1, True), "n_mod_16_is_15": (4, 16, 15, True),
+    "no_final_newline": (1, 16, 1, False),
+})
+
+
+@pytest.mark.parametrize("name", sorted(END_CASES))
+def test_end_places_across_lane_and_workgroup_borders(phi, name):
+    """The marks take the text 16 bytes a lane, 4096 a workgroup: "END=" with the tab or ';' in front of it split by a border
+    at each of its bytes, texts that end 0, 1 and 15 bytes into a lane, one without its last line feed.  The index is the
+    per-line writer's, whose ends here all come from END (POS + 50, not POS + len(REF))."""
+    k, border, n_mod, final_newline = END_CASES[name]
+    text = _end_text(k, border, n_mod, final_newline)
+    assert text.endswith(b"\n") == final_newline and (n_mod is None or len(text) % 16 == n_mod)
+    assert all((text.index(b"END=%d" % (p + 50)) - 1 + k) % border == 0 for p in (100, 200, 300, 400))
+    recs = [T.record_of(ln) for _, _, ln in T.lines_of(text) if not ln.startswith(b"#")]
+    assert [r[2] - r[1] for r in recs[:4]] == [51] * 4
+    _, _, info = _indexed_vcf(phi, text)
+    assert info["records"] == len(recs)
+
+
 # ------------------------------------------------------------------ 5. empty inputs
 
 def test_texts_without_a_record(phi):

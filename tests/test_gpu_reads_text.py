@@ -132,6 +132,27 @@ def test_block_boundary_vectors_through_the_device_splitter(ctx):
             assert len(got) == c["n_records"] and hashlib.sha256(b"\0".join(got)).hexdigest() == c["sha256_seqs"], (c["tail_hex"], c["size"], call)
 
 
+def test_the_window_of_a_chunk_at_every_offset_of_a_lane(ctx):
+    """The kernels read [carry | chunk] 16 aligned bytes a lane, and the window begins where the carry does.  A FASTQ in two
+    calls, the first of which ends 0 .. 16 bytes into the third record: the carry, and with it the second window's first byte,
+    takes every offset of a lane (at 0 the first window's last byte is a line feed).  Then a second call that begins with a
+    line feed and no carry before it -- an empty line where a header should stand: irregular, and the host reader's from there.
+    Device + host rest == the host reader's records of the whole text."""
+    rec = [b"@r%d some comment here\n" % i + s + b"\n+\n" + b"I" * len(s) + b"\n" for i, s in enumerate((b"ACGTACGTAC", b"GGTTAACC", b"TTGACCA", b"ACGTTGCAAGT"))]
+    text = b"".join(rec)
+    want = kseq_records(text)
+    assert len(want) == 4 and len(rec[2]) > 16
+    for r in range(17):
+        call = len(rec[0]) + len(rec[1]) + r
+        assert 2 * call >= len(text)
+        got, taken, irregular = split_on_device(ctx, text, call, max_chunk=max(64, call))
+        assert got == want and not irregular, r
+    text = rec[0] + rec[1] + b"\n" + rec[2] + rec[3]
+    call = len(rec[0]) + len(rec[1])
+    got, taken, irregular = split_on_device(ctx, text, call, max_chunk=max(64, call))
+    assert got == kseq_records(text) and len(got) == 4 and irregular
+
+
 def _random_text(rng):
     """FASTA / FASTQ text, mostly regular, with the anomalies a reads file can hold mixed in."""
     fastq = rng.random() < 0.5

@@ -176,6 +176,42 @@ def test_irregular_walk_text_is_refused_whole_and_the_host_resolves_it(ctx_facto
     assert ctx.index_stats()["n_entries"] == len(want.walk_vtx)
 
 
+LANE_CASES = {
+    # a kernel lane takes 16 bytes of a walk field, which begins on a lane border: byte 15 is a lane's last, byte 16 the next one's first.
+    # (first walk, the walk looked at, what follows its byte 15 / 16; a reversed walk needs its segments forward in another walk)
+    "tags from byte 15": (">s1>s2>s3", ">s1>s2>s3>s4>s5", "\tXX:Z:a>s3<s9>c\tYY:i:7", 15),
+    "tags from byte 16": (">s1>s2>s3", ">s2>s4>s6>s8>s10", "\tXX:Z:a>s3<s9>c\tYY:i:7", 16),
+    "a reverse step at byte 15": (">s7>s8>s9>s10>s11>s12", "<s12<s11<s10<s9", "<s8<s7", 15),
+    "a reverse step at byte 16": (">s7>s9>s10>s11>s12>s13", "<s13<s12<s11<s10", "<s9<s7", 16),
+}
+
+
+@pytest.mark.parametrize("case", sorted(LANE_CASES))
+def test_a_tab_and_a_reverse_step_on_either_side_of_a_lane_border(ctx_factory, tmp_path, case):
+    """The tab that ends a walk (tags follow) and a '<' step as the last byte of a 16-byte lane and as the first byte of the
+    next: the tags are no steps, and the reverse step makes the device refuse the graph whole, as anywhere else."""
+    from phi_amd import ilp_index as H
+    first, walk, behind, at = LANE_CASES[case]
+    assert len(walk) == at
+    segs, links = _chain(13)
+    path = _write(tmp_path, "lane.gfa", segs, links, [first, walk + behind, ">s3>s5"])
+    ctx = _ctx(ctx_factory)
+    if behind.startswith("\t"):
+        want = H.Graph(_write(tmp_path, "lane_plain.gfa", segs, links, [first, walk, ">s3>s5"]))
+        g, on_dev = _device_walks(ctx, path)
+        assert on_dev
+        _same_graph(g, want)
+        assert np.array_equal(ctx.walk_entries(), want.walk_vtx)
+    else:
+        want = H.Graph(path)
+        g = H.DeferredGraph(path)
+        assert not g.resolve_on_device(ctx) and g.irregular & 1
+        assert ctx.walk_entries().size == 0                   # nothing was left behind
+        g.resolve_on_host()
+        _same_graph(g, want)
+        assert g.walk_vtx.tolist() == want.walk_vtx.tolist()
+
+
 def test_names_of_another_form_never_reach_the_device(ctx_factory, tmp_path):
     """Segment names that are not <prefix><number> (or a W-line standing before an S-line): the reader has no direct name
     index to give (phi_graph_name_index = PHI_HOST_ERR_UNSUPPORTED) and the walks are the host's."""
